@@ -160,19 +160,6 @@ def load() -> C.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    # one hardware queue per stream of the step pipeline (see alpharat_hip.hip "hardware queues"): effective when the
-    # HIP runtime has not been initialised in this process yet
-    # -- so it is only set when nothing can have brought the runtime up before (torch with an initialised device has)
-    import sys
-
-    torch = sys.modules.get("torch")
-    runtime_up = bool(torch is not None and getattr(torch, "cuda", None) is not None and torch.cuda.is_initialized())
-    if not runtime_up:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-    elif "GPU_MAX_HW_QUEUES" not in os.environ:
-        # nobody asked for more queues before the runtime came up: it has its default four, and setting the variable now
-        # would only make the library believe otherwise -- it then keeps one group of games (no extra streams)
-        os.environ.setdefault("AR_HW_QUEUES_UNKNOWN", "1")
     if not LIB_PATH.exists():
         raise ImportError(
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

@@ -39,23 +39,14 @@ using namespace ar;
 // hardware queues
 // ------------------------------------------------------------------------------------------------
 // The step pipeline of a large run keeps four streams busy at once (two groups of games x {walk + evaluator, tree
-// reuse}; group 0 runs on the engine's own stream). The HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default:
-// streams that share a queue serialise, and the pipeline runs 1.1-1.7x slower than with one queue per stream
-// (measured). The variable is read when the runtime initialises, so it is set when this
-// library is loaded -- unless the host has chosen a value itself. A process that brought the runtime up earlier
-// (e.g. torch imported first) has to export it itself: bench.py does.
-// What is known about the queues is what the variable said when this library was loaded: a value set later (by this
-// constructor, or by anyone) does not reach a runtime that is already up. AR_HW_QUEUES_UNKNOWN=1 (set by
-// alpharat_amd/_lib.py when torch has initialised a device before the library is loaded) says exactly that.
+// reuse}; group 0 runs on the engine's own stream). The HIP runtime maps streams onto its hardware queues (four by
+// default, GPU_MAX_HW_QUEUES): streams that share a queue serialise, and the pipeline runs 1.1-1.7x slower than with
+// one queue per stream (measured). The number of queues is the host's choice, made before the
+// runtime initialises; the library never sets it. What is known about the queues is what the variable said when this
+// library was loaded.
 static int g_hw_queues_at_load = 0;
-__attribute__((constructor)) static void ar_more_hw_queues() {
+__attribute__((constructor)) static void ar_read_hw_queues() {
     const char* e = getenv("GPU_MAX_HW_QUEUES");
-    if (getenv("AR_HW_QUEUES_UNKNOWN")) {
-        g_hw_queues_at_load = e ? atoi(e) : 4;  // whatever the runtime came up with: not ours to change now
-        return;
-    }
-    if (!e) setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    e = getenv("GPU_MAX_HW_QUEUES");
     g_hw_queues_at_load = e ? atoi(e) : 4;
 }
 static int hw_queues() { return g_hw_queues_at_load; }

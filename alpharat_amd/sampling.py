@@ -231,10 +231,14 @@ class SelfPlaySession:
 
         with SelfPlaySession(width=7, ..., num_games=UNBOUNDED, concurrent_games=65536) as s:
             window = s.step(1024)     # SelfPlayStats of what happened inside these 1024 batch steps
+
+    ``record_filter(game_index) -> bool`` (with ``on_game``): only the records it accepts are copied out for ``on_game``
+    (the copy takes ~70 us of host time per game, which a long run keeping a few games need not pay for all of them).
     """
 
     def __init__(self, *, on_game: Callable[[dict], None] | None = None, progress: SelfPlayProgress | None = None,
-                 onnx_model_path: str | None = None, **kw: Any) -> None:
+                 onnx_model_path: str | None = None, record_filter: Callable[[int], bool] | None = None,
+                 **kw: Any) -> None:
         L = _lib.load()
         defaults = dict(cheese_symmetric=True, maze_type="open", positions="corners", wall_density=0.7, mud_density=0.1,
                         maze_symmetric=True, batch_size=8, c_puct=1.5, fpu_reduction=0.2, force_k=2.0, noise_epsilon=0.0,
@@ -249,7 +253,11 @@ class SelfPlaySession:
         p = _params(**defaults)
         self._sink = _lib.ArGameSink()
         if on_game is not None:
-            self._sink = _lib.ArGameSink(lambda _u, v: on_game(record_to_dict(v.contents)))
+            def sink(_u, v):
+                if record_filter is None or record_filter(int(v.contents.game_index)):
+                    on_game(record_to_dict(v.contents))
+
+            self._sink = _lib.ArGameSink(sink)
         self._progress = progress
         prog = C.byref(progress._c) if progress is not None else None
         self._h = C.c_void_p()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the self-play MCTS sampling path on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (config.workload): BASELINE config 3 -- 7x7 open PyRat, 10 symmetric cheese, 50 turns,
@@ -29,16 +29,15 @@ from __future__ import annotations
 
 import argparse
 import hashlib
+import inspect
 import json
 import os
 import sys
+import tempfile
 import time
 from pathlib import Path
 
 T_START = time.perf_counter()
-# one hardware queue per stream of the sampler's step pipeline; must be in the environment before anything (torch in
-# multi-rank runs) initialises the HIP runtime
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
@@ -61,6 +60,11 @@ WORKLOADS = {
     "cnn": (dict(c_puct=0.512, fpu_reduction=0.459, force_k=0.103, noise_epsilon=0.25, noise_concentration=10.83), 4096, 16,
             "4096 sims (tuned constants, batch 16, noise 0.25), PyRatCNN c64 res,res,gpool(32) random weights"),
 }
+# --dump-outputs: sampled games (at 7x7 at most 50 positions of 90 values each: < 20 MB in all), the sample's seed, the
+# bound on the batch steps that may follow the timed ones until every sampled game has finished, and the record fields
+# that hold one board per game (every other array field has one row per position)
+DUMP_GAMES, DUMP_SEED, DUMP_MAX_BATCH_STEPS_AFTER = 1024, 0, 32768
+DUMP_BOARD_KEYS = ("maze", "initial_cheese", "cheese_outcomes")
 # sources whose change invalidates a committed PMC traffic measurement of the tree kernels
 TRAFFIC_SOURCES = ("dev_search.h", "dev_gatherw.h", "dev_gather8.h", "dev_backup16.h", "dev_engine.h", "dev_rng.h", "slot_layout.h", "alpharat_hip.hip")
 
@@ -118,14 +122,13 @@ def make_mlp_blob(path: Path) -> Path:
     return write_blob(path, "mlp", 7, 7, t)
 
 
-def weights_for(evaluator: str, rank: int) -> str | None:
+def weights_for(evaluator: str, scratch: Path) -> str | None:
+    """The evaluator's weight blob. The MLP's seeded random weights are written to `scratch`, a directory of this
+    process (the checkout may be read-only); every rank writes the same bytes."""
     if evaluator == "uniform":
         return None
     if evaluator == "mlp":
-        blob = ROOT / "gpurun_out" / "bench_mlp_7x7_h256.arnet"
-        if rank == 0:
-            make_mlp_blob(blob)
-        return str(blob)
+        return str(make_mlp_blob(scratch / "bench_mlp_7x7_h256.arnet"))
     # the seeded random networks of the parity tests (tools/gen_net_golden.py)
     name = {"symmetric": "symmetric_7x7_h256", "cnn": "cnn_gpool_7x7_c64"}[evaluator]
     return str(ROOT / "tests" / "golden" / "nets" / f"{name}.arnet")
@@ -172,14 +175,13 @@ def under_profiler() -> str | None:
     return None
 
 
-def full_launch_leg(evaluator: str, resident: int, batch_steps: int, device_index: int) -> dict:
+def full_launch_leg(evaluator: str, resident: int, batch_steps: int, device_index: int, weights: str | None) -> dict:
     """The extra leg: the same workload with the games as ONE group, i.e. one gather launch over all resident games per
     batch step. Runs in this process, after the timed session is closed and its device memory released (the group
     count is a per-session choice the library reads from AR_GROUPS when a session opens)."""
     from alpharat_amd.sampling import UNBOUNDED, SelfPlaySession
 
     search, sims, batch, _ = WORKLOADS[evaluator]
-    weights = weights_for(evaluator, 0)
     os.environ["AR_GROUPS"] = "1"
     try:
         return _full_launch_session(evaluator, resident, batch_steps, device_index, search, sims, batch, weights)
@@ -226,7 +228,11 @@ def main() -> int:
     ap.add_argument("--no-full-launch", action="store_true",
                     help="skip the extra leg that times the gather kernel launched over all resident games at once")
     ap.add_argument("--deadline", type=float, default=480.0,
-                    help="seconds after process start at which the timed loop stops early and reports the steps done")
+                    help="seconds after process start after which the extra legs (full launch, CPU baseline) are skipped; "
+                         "the timed loop always runs --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"write the game records of a fixed, seeded sample of {DUMP_GAMES} games of the timed session to "
+                         "DIR/<field>.npy (float32 arrays, float64 per-game scalars), to compare builds output for output")
     ap.add_argument("--warmup-batch-steps", type=int, default=0,
                     help="warm up for this many batch steps instead of --warmup steps (the extra evaluators' lines: a game of "
                          "config 4 lasts about 2900 batch steps, of config 5 about 4400; a steady-state window starts after that)")
@@ -276,7 +282,8 @@ def main() -> int:
         args.batch_steps = {"symmetric": 128, "cnn": 64}.get(args.evaluator, 1024)
     if args.resident <= 0:
         args.resident = 16384 if args.evaluator == "cnn" else 131072
-    weights = weights_for(args.evaluator, rank)
+    scratch = tempfile.TemporaryDirectory(prefix=f"ar_bench_r{rank}_")
+    weights = weights_for(args.evaluator, Path(scratch.name))
     if dist is not None:
         dist.barrier()
 
@@ -294,11 +301,24 @@ def main() -> int:
     rec_dir = None
     rec_games = [0]
     extra = {}
-    if args.record:
-        import tempfile
+    sample = dump_sample(args.resident, rank << 28) if args.dump_outputs else set()
+    kept = {}
 
+    def on_game(g):
+        rec_games[0] += 1
+        if g["game_index"] in sample:
+            kept[g["game_index"]] = g
+
+    if args.record:
         rec_dir = tempfile.mkdtemp(prefix=f"ar_bench_rec_r{rank}_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
-        extra = dict(output_dir=rec_dir, on_game=lambda g: rec_games.__setitem__(0, rec_games[0] + 1))
+        extra = dict(output_dir=rec_dir, on_game=on_game)
+    elif sample:
+        extra = dict(on_game=on_game)
+        # only the sampled games' records are copied out to Python: the timed steps then pay for a record build and a
+        # callback per finished game, not for the copy (~70 us each). A build whose sessions lack the filter (this script
+        # also measures earlier builds) copies every record out: the same dump, slower timed steps.
+        if "record_filter" in inspect.signature(SelfPlaySession).parameters:
+            extra["record_filter"] = sample.__contains__
     session = SelfPlaySession(**GAME, num_games=UNBOUNDED, simulations=sims, batch_size=batch,
                               weights_path=weights, seed=0, first_game_index=rank << 28, concurrent_games=args.resident,
                               device_index=local_rank, **{"output_dir": None, **extra}, **search)
@@ -323,16 +343,24 @@ def main() -> int:
         w = session.step(args.batch_steps)
         acc = w if acc is None else _sum_windows(acc, w)
         done += 1
-        # insurance against a kill: a provisional line after every timed step (stderr + a file; stdout carries
-        # exactly one line, the final one)
+        # insurance against a kill: a provisional line on stderr after every timed step (stdout carries exactly one
+        # line, the final one)
         _progress(rank, {"provisional": True, "steps_done": done, "value": acc.total_simulations * world / (time.perf_counter() - t0),
                          "unit": "simulations/s (this rank x world)"})
-        if time.perf_counter() - T_START > args.deadline and done < args.steps:
-            print(f"bench: deadline of {args.deadline:.0f} s reached after {done} of {args.steps} timed steps", file=sys.stderr)
-            break
     sync()
     elapsed = time.perf_counter() - t0
+    after = 0
+    if sample:
+        # sampled games still being played when the timed steps end are played to their end here, outside the timed region
+        while len(kept) < len(sample) and after < DUMP_MAX_BATCH_STEPS_AFTER:
+            session.step(1024)
+            after += 1024
     session.close()
+    if sample:
+        if len(kept) < len(sample):
+            raise RuntimeError(f"--dump-outputs: {len(sample) - len(kept)} of the {len(sample)} sampled games did not finish "
+                               f"within {after} batch steps after the timed steps")
+        dump_records(Path(args.dump_outputs), [kept[i] for i in sorted(kept)], f"rank{rank}_" if world > 1 else "")
     stats = acc
     if rec_dir is not None:
         import shutil
@@ -433,6 +461,8 @@ def main() -> int:
                    "games_finished": int(tot["games"]), "positions_finished": int(tot["positions"])},
         "timing": {"session_open_s": t_open, "timed_s": elapsed},
     }
+    if args.dump_outputs:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "games": len(kept), "batch_steps_after_timed": after}
     if args.record:
         out["record"] = {"what": "every finished game's record built on the host (sink callback) and written as bundles to a "
                                  "tmpfs inside the timed region", "games_in_callback": rec_games[0], "bundle_files": rec_files}
@@ -449,7 +479,7 @@ def main() -> int:
                 from alpharat_amd.sampling import release_device_memory
 
                 release_device_memory(local_rank)  # (the arena block this process keeps cached between sessions)
-                out["roofline"]["full_launch"] = full_launch_leg(args.evaluator, args.resident, args.batch_steps, local_rank)
+                out["roofline"]["full_launch"] = full_launch_leg(args.evaluator, args.resident, args.batch_steps, local_rank, weights)
             except Exception as e:  # noqa: BLE001 -- the extra leg never costs the headline line
                 out["roofline"]["full_launch"] = {"error": str(e)}
     if not args.no_cpu_baseline and args.cpu_secs > 0 and world == 1:  # a reported baseline, timed on rank 0 at N=1 only
@@ -480,18 +510,36 @@ def _sum_windows(a, b):
     return SelfPlayStats(**kw)
 
 
+def dump_sample(resident: int, first_game_index: int) -> set:
+    """Game indices whose records --dump-outputs writes: a seeded sample of the first `resident` games of the session.
+    Which games finish inside a given step depends on scheduling (parked gathers, games waiting for tree pages); what a
+    game computes does not, so a sample chosen by index compares across runs and builds."""
+    import numpy as np
+
+    rng = np.random.default_rng(DUMP_SEED)
+    return {first_game_index + int(i) for i in rng.choice(resident, min(DUMP_GAMES, resident), replace=False)}
+
+
+def dump_records(out_dir: Path, games: list, prefix: str = "") -> None:
+    """One file per record field, games in index order: scalars as float64 (one entry per game), the per-game boards
+    stacked, the per-position arrays concatenated over the games (`n` gives each game's rows), both as float32."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for key, v in games[0].items():
+        if not isinstance(v, np.ndarray):
+            a = np.array([g[key] for g in games], np.float64)
+        elif key in DUMP_BOARD_KEYS:
+            a = np.stack([g[key] for g in games]).astype(np.float32)
+        else:
+            a = np.concatenate([g[key] for g in games]).astype(np.float32)
+        np.save(out_dir / f"{prefix}{key}.npy", a)
+
+
 def _progress(rank: int, line: dict) -> None:
     if rank != 0:
         return
-    s = json.dumps(line)
-    print(s, file=sys.stderr, flush=True)
-    try:
-        d = ROOT / "gpurun_out"
-        d.mkdir(exist_ok=True)
-        with open(d / "bench_progress.jsonl", "a") as f:
-            f.write(s + "\n")
-    except OSError:
-        pass
+    print(json.dumps(line), file=sys.stderr, flush=True)
 
 
 if __name__ == "__main__":

@@ -248,6 +248,18 @@ def test_session_slices_play_the_same_games_and_windows_add_up():
     assert all(w.steps <= 37 for w in windows) and windows[0].steps == 37
     # work is reported per finished move, not per finished game: the first window already has simulations
     assert windows[0].total_simulations > 0 and windows[0].total_positions > 0 and windows[0].total_games == 0
+    # record_filter: on_game receives the records of the accepted games only, and the same records
+    kept = {}
+    with SelfPlaySession(on_game=lambda g: kept.__setitem__(g["game_index"], g), record_filter=lambda i: i % 3 == 1, **kw) as s:
+        while not s.finished:
+            s.step(1024)
+    assert sorted(kept) == list(range(1, 70, 3))
+    for i, g in kept.items():
+        for k, v in g.items():
+            if isinstance(v, np.ndarray):
+                np.testing.assert_array_equal(v, whole[i][k], err_msg=f"filtered game {i} {k}")
+            else:
+                assert v == whole[i][k], (i, k)
 
 
 def test_unbounded_session_keeps_every_slot_busy():
