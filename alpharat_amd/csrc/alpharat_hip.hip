@@ -479,9 +479,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 // the same eighth of the games waiting in all of them. Which wavefront walks a game never changes what its walk does.
 // Leaves are left in the games' scratch (k_pack_leaves appends them to the evaluator queue).
 // Ring item: context (bits 0..6), BEGIN flag (bit 7: the context wants a game), visit slot, siblings behind it.
+// At most 168 VGPRs (the lane state takes 160-166, no scratch; the attribute is a guard): three wavefronts per SIMD. With
+// G = 32 and two records per game the LDS (12 952 B + the maze stage) holds twelve per CU (profiles/r04_resource_usage.txt).
+enum { GW_RECS = 2 };           // position records per game in LDS (R); a parent that finds them taken uses its game's scratch
+enum { GW_WAVES_PER_CU = 11 };  // default persistent grid (AR_GW_WAVES overrides it)
 template <int NW, int G, int R>
-__global__ void __launch_bounds__(64) k_gatherw(Slot<NW>* slots, uint32_t n_slots, SearchCfg cfg, Bases B, uint32_t first,
-                                                uint32_t phase, uint32_t accept_ready, uint32_t pass_limit, uint32_t rot) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3)))
+k_gatherw(Slot<NW>* slots, uint32_t n_slots, SearchCfg cfg, Bases B, uint32_t first, uint32_t phase, uint32_t accept_ready,
+          uint32_t pass_limit, uint32_t rot) {
     static_assert((G & (G - 1)) == 0 && G <= 64, "the ring is a power of two; a context number fits a ring item");
     static_assert(sizeof(GwRec<NW>) == (sizeof(State<NW>) + 16 + 7) / 8 * 8, "slot_layout.h sizes the spill area");
     typedef GwShared<NW, G, R> Sh;
@@ -515,8 +520,9 @@ __global__ void __launch_bounds__(64) k_gatherw(Slot<NW>* slots, uint32_t n_slot
     }
     uint32_t head = 0;
 #if defined(AR_STATS)
-    // per-wavefront counters (lane 0): passes, items, begins, pick ends, waits, interior, final; 100 MHz clocks of the four phases
-    unsigned long long gs_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, gs_clk[5] = {0, 0, 0, 0, 0}, gs_hist[17] = {0}, gs_x[6] = {0, 0, 0, 0, 0, 0};
+    // per-wavefront counters (lane 0): passes, items, begins, pick ends, waits, interior, final, entries whose record came
+    // from the game's scratch (no free record in LDS), passes with such an entry; 100 MHz clocks of the four phases
+    unsigned long long gs_cnt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, gs_clk[5] = {0, 0, 0, 0, 0}, gs_hist[17] = {0}, gs_x[6] = {0, 0, 0, 0, 0, 0};
     const unsigned long long gs_t0 = wall_clock64();
 #define GW_STAT(...) __VA_ARGS__
 #else
@@ -558,6 +564,12 @@ __global__ void __launch_bounds__(64) k_gatherw(Slot<NW>* slots, uint32_t n_slot
             }
         }
         if (ln.active) gw_fetch<NW, R>(ln, item, sh.game, &sh.rec[0][0], &sh.stub[0][0], &sh.stub_node[0][0], m);
+        GW_STAT({
+            const bool sp = ln.active && !ln.from_pick && ((sh.stub[g][(item >> 8) & 0xfu] >> 12) & 7u) == GW_SPILL;
+            const unsigned long long b = __ballot(sp);
+            gs_cnt[7] += (unsigned long long)__popcll(b);
+            gs_cnt[8] += b ? 1ULL : 0ULL;
+        })
         // ---- phase 2
         GW_STAT(const unsigned long long gs_b = wall_clock64();)
         bool started = false, retire = false;
@@ -639,6 +651,8 @@ __global__ void __launch_bounds__(64) k_gatherw(Slot<NW>* slots, uint32_t n_slot
         atomicAdd(&g_gather_clk[0], 1ULL);
         for (int k = 0; k < 7; ++k) atomicAdd(&g_gather_clk[1 + k], gs_cnt[k]);
         for (int k = 0; k < 5; ++k) atomicAdd(&g_gather_clk[8 + k], gs_clk[k]);
+        atomicAdd(&g_gather_clk[13], gs_cnt[7]);
+        atomicAdd(&g_gather_clk[14], gs_cnt[8]);
         for (int k = 0; k < 17; ++k) atomicAdd(&g_gather_clk[16 + k], gs_hist[k]);
         for (int k = 0; k < 6; ++k) atomicAdd(&g_gather_clk[40 + k], gs_x[k]);
     }
@@ -1715,10 +1729,9 @@ struct Engine {
         if (gatherw) {
             int cus = 0;
             HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            // two wavefronts per SIMD (212 registers each), 32 (16 on boards above 64 cells) games each -- less one per CU: the
-            // grid is persistent, and the other group's small kernels (k_finish, k_backup: 130-220 registers) then find
-            // a SIMD with room instead of waiting for a gather wavefront to end (655 vs 643 M simulations/s)
-            gatherw_waves = (uint32_t)(cus > 0 ? cus : 256) * 7u;
+            // one wavefront per CU fewer than fit (twelve), 32 (16 on boards above 64 cells) games each: a full CU leaves no
+            // room for the small kernels beside the gather (profiles/r04_ab.txt: 705 M simulations/s at 11, 651 M at 12)
+            gatherw_waves = (uint32_t)(cus > 0 ? cus : 256) * GW_WAVES_PER_CU;
             if (const char* e = getenv("AR_GW_WAVES"))
                 if (atoi(e) > 0) gatherw_waves = (uint32_t)atoi(e);
             if (const char* e = getenv("AR_GW_PASSES")) gatherw_passes = atoi(e) > 0 ? (uint32_t)atoi(e) : 0xFFFFFFFFu;  // 0: no limit
@@ -1931,8 +1944,8 @@ struct Engine {
         // (AR_STAGGER=1, off by default) One gather at a time: a group's tree walk starts when the previous group's (in launch
         // order) has ended. Left to themselves the groups drift into step -- both walk, then both evaluate (kernel trace,
         // profiles/r03_timeline_131k.txt) -- so stages do not overlap across groups. Held apart they do not overlap either:
-        // the persistent gather fills every SIMD's registers (2 x 212 of 512) and the evaluator's wavefronts (141) wait for
-        // it to end: 588 vs 643 M simulations/s, also with half the gather wavefronts (570 M).
+        // the persistent gather fills every SIMD's registers (2 x 212 of 512 when this was measured) and the
+        // evaluator's wavefronts (141) wait for it to end: 588 vs 643 M simulations/s, also with half the gather wavefronts (570 M).
         if (stagger_gathers && groups.size() > 1)
             HIP_TRY(hipStreamWaitEvent(g.stream, groups[(gi + groups.size() - 1) % groups.size()].gathered, 0));
         const bool timed_launch = true;  // every group's gather launch is timed on its own stream
@@ -1951,7 +1964,7 @@ struct Engine {
             if (waves > gatherw_waves) waves = gatherw_waves;
             const uint32_t n_sets = (n + GWG - 1) / GWG, second_turn = n_sets > waves ? n_sets - waves : 0u;
             const uint32_t rot = second_turn ? (uint32_t)((g.step * (uint64_t)second_turn) % n_sets) : 0u;
-            hipLaunchKernelGGL((k_gatherw<NW, GWG, 4>), dim3(waves), dim3(64), (size_t)bases().maze_stage, g.stream, slots.p, g.end, cfg,
+            hipLaunchKernelGGL((k_gatherw<NW, GWG, GW_RECS>), dim3(waves), dim3(64), (size_t)bases().maze_stage, g.stream, slots.p, g.end, cfg,
                                bases(), g.first, phase, ready, gatherw_passes, rot);
         } else if (gather8 && gather8_wpe == 3)
             hipLaunchKernelGGL((k_gather8<NW, 3>), dim3((n + 7) / 8), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), q,

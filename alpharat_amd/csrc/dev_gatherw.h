@@ -163,7 +163,7 @@ struct GwLane {
     uint32_t fin_node, fin_kind, coll_mv, arr;
     uint32_t omap0, omap1, mask;
     uint32_t vtp[5];  // visits allocated to child slot (o1, o2): field o2 (6 bits) of word o1
-    uint32_t kid[25];  // the node's child table (it arrives with the record: the children need no trip of their own for their ids)
+    const uint32_t* kid;  // the node's child table in the arena, read in phase 3 (the lines arrived with the record in phase 2)
 #if defined(AR_STATS)
     uint32_t dbg_steps;               // allocation steps of this entry
     unsigned long long dbg_t[3];      // 100 MHz clock: record arrived, set-up done, allocation done
@@ -185,19 +185,6 @@ AR_HD float gw_sel5f(const float* a, uint32_t i) {
     for (uint32_t j = 0; j < 5; ++j) r |= (i == j) ? f32_to_bits(a[j]) : 0u;
     return bits_to_f32(r);
 }
-// kid[idx]: the row of five first (masks), then the column
-AR_HD uint32_t gw_pick25(const uint32_t* a, uint32_t idx) {
-    const uint32_t row = idx / 5, col = idx % 5;
-    uint32_t r[5] = {0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-    for (uint32_t q = 0; q < 5; ++q) {
-        const uint32_t mk = row == q ? 0xFFFFFFFFu : 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 5; ++j) r[j] |= a[5 * q + j] & mk;
-    }
-    return gw_sel5u(r, col);
-}
-
 // ---- per-player allocation state (the lane kernel's HalfAlloc with the added-visits counters packed) ------------
 struct GwHalf {
     float score[5], util[5], num[5];
@@ -454,10 +441,6 @@ AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of 
         ln.dbg_steps = 0;
         ln.dbg_t[0] = ln.dbg_t[1] = ln.dbg_t[2] = (a.visits + c.terminal + e1[4].visits + e2[4].visits) ? wall_clock64() : wall_clock64() + 0;
 #endif
-        // its child table rides along in the same round trip (used if the node turns out to be interior)
-        uint32_t kid_in[25];
-#pragma unroll
-        for (int j = 0; j < 25; ++j) kid_in[j] = N.c[j];
         if (a.visits == 0 || c.terminal != 0) {
             // leaf or terminal (search.rs:591-636 for the root, :675-706 for a child)
             ln.is_final = true;
@@ -539,8 +522,7 @@ AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of 
             ln.vtp[2] = v2;
             ln.vtp[3] = v3;
             ln.vtp[4] = v4;
-#pragma unroll
-            for (int j = 0; j < 25; ++j) ln.kid[j] = kid_in[j];
+            ln.kid = N.c;
         }
     }
     if (ln.is_final) {
@@ -624,7 +606,7 @@ AR_HD bool gw_publish(const GwLane<NW>& ln, GwGame<NW>& G, GwRec<NW>* rec /*[R] 
         const uint32_t kj = (gw_sel5u(ln.vtp, idx / 5) >> (6u * (idx % 5))) & 63u;
         left -= 1;
         stub[slot] = gw_stub(true, false, idx, kj, ref, ln.t);
-        stub_node[slot] = gw_pick25(ln.kid, idx);
+        stub_node[slot] = ln.kid[idx];  // (no lane writes this node's child table in the pass in which it publishes)
         ring[at & ring_mask] = gw_item(ln.g, slot, left);
         at += 1;
         slot += kj;

@@ -37,6 +37,8 @@ print(f"launches {st.gather_launches}  avg launch {st.gather_secs / max(st.gathe
 for i, n in enumerate(names):
     print(f"  {n:<20} {c[1 + i]:>14}  per wavefront {c[1 + i] / waves:10.1f}  per launch {c[1 + i] / max(st.gather_launches, 1):12.0f}")
 print(f"  items per pass {c[2] / max(c[1], 1):.1f}")
+print(f"  records from the game's scratch (no free LDS record): {c[13]} entries, {100.0 * c[13] / max(c[2], 1):.3f}% of items; "
+      f"passes with one {100.0 * c[14] / max(c[1], 1):.2f}%")
 ph = ["pop + fetch (1)", "visit (2)", "publish (3)", "pick end / begin (4)", "whole loop"]
 for i, n in enumerate(ph):
     print(f"  {n:<22} {c[8 + i] / waves / 100.0:10.1f} us per wavefront   {c[8 + i] / max(c[1], 1) / 100.0:8.2f} us per pass")
