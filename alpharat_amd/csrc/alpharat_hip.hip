@@ -1400,6 +1400,7 @@ int check_cfg(const SearchCfg& c) {
     if (c.n_sims == 0) return fail(AR_E_INVALID, "simulations must be > 0");
     if (c.batch_size == 0 || c.batch_size > 4096) return fail(AR_E_INVALID, "batch_size must be in 1..4096");
     if (c.coll_max > 65536) return fail(AR_E_INVALID, "collision_limit_max must be <= 65536");
+    if (c.coll_min > c.coll_max) return fail(AR_E_INVALID, "collision_limit_min must be <= collision_limit_max");
     if (c.noise_epsilon > 0.0f && !(c.noise_concentration / 5.0f > 1.0f))
         return fail(AR_E_INVALID, "noise_concentration must exceed 5 (Gamma shape >= 1 path only)");
     return AR_OK;
@@ -1722,10 +1723,16 @@ struct Engine {
         if (const char* e = getenv("AR_GATHER"))
             if (std::string(e).rfind("octet", 0) == 0)
                 gather8_wpe = std::string(e) == "octet4" ? 4 : std::string(e) == "octet3" ? 3 : std::string(e) == "octet2" ? 2 : gather8_wpe;
-        // the work-queue gather serves batches of up to GW_SLOTS descents; with uniform priors nearly every allocation step
-        // draws a tie break, which puts its items in sequence again: those runs keep the eight-lane kernel
-        gatherw = need_queue && net != nullptr && cfg.batch_size <= GW_SLOTS;
-        if (const char* e = getenv("AR_GATHER")) gatherw = std::string(e) == "wide" && need_queue && cfg.batch_size <= GW_SLOTS;
+        // the work-queue gather serves batches of up to GW_SLOTS descents and GW_MAX_PICKS picks (batch_size + collision
+        // budget); with uniform priors nearly every allocation step draws a tie break, which puts its items in sequence
+        // again: those runs keep the eight-lane kernel. AR_GATHER=wide beyond its bounds takes k_gather8.
+        const bool gw_fits = need_queue && cfg.batch_size <= GW_SLOTS &&
+                             cfg.batch_size + std::max(cfg.coll_min, cfg.coll_max) <= (uint32_t)GW_MAX_PICKS;
+        gatherw = gw_fits && net != nullptr;
+        if (const char* e = getenv("AR_GATHER")) {
+            gatherw = std::string(e) == "wide" && gw_fits;
+            if (std::string(e) == "wide" && !gatherw) gather8 = true;
+        }
         if (gatherw) {
             int cus = 0;
             HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));

@@ -35,6 +35,10 @@
 namespace ar {
 
 enum { GW_SLOTS = 16 };  // visit slots per pick (= largest batch size served)
+// picks one batch may make: a batch entry's backup order key is (pick number << 4 | visit slot) in 16 bits. A pick adds an
+// entry or spends at least one collision, so a batch makes at most batch_size + collision budget picks; the engine takes
+// this gather only when that is at most GW_MAX_PICKS, and a gather that would go past it stops with an error.
+enum { GW_MAX_PICKS = 4095 };
 enum { GW_SPILL = 7 };   // record reference of a stub: 0..R-1 = one of the game's records in LDS, GW_SPILL = the game's scratch in global memory
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -115,9 +119,10 @@ struct alignas(8) GwGame {
     uint32_t b_coll;
     uint32_t next_game;   // (kernel) how many games this context has taken
     int32_t left;  // collision budget left (search.rs:970)
-    uint8_t batch, budget, pick, error;  // pick: number of the running pick_nodes_to_extend call
+    uint16_t pick;  // number of the running pick_nodes_to_extend call (1..GW_MAX_PICKS: 12 bits of the backup order key)
+    uint8_t batch, budget, error;
     uint8_t running;  // 1: gather in progress
-    uint8_t stalled, began;
+    uint8_t stalled : 1, began : 1;  // (one byte: both are written only by gw_begin, by the lane that begins the game)
     uint8_t parked;   // 1: the launch's pass limit was reached between two picks: the gather goes on in the next launch
 #if defined(AR_STATS)
     uint32_t dbg_start;  // pass of the wavefront in which the game began
@@ -317,6 +322,11 @@ struct GwMem {
 template <int NW>
 AR_HD bool gw_next_pick(GwGame<NW>& G, uint32_t* stub, uint16_t* ring, uint32_t ring_mask, uint32_t* tail, uint32_t g) {
     if (!(G.n_proc < G.batch && G.left > 0)) {
+        G.running = 0;
+        return false;
+    }
+    if (G.pick >= GW_MAX_PICKS) {  // (excluded by the engine's choice of gather: the order key would wrap)
+        G.error = 9;
         G.running = 0;
         return false;
     }
@@ -670,7 +680,7 @@ AR_HD void gw_begin(GwGame<NW>& G, const Slot<NW>& S, uint32_t slot, const Searc
         G.b_term = S.b_term;
         G.b_coll = S.b_coll;
         G.left = S.g_left;
-        G.pick = (uint8_t)S.g_pick;
+        G.pick = (uint16_t)S.g_pick;
         return;
     }
     G.left = (int32_t)collisions_left(G.node_count, cfg);

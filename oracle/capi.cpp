@@ -540,4 +540,10 @@ int or_selfplay_bench(uint8_t w, uint8_t h, uint16_t cheese, uint16_t max_turns,
     return failed ? -1 : 0;
 }
 
+// search.rs:437-450 calculate_collisions_left for each of `n` tree node counts
+void or_collisions_left(const OrSearchConfig* cfg, const uint32_t* node_counts, uint32_t n, uint32_t* out) {
+    const SearchConfig c = to_cfg(cfg);
+    for (uint32_t i = 0; i < n; ++i) out[i] = calculate_collisions_left(node_counts[i], c);
+}
+
 }  // extern "C"

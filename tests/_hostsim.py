@@ -47,6 +47,8 @@ def lib():
         L.hs_final.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.hs_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hs_last.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hs_collisions_left.restype = None
+        L.hs_collisions_left.argtypes = [C.POINTER(HsCfg), C.c_void_p, C.c_uint32, C.c_void_p]
         L.hs_tree_dump.restype = C.c_uint32
         L.hs_tree_dump.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         _lib = L
@@ -107,6 +109,14 @@ def run(og, max_turns, ocfg, n_sims, batch, seed, single=False, eval_mode=0, v1=
         )
     finally:
         L.hs_free(h)
+
+
+def collisions_left(ocfg, node_counts) -> np.ndarray:
+    """The product's collision budget (dev_search.h collisions_left) at each tree node count, for the oracle config."""
+    n = np.ascontiguousarray(node_counts, dtype=np.uint32)
+    out = np.zeros(len(n), dtype=np.uint32)
+    lib().hs_collisions_left(C.byref(cfg_from_oracle(ocfg)), _p(n), len(n), _p(out))
+    return out
 
 
 def hashed_eval(width):

@@ -125,6 +125,7 @@ def lib() -> C.CDLL:
         "or_record_header": (None, [vp, vp, vp, vp]),
         "or_record_game_arrays": (None, [vp, vp, vp, vp]),
         "or_record_positions": (None, [vp, vp, vp, vp]),
+        "or_collisions_left": (None, [C.POINTER(OrSearchConfig), vp, u32, vp]),
         "or_selfplay_bench": (
             i32,
             [u8, u8, u16, u16, u32, C.POINTER(OrSearchConfig), u32, u32, u32, u64, u64, i32, vp, vp, C.POINTER(C.c_double),
@@ -325,6 +326,14 @@ def search_once(game: Game, cfg=None, n_sims=100, batch=8, seed=42, **kw):
     r = t.search(game, cfg, n_sims, batch, Rng(seed), **kw)
     r["tree"] = t
     return r
+
+
+def collisions_left(cfg: OrSearchConfig, node_counts) -> np.ndarray:
+    """calculate_collisions_left (search.rs:437-450) at each tree node count."""
+    n = np.ascontiguousarray(node_counts, dtype=np.uint32)
+    out = np.zeros(len(n), dtype=np.uint32)
+    lib().or_collisions_left(C.byref(cfg), _ptr(n), len(n), _ptr(out))
+    return out
 
 
 def play_game(game: Game, cfg: OrSearchConfig, n_sims, batch, rng_seed, backend=0, net: Net | None = None, game_index=0) -> dict:

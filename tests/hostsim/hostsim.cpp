@@ -398,4 +398,10 @@ uint32_t hs_tree_dump(const void* p, uint32_t* out, uint32_t max_nodes) {
     return count;
 }
 
+// the product's collision budget (dev_search.h collisions_left) for each of `n` tree node counts
+void hs_collisions_left(const HsCfg* c, const uint32_t* node_counts, uint32_t n, uint32_t* out) {
+    const SearchCfg cfg = to_cfg(c, 1, 1);
+    for (uint32_t i = 0; i < n; ++i) out[i] = collisions_left(node_counts[i], cfg);
+}
+
 }  // extern "C"

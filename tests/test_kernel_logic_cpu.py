@@ -22,6 +22,24 @@ def games():
     yield "7x7", O.Game(7, 7, 50).random_cheese(10, True, 5), 50
 
 
+def _same_search(want, got, name):
+    """One search (single=True) against the oracle's: tree dump, result, last-search counts, counters."""
+    assert got["error"] == 0, name
+    wd = want["tree"].dump()
+    assert got["dump_count"] == len(wd), name
+    np.testing.assert_array_equal(got["dump"], wd, err_msg=name)
+    f = got["last"]
+    for k, sl in (("value_p1", 2), ("value_p2", 3)):
+        assert np.float32(want[k]).tobytes() == f[sl].tobytes(), (name, k)
+    for k, a in (("visit_counts_p1", 4), ("visit_counts_p2", 9), ("prior_p1", 14), ("prior_p2", 19),
+                 ("policy_p1", 24), ("policy_p2", 29)):
+        assert want[k].tobytes() == f[a:a + 5].tobytes(), (name, k)
+    assert list(got["last_counts"]) == [want[k] for k in ("total_visits", "nn_evals", "terminals", "collisions")], name
+    assert got["gather_node_visits"] == int(want["counters"][0]), name
+    assert got["backup_node_visits"] == int(want["counters"][1]), name
+    assert got["new_nodes"] == int(want["counters"][2]), name
+
+
 @pytest.mark.parametrize("sims,batch", [(1, 1), (40, 1), (200, 8), (600, 16)])
 def test_single_search_tree_bit_exact(sims, batch):
     for name, g, mt in games():
@@ -29,20 +47,7 @@ def test_single_search_tree_bit_exact(sims, batch):
             cfg = O.make_config(**cfgkw)
             want = O.search_once(g, cfg, sims, batch, seed=42)
             got = H.run(g, mt, cfg, sims, batch, 42, single=True)
-            assert got["error"] == 0, name
-            wd = want["tree"].dump()
-            assert got["dump_count"] == len(wd), name
-            np.testing.assert_array_equal(got["dump"], wd, err_msg=name)
-            f = got["last"]
-            for k, sl in (("value_p1", 2), ("value_p2", 3)):
-                assert np.float32(want[k]).tobytes() == f[sl].tobytes(), (name, k)
-            for k, a in (("visit_counts_p1", 4), ("visit_counts_p2", 9), ("prior_p1", 14), ("prior_p2", 19),
-                         ("policy_p1", 24), ("policy_p2", 29)):
-                assert want[k].tobytes() == f[a:a + 5].tobytes(), (name, k)
-            assert list(got["last_counts"]) == [want[k] for k in ("total_visits", "nn_evals", "terminals", "collisions")]
-            assert got["gather_node_visits"] == int(want["counters"][0])
-            assert got["backup_node_visits"] == int(want["counters"][1])
-            assert got["new_nodes"] == int(want["counters"][2])
+            _same_search(want, got, name)
 
 
 def _same_game(want, got):
@@ -116,3 +121,114 @@ def test_constant_value_backend_search():
     want = O.search_once(g, cfg, 120, 4, seed=123, backend=1, v1=1.5, v2=0.5)
     got = H.run(g, 100, cfg, 120, 4, 123, single=True, eval_mode=1, v1=1.5, v2=0.5)
     np.testing.assert_array_equal(got["dump"], want["tree"].dump())
+
+
+# ---- collision budgets (search.rs:437-450 calculate_collisions_left, :961-999 simulate_batch) -------------------------
+# A batch runs pick_nodes_to_extend until it has batch_size entries or its collision budget is spent, so the budget sets
+# how many picks a batch makes (at most batch_size + budget) and how many multi-visit collisions it records. The
+# work-queue gather keys each entry with its pick number in 12 bits; the engine takes it only while
+# batch_size + budget <= GW_MAX_PICKS (dev_gatherw.h), and beyond that a gather that would wrap the key must stop with an
+# error. The harness forces the work-queue modes at every budget, so there a case is either bit-exact or an error.
+GW_MAX_PICKS = 4095
+UNIFORM_MODES = (0, 2, 3)   # SmartUniform inline, the fused kernel body, the gather cut off and resumed
+HASHED_MODES = (6, 7, 8, 9)  # hashed_eval: work-queue gather (whole / random cuts / one record, pass limit), lane gather
+WIDE_MODES = (6, 7, 9)
+
+
+def _coll(lo, hi=None, start=800, end=50000, power=1.0, **kw):
+    return O.make_config(collision_limit_min=lo, collision_limit_max=lo if hi is None else hi,
+                         collision_scaling_start=start, collision_scaling_end=end, collision_scaling_power=power,
+                         **TUNED, **kw)
+
+
+def _check_searches(cfg, sims, batch, positions=None, seed=42):
+    """Every eval mode against the oracle for one search from each of the games() positions (or the named ones)."""
+    limit = max(cfg.collision_limit_min, cfg.collision_limit_max)
+    for name, g, mt in games():
+        if positions is not None and name not in positions:
+            continue
+        want = O.search_once(g, cfg, sims, batch, seed=seed)
+        for mode in UNIFORM_MODES:
+            _same_search(want, H.run(g, mt, cfg, sims, batch, seed, single=True, eval_mode=mode), (name, mode))
+        want = O.search_once(g, cfg, sims, batch, seed=seed, backend=4, net=O.CallbackBackend(H.hashed_eval(g.w)))
+        for mode in HASHED_MODES:
+            got = H.run(g, mt, cfg, sims, batch, seed, single=True, eval_mode=mode)
+            if mode in WIDE_MODES and batch + limit > GW_MAX_PICKS and got["error"] != 0:
+                continue  # (the engine never takes the work-queue gather here; it must not return a wrong tree)
+            _same_search(want, got, (name, mode))
+
+
+@pytest.mark.parametrize("limit", [2, 16, 255, 256, 257, 1000, 4079, 4080, 65536])
+@pytest.mark.parametrize("batch", [16, 3])
+def test_fixed_collision_budget_single_search(limit, batch):
+    # 255/256/257: the old 8-bit pick number; 4079/4080 with batch 16: the last budget the work-queue gather serves
+    _check_searches(_coll(limit), 2000, batch)
+
+
+@pytest.mark.parametrize("power", [0.5, 1.0, 2.0, 3.7])
+def test_collision_budget_scaling_crossed_in_the_search(power):
+    # the tree passes `start` early and `end` before the search ends: every batch in between gets a new budget
+    _check_searches(_coll(1, 512, start=20, end=1500, power=power), 2000, 16, positions=("open5_corner", "7x7"))
+
+
+@pytest.mark.parametrize("lo,hi,start,end", [
+    (1, 300, 200, 200),   # start == end: min up to and below it, max from it on
+    (0, 256, 20, 1500),   # min 0: the first batches are empty and still consume one simulation each
+    (0, 0, 800, 50000),   # no budget at all: every batch is empty, the root is never evaluated
+])
+def test_collision_budget_edges(lo, hi, start, end):
+    _check_searches(_coll(lo, hi, start=start, end=end, power=2.0), 2000, 16, positions=("open5_corner", "mud_wall"))
+    _check_searches(_coll(lo, hi, start=start, end=end, power=2.0), 301, 3, positions=("same_cell", "short"))
+
+
+@pytest.mark.parametrize("limit", [300, 1000])
+def test_collision_budget_whole_games(limit):
+    """Tree reuse between moves: the node count carried into each search feeds the budget."""
+    g = O.Game(7, 7, 50).random_cheese(10, True, 4)
+    cfg = _coll(limit, power=0.5, noise_epsilon=0.25)
+    want = O.play_game(g, cfg, 600, 16, 31, backend=4, net=O.CallbackBackend(H.hashed_eval(7)))
+    assert want["total_collisions"] > 0
+    for mode in HASHED_MODES:
+        _same_game(want, H.run(g, 50, cfg, 600, 16, 31, eval_mode=mode))
+    want = O.play_game(g, cfg, 600, 16, 31)
+    for mode in UNIFORM_MODES:
+        _same_game(want, H.run(g, 50, cfg, 600, 16, 31, eval_mode=mode))
+
+
+def test_collisions_left_known_answers():
+    """calculate_collisions_left from its definition: min at or below start, max at or beyond end, otherwise
+    min + (max - min) * ratio^power rounded half away from zero, clamped to [min, max]."""
+    cases = [
+        # (min, max, start, end, power, [(node_count, budget), ...])
+        (1, 256, 800, 50000, 1.0, [(0, 1), (799, 1), (800, 1), (801, 1), (25400, 129), (49999, 256), (50000, 256),
+                                   (60000, 256)]),  # 25400: ratio 1/2, 128.5 -> 129
+        (1, 256, 800, 50000, 2.0, [(25400, 65)]),      # 1 + 255 / 4 = 64.75
+        (1, 256, 800, 50000, 0.5, [(25400, 181)]),     # 1 + 255 * 0.7071 = 181.3
+        (1, 256, 800, 50000, 3.7, [(25400, 21)]),      # 1 + 255 * 0.0769 = 20.6
+        (1, 512, 20, 1500, 1.0, [(390, 129)]),         # ratio 1/4: 128.75
+        (1, 512, 20, 1500, 2.0, [(390, 33)]),          # 32.9375
+        (1, 512, 20, 1500, 0.5, [(390, 257), (20, 1), (21, 14), (1500, 512)]),  # 256.5 -> 257 (half away from zero)
+        (1, 300, 200, 200, 1.0, [(199, 1), (200, 300), (201, 300)]),  # start == end: the `end` test comes first
+        (0, 256, 20, 1500, 1.0, [(1, 0), (20, 0), (21, 0), (760, 128)]),  # 0 + 256 * 1/2
+        (0, 0, 800, 50000, 1.0, [(0, 0), (25400, 0), (60000, 0)]),
+        (1000, 1000, 800, 50000, 1.0, [(0, 1000), (25400, 1000), (60000, 1000)]),
+        (65536, 65536, 800, 50000, 2.0, [(1, 65536), (30000, 65536)]),
+    ]
+    for lo, hi, start, end, power, pts in cases:
+        cfg = _coll(lo, hi, start=start, end=end, power=power)
+        n = [p[0] for p in pts]
+        expect = [p[1] for p in pts]
+        assert list(O.collisions_left(cfg, n)) == expect, (lo, hi, start, end, power)
+        assert list(H.collisions_left(cfg, n)) == expect, (lo, hi, start, end, power)
+
+
+@pytest.mark.parametrize("power", [0.5, 1.0, 2.0, 3.7])
+def test_collisions_left_matches_the_oracle_everywhere(power):
+    n = np.arange(0, 60001, dtype=np.uint32)
+    for lo, hi, start, end in ((1, 256, 800, 50000), (1, 512, 20, 1500), (0, 65536, 0, 60000), (7, 4080, 1000, 1001)):
+        cfg = _coll(lo, hi, start=start, end=end, power=power)
+        want = O.collisions_left(cfg, n)
+        got = H.collisions_left(cfg, n)
+        bad = np.flatnonzero(want != got)
+        assert bad.size == 0, (lo, hi, start, end, [(int(i), int(want[i]), int(got[i])) for i in bad[:5]])
+        assert want[start] == lo and want[min(end, 60000)] == hi
