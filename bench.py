@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the self-play MCTS sampling path on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (config.workload): BASELINE config 3 -- 7x7 open PyRat, 10 symmetric cheese, 50 turns,
@@ -21,6 +21,10 @@ value = MCTS simulations per second over all ranks (the reference's own count: t
 totals of the moves finished inside the timed region, selfplay.rs:547 -- visits kept by tree reuse count);
 productive descents/s (evaluations + terminals, what the search actually walks) and NN evaluations/s ride
 along, as do games/s. The timed region starts with everything resident on the device.
+
+A plain run does only what that line needs: it sets up, warms up, times the steps, writes --dump-outputs if asked
+and prints the line. --full adds the legs that take runs of their own (N=1): roofline.full_launch (the gather over
+all resident games as one group, in a fresh session) and cpu_baseline (the oracle's self-play on the host cores).
 
 Extra, non-headline evaluators: --evaluator symmetric (BASELINE config 4: SymmetricMLP h256, 7x7_rust_strong,
 2693 sims), --evaluator cnn (config 5: CNN + global pooling c64, 4096 sims), --evaluator uniform (tree kernels only).
@@ -223,13 +227,18 @@ def main() -> int:
                     help="games resident on each GPU (default: 131072; 16384 for cnn); the library may choose fewer "
                          "(device memory), the line reports what it used")
     ap.add_argument("--evaluator", choices=sorted(WORKLOADS), default="mlp")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's own work, also run the extra legs that take runs of their own: the "
+                         "gather kernel launched over all resident games at once (roofline.full_launch) and the CPU "
+                         "baseline (cpu_baseline); a plain run leaves both out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-secs", type=float, default=8.0, help="bound of the CPU baseline sample")
     ap.add_argument("--no-full-launch", action="store_true",
-                    help="skip the extra leg that times the gather kernel launched over all resident games at once")
+                    help="with --full: skip the extra leg that times the gather kernel launched over all resident games "
+                         "at once")
     ap.add_argument("--deadline", type=float, default=480.0,
-                    help="seconds after process start after which the extra legs (full launch, CPU baseline) are skipped; "
-                         "the timed loop always runs --steps steps")
+                    help="seconds after process start after which the extra legs of --full (full launch, CPU baseline) are "
+                         "skipped; the timed loop always runs --steps steps")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help=f"write the game records of a fixed, seeded sample of {DUMP_GAMES} games of the timed session to "
                          "DIR/<field>.npy (float32 arrays, float64 per-game scalars), to compare builds output for output")
@@ -240,8 +249,11 @@ def main() -> int:
                     help="also build every finished game's record on the host and write the bundles (the reference's "
                          "recording path) inside the timed region: a sink callback + output_dir on a tmpfs")
     ap.add_argument("--cpu-sweep", action="store_true",
-                    help="CPU baseline at 1, 8, 32, 64 and all threads (bench_selfplay.rs:213-224) instead of one count")
+                    help="with --full: CPU baseline at 1, 8, 32, 64 and all threads (bench_selfplay.rs:213-224) instead of "
+                         "one count")
     args = ap.parse_args()
+    if args.cpu_sweep and not args.full:
+        ap.error("--cpu-sweep is part of the CPU baseline, which only --full runs")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -337,6 +349,7 @@ def main() -> int:
 
     sync()
     t0 = time.perf_counter()
+    t_warm = t0 - T_START - t_open
     acc = None
     done = 0
     for k in range(args.steps):
@@ -355,7 +368,9 @@ def main() -> int:
         while len(kept) < len(sample) and after < DUMP_MAX_BATCH_STEPS_AFTER:
             session.step(1024)
             after += 1024
+    tc = time.perf_counter()
     session.close()
+    t_close = time.perf_counter() - tc
     if sample:
         if len(kept) < len(sample):
             raise RuntimeError(f"--dump-outputs: {len(sample) - len(kept)} of the {len(sample)} sampled games did not finish "
@@ -459,17 +474,17 @@ def main() -> int:
         # how much of a game's life the window covers (steady state needs the warm-up to be longer than a game)
         "window": {"warmup_batch_steps": warm_done, "timed_batch_steps": int(tot["done"]) * args.batch_steps,
                    "games_finished": int(tot["games"]), "positions_finished": int(tot["positions"])},
-        "timing": {"session_open_s": t_open, "timed_s": elapsed},
+        "timing": {"session_open_s": t_open, "warmup_s": t_warm, "timed_s": elapsed, "close_s": t_close},
     }
     if args.dump_outputs:
         out["dump_outputs"] = {"dir": args.dump_outputs, "games": len(kept), "batch_steps_after_timed": after}
     if args.record:
         out["record"] = {"what": "every finished game's record built on the host (sink callback) and written as bundles to a "
                                  "tmpfs inside the timed region", "games_in_callback": rec_games[0], "bundle_files": rec_files}
-    # Extra leg (N=1, network evaluators): the same workload with the games as ONE group, i.e. the gather kernel launched
-    # over all resident games at once instead of two half-size launches pipelined against the evaluator. It is the
-    # kernel's best per-launch figure; the timed configuration above trades it for throughput.
-    if has_net and world == 1 and not args.no_full_launch and "AR_GROUPS" not in os.environ and \
+    # Extra leg (--full, N=1, network evaluators): the same workload with the games as ONE group, i.e. the gather kernel
+    # launched over all resident games at once instead of two half-size launches pipelined against the evaluator. It is
+    # the kernel's best per-launch figure; the timed configuration above trades it for throughput.
+    if args.full and has_net and world == 1 and not args.no_full_launch and "AR_GROUPS" not in os.environ and \
             (time.perf_counter() - T_START) < args.deadline - 120.0:
         prof = under_profiler()
         if prof:
@@ -482,7 +497,8 @@ def main() -> int:
                 out["roofline"]["full_launch"] = full_launch_leg(args.evaluator, args.resident, args.batch_steps, local_rank, weights)
             except Exception as e:  # noqa: BLE001 -- the extra leg never costs the headline line
                 out["roofline"]["full_launch"] = {"error": str(e)}
-    if not args.no_cpu_baseline and args.cpu_secs > 0 and world == 1:  # a reported baseline, timed on rank 0 at N=1 only
+    # a reported baseline, timed on rank 0 at N=1 only
+    if args.full and not args.no_cpu_baseline and args.cpu_secs > 0 and world == 1:
         left = args.deadline + 60.0 - (time.perf_counter() - T_START)
         if left > args.cpu_secs + 15.0:
             out["cpu_baseline"] = cpu_baseline(weights, args.evaluator, args.cpu_secs)
