@@ -301,16 +301,14 @@ __global__ void __launch_bounds__(64) k_step_uniform(Slot<NW>* slots, uint32_t n
 template <int NW>
 __global__ void __launch_bounds__(64) k_gather(Slot<NW>* slots, uint32_t n_slots, SearchCfg cfg, Bases B,
                                                LeafReq<NW>* queue, uint32_t* queue_count, uint32_t max_rounds,
-                                               uint32_t lanes, uint32_t first, uint32_t phase,
-                                               uint32_t accept_ready) {
-    // slots [first, n_slots) -- one group of games; `lanes` games per wavefront (<= 64)
+                                               uint32_t first, uint32_t phase, uint32_t accept_ready) {
+    // slots [first, n_slots) -- one group of games; one game per lane
     __shared__ uint32_t lds_maze[MAZE_STAGE_BYTES / 4];
     if (B.maze_stage) {
         for (uint32_t w = threadIdx.x; w < B.maze_stage / 4; w += blockDim.x) lds_maze[w] = ((const uint32_t*)B.maze)[w];
         __syncthreads();
     }
-    if (threadIdx.x >= lanes) return;
-    const uint32_t i = first + blockIdx.x * lanes + threadIdx.x;
+    const uint32_t i = first + blockIdx.x * 64u + threadIdx.x;
     if (i >= n_slots) return;
     {
         const uint32_t st = slots[i].status;
@@ -691,10 +689,9 @@ __global__ void __launch_bounds__(64) k_pack_leaves(Slot<NW>* slots, uint32_t n_
 
 template <int NW>
 __global__ void __launch_bounds__(64) k_backup(Slot<NW>* slots, uint32_t n_slots, SearchCfg cfg, Bases B,
-                                               const ZigTables* zt, const EvalOut* ev_queue, uint32_t lanes,
-                                               uint32_t first, uint32_t phase) {
-    if (threadIdx.x >= lanes) return;
-    const uint32_t i = first + blockIdx.x * lanes + threadIdx.x;
+                                               const ZigTables* zt, const EvalOut* ev_queue, uint32_t first,
+                                               uint32_t phase) {
+    const uint32_t i = first + blockIdx.x * 64u + threadIdx.x;
     if (i >= n_slots) return;
     if (slots[i].status != SLOT_ACTIVE || !slots[i].batch_active) return;
     Slot<NW> s = slots[i];
@@ -1545,13 +1542,15 @@ struct ArenaHold {
     ~ArenaHold() { arena_release(dev, blk); }
 };
 
-// Which gather kernel the network path uses when AR_GATHER does not say: measured on the bench workload (DESIGN.md
-// section 7, profiles/r02_gather_ab.md) the eight-lanes-per-game kernel is faster per launch at every size -- 1.9x /
-// 1.7x at 1024 / 8192 resident games, where its eight-fold wavefront count fills SIMDs the lane-per-game kernel leaves
-// to one wavefront or none, and still ahead at 65536 once the shared maze sits in LDS and three wavefronts share a SIMD.
-static bool default_gather8(uint32_t) { return true; }
-// its register budget: two wavefronts per SIMD without spills up to 32768 games, three (168 VGPRs) above
-static int default_gather8_wpe(uint32_t resident_games) { return resident_games <= 32768u ? 2 : 3; }
+// The kernel that walks the trees of the split pipeline (results are identical; Engine::choose_gather):
+// - Wide: the work queue over tree levels (k_gatherw, dev_gatherw.h), the default of network runs whose batches it serves.
+// - Octet2 / Octet3: eight lanes per game (k_gather8). Measured on the bench workload (DESIGN.md section 7,
+//   profiles/r02_gather_ab.md) it is faster per launch than one lane per game at every size -- 1.9x / 1.7x at 1024 /
+//   8192 resident games, where its eight-fold wavefront count fills SIMDs the lane-per-game kernel leaves to one
+//   wavefront or none, and still ahead at 65536 once the shared maze sits in LDS and three wavefronts share a SIMD.
+//   Its register budget: two wavefronts per SIMD without spills up to 32768 games (Octet2), three (168 VGPRs) above.
+// - Lane: one lane per game (k_gather).
+enum class GatherKernel { Lane, Octet2, Octet3, Wide };
 // measured (BASELINE config 2: 5x5, 1000 sims, 4096 games: 71.1 M vs 41.5 M simulations/s through the split pipeline;
 // 7x7 / 1897 sims at 65536 games: 1180 M vs 1251 M): few games want k_gather8's wavefront count, many the fused kernel
 static bool default_uniform_queue(uint32_t resident_games) { return resident_games <= 16384u; }
@@ -1622,15 +1621,11 @@ struct Engine {
     DevBuf<EvalOut> ev_miss;
     DevBuf<unsigned long long> cache_counters;
     ArenaPool pool = {};            // overflow blocks handed out by the kernels themselves
-    uint32_t lanes = 64;  // games per wavefront in k_gather / k_backup
-    uint32_t backup_lanes = 64;  // games per wavefront in the network path's k_backup (AR_BACKUP_LANES)
     bool backup16 = false;       // network path: the sixteen-lanes-per-game backup (k_backup16 + k_finish) instead of k_backup
     bool uniform_queue = false;  // SmartUniform through the split pipeline (leaf queue + k_uniform_eval) instead of k_step_uniform
     bool use_queue() const { return net != nullptr || uniform_queue; }
-    bool gather8 = false; // network path: the eight-lanes-per-game gather (k_gather8) instead of k_gather
-    int gather8_wpe = 2;  // its register budget: 2 wavefronts per SIMD (no spills) or 4 (128 VGPRs, spills to scratch)
-    // network path: the gather as a work queue over tree levels (k_gatherw, dev_gatherw.h); a persistent grid of `gatherw_waves`
-    bool gatherw = false;
+    GatherKernel gather = GatherKernel::Lane;  // the split pipeline's gather (setup() chooses it)
+    // k_gatherw runs as a persistent grid of `gatherw_waves`
     uint32_t gatherw_waves = 2048;
     // passes one launch may run; gathers that are not complete then are parked between two picks and go on in the next
     // launch. A game needs 50 passes in the median, 110 at the 90th and 160 at the 99th percentile, a few need 300+
@@ -1639,7 +1634,7 @@ struct Engine {
     // evaluator and the late tree reuse of the round's end, over windows of five generations of games: 32 / 48 / 64 / 96 ->
     // 726 / 732 / 730 / 721 M (profiles/r03_sweeps.md; shorter windows sample one phase of the games and mislead).
     uint32_t gatherw_passes = 64;
-    uint32_t gather_rounds = 0xFFFFFFFFu;  // rounds one k_gather launch may run per lane (self-play sets a limit)
+    uint32_t gather_rounds = 0xFFFFFFFFu;  // rounds one k_gather launch may run per lane (set before setup())
     size_t region_bytes = 0;
     uint32_t region_low_mb = 0xFFFFFFFFu;  // least the region had left: MB never carved + MB in free blocks
     DevBuf<unsigned long long> pool_bits;
@@ -1698,6 +1693,27 @@ struct Engine {
         return b;
     }
 
+    // The gather of the split pipeline, from S, L, cfg, net and gather_rounds; AR_GATHER = wide | octet | octet2 | octet3 |
+    // lane asks for one (results are identical).
+    GatherKernel choose_gather(bool need_queue) const {
+        // the work-queue gather serves batches of up to GW_SLOTS descents and GW_MAX_PICKS picks (batch_size + collision
+        // budget: its entries carry a 12-bit pick number); with uniform priors nearly every allocation step draws a tie
+        // break, which puts its items in sequence again: those runs keep the eight-lane kernel
+        const bool fits = need_queue && cfg.batch_size <= GW_SLOTS &&
+                          cfg.batch_size + std::max(cfg.coll_min, cfg.coll_max) <= (uint32_t)GW_MAX_PICKS;
+        const bool big = (size_t)S * L.total >= ((size_t)1 << 32);  // k_gather8 addresses scratch with 32-bit offsets
+        const GatherKernel octet = big ? GatherKernel::Lane : S <= 32768u ? GatherKernel::Octet2 : GatherKernel::Octet3;
+        const char* e = getenv("AR_GATHER");
+        const std::string want = e ? e : "";
+        if (gather_rounds != 0xFFFFFFFFu) return GatherKernel::Lane;  // the round limit parks the walk: lane kernel only
+        if (!e) return net != nullptr && fits ? GatherKernel::Wide : octet;
+        if (want == "wide") return fits ? GatherKernel::Wide : octet;
+        if (want == "octet2") return big ? GatherKernel::Lane : GatherKernel::Octet2;
+        if (want == "octet3") return big ? GatherKernel::Lane : GatherKernel::Octet3;
+        if (want.rfind("octet", 0) == 0) return octet;
+        return GatherKernel::Lane;
+    }
+
     // `tree_bytes`: device memory for the trees (0 = one smallest block per game: every growth goes through the host)
     int setup(int device, uint32_t n_slots, const SearchCfg& c, uint32_t mt, const std::vector<uint8_t>& maze_bytes,
               uint32_t arena_nodes, bool need_queue, size_t tree_bytes = 0) {
@@ -1712,28 +1728,12 @@ struct Engine {
         HIP_TRY(hipEventCreateWithFlags(&ev_order, hipEventDisableTiming));
         L = make_layout<NW>(cfg, max_turns);
         static_assert(sizeof(LevelO<NW>) <= (16 + 112 + sizeof(State<NW>) + 15) / 16 * 16, "slot_layout.h sizes the level stack");
-        // which gather kernel walks the trees of the network path (results are identical): AR_GATHER=lane | octet
-        gather8 = default_gather8(S);
-        gather8_wpe = default_gather8_wpe(S);
         // which backup kernel (results are identical): AR_BACKUP=lane | group; the group kernel keeps 64 paths in LDS
         // (the deep part of its paths lives in the level-stack scratch: 16 lanes x path_cap steps must fit there)
         backup16 = (size_t)16 * (L.max_depth + 2) * sizeof(PathStep) <= (size_t)L.max_depth * (16 + 112 + sizeof(State<NW>));
         if (const char* e = getenv("AR_BACKUP")) backup16 = backup16 && std::string(e) != "lane";
-        if (const char* e = getenv("AR_GATHER")) gather8 = std::string(e).rfind("octet", 0) == 0;
-        if (const char* e = getenv("AR_GATHER"))
-            if (std::string(e).rfind("octet", 0) == 0)
-                gather8_wpe = std::string(e) == "octet4" ? 4 : std::string(e) == "octet3" ? 3 : std::string(e) == "octet2" ? 2 : gather8_wpe;
-        // the work-queue gather serves batches of up to GW_SLOTS descents and GW_MAX_PICKS picks (batch_size + collision
-        // budget); with uniform priors nearly every allocation step draws a tie break, which puts its items in sequence
-        // again: those runs keep the eight-lane kernel. AR_GATHER=wide beyond its bounds takes k_gather8.
-        const bool gw_fits = need_queue && cfg.batch_size <= GW_SLOTS &&
-                             cfg.batch_size + std::max(cfg.coll_min, cfg.coll_max) <= (uint32_t)GW_MAX_PICKS;
-        gatherw = gw_fits && net != nullptr;
-        if (const char* e = getenv("AR_GATHER")) {
-            gatherw = std::string(e) == "wide" && gw_fits;
-            if (std::string(e) == "wide" && !gatherw) gather8 = true;
-        }
-        if (gatherw) {
+        gather = choose_gather(need_queue);
+        if (gather == GatherKernel::Wide) {
             int cus = 0;
             HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
             // one wavefront per CU fewer than fit (twelve), 32 (16 on boards above 64 cells) games each: a full CU leaves no
@@ -1754,7 +1754,6 @@ struct Engine {
         g_dbg_nw = NW;
 #endif
         HIP_TRY(scratch.alloc((size_t)S * L.total));
-        if ((size_t)S * L.total >= ((size_t)1 << 32)) gather8 = false;  // k_gather8 addresses scratch with 32-bit offsets
         // the tree region: pages, a bitmap per zone of 1024 slots; at least a fresh game's pages for every slot
         size_t region = tree_bytes;
         {
@@ -1886,9 +1885,6 @@ struct Engine {
     uint64_t gather_launches = 0;
     bool overlap_advance = true;
     bool merge_per_group = false;
-    bool stagger_gathers = false;
-    int cu_split = 0;  // 1: groups on the low / high half of the CU mask bits, 2: even / odd bits
-    bool adv_late = true;   // AR_ADV_LATE=0: the tree reuse beside the group's next tree walk, as before
     std::vector<Group> groups;
     int make_groups(uint32_t n) {
         if (n < 1) n = 1;
@@ -1910,26 +1906,14 @@ struct Engine {
             // = 4); a fifth stream shares a queue with another and the pipeline collapses (measured: 321 M against
             // 565 M simulations/s)
             HIP_TRY(hipEventCreateWithFlags(&groups[g].gathered, hipEventDisableTiming));
-            // (AR_CUMASK=lohi|evenodd, off by default) every group on its own half of the compute units: the streams of
-            // group g are created with a CU mask, so that kernels of different groups never share a CU
-            uint32_t mask[8];
-            const bool masked = cu_split != 0 && n == 2;
-            for (int w = 0; w < 8; ++w)
-                mask[w] = cu_split == 2 ? (g == 0 ? 0x55555555u : 0xAAAAAAAAu) : ((w < 4) == (g == 0) ? 0xFFFFFFFFu : 0u);
-            if (g > 0 || masked) {
-                if (masked)
-                    HIP_TRY(hipExtStreamCreateWithCUMask(&groups[g].stream, 8, mask));
-                else
-                    HIP_TRY(hipStreamCreateWithFlags(&groups[g].stream, hipStreamNonBlocking));
+            if (g > 0) {
+                HIP_TRY(hipStreamCreateWithFlags(&groups[g].stream, hipStreamNonBlocking));
                 HIP_TRY(hipEventCreateWithFlags(&groups[g].done, hipEventDisableTiming));
             } else {
                 groups[g].stream = stream;
             }
             if (overlap_advance) {
-                if (masked)
-                    HIP_TRY(hipExtStreamCreateWithCUMask(&groups[g].adv_stream, 8, mask));
-                else
-                    HIP_TRY(hipStreamCreateWithFlags(&groups[g].adv_stream, hipStreamNonBlocking));
+                HIP_TRY(hipStreamCreateWithFlags(&groups[g].adv_stream, hipStreamNonBlocking));
                 HIP_TRY(hipEventCreateWithFlags(&groups[g].backed_up, hipEventDisableTiming));
                 HIP_TRY(hipEventCreateWithFlags(&groups[g].adv_done, hipEventDisableTiming));
                 HIP_TRY(hipEventCreateWithFlags(&groups[g].adv_ev[0], hipEventDisableTiming));
@@ -1948,23 +1932,14 @@ struct Engine {
         EvalOut* ev = ev_queue.p + (size_t)g.first * cfg.batch_size;
         uint32_t* qc = queue_count.p + gi;
         HIP_TRY(hipMemsetAsync(qc, 0, 4, g.stream));
-        // (AR_STAGGER=1, off by default) One gather at a time: a group's tree walk starts when the previous group's (in launch
-        // order) has ended. Left to themselves the groups drift into step -- both walk, then both evaluate (kernel trace,
-        // profiles/r03_timeline_131k.txt) -- so stages do not overlap across groups. Held apart they do not overlap either:
-        // the persistent gather fills every SIMD's registers (2 x 212 of 512 when this was measured) and the
-        // evaluator's wavefronts (141) wait for it to end: 588 vs 643 M simulations/s, also with half the gather wavefronts (570 M).
-        if (stagger_gathers && groups.size() > 1)
-            HIP_TRY(hipStreamWaitEvent(g.stream, groups[(gi + groups.size() - 1) % groups.size()].gathered, 0));
-        const bool timed_launch = true;  // every group's gather launch is timed on its own stream
-        if (timed_launch) {
-            while (gather_ev.size() < gather_ev_used + 2) {
-                hipEvent_t e = nullptr;
-                HIP_TRY(hipEventCreate(&e));
-                gather_ev.push_back(e);
-            }
-            HIP_TRY(hipEventRecord(gather_ev[gather_ev_used], g.stream));
+        while (gather_ev.size() < gather_ev_used + 2) {  // every group's gather launch is timed on its own stream
+            hipEvent_t e = nullptr;
+            HIP_TRY(hipEventCreate(&e));
+            gather_ev.push_back(e);
         }
-        if (gatherw) {
+        HIP_TRY(hipEventRecord(gather_ev[gather_ev_used], g.stream));
+        switch (gather) {
+        case GatherKernel::Wide: {
             // a persistent grid: at most gatherw_waves wavefronts, and at small sizes about four games per wavefront
             constexpr int GWG = NW == 1 ? 32 : 16;
             uint32_t waves = (n + 3) / 4;
@@ -1973,26 +1948,27 @@ struct Engine {
             const uint32_t rot = second_turn ? (uint32_t)((g.step * (uint64_t)second_turn) % n_sets) : 0u;
             hipLaunchKernelGGL((k_gatherw<NW, GWG, GW_RECS>), dim3(waves), dim3(64), (size_t)bases().maze_stage, g.stream, slots.p, g.end, cfg,
                                bases(), g.first, phase, ready, gatherw_passes, rot);
-        } else if (gather8 && gather8_wpe == 3)
-            hipLaunchKernelGGL((k_gather8<NW, 3>), dim3((n + 7) / 8), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), q,
-                               qc, g.first, phase, ready);
-        else if (gather8 && gather8_wpe == 4)
-            hipLaunchKernelGGL((k_gather8<NW, 4>), dim3((n + 7) / 8), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), q,
-                               qc, g.first, phase, ready);
-        else if (gather8)
+            break;
+        }
+        case GatherKernel::Octet2:
             hipLaunchKernelGGL((k_gather8<NW, 2>), dim3((n + 7) / 8), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), q,
                                qc, g.first, phase, ready);
-        else
-            hipLaunchKernelGGL(k_gather<NW>, dim3((n + lanes - 1) / lanes), dim3(64), 0, g.stream, slots.p, g.end, cfg,
-                               bases(), q, qc, gather_rounds, lanes, g.first, phase, ready);
-        if (timed_launch) {
-            HIP_TRY(hipEventRecord(gather_ev[gather_ev_used + 1], g.stream));
-            gather_ev_used += 2;
+            break;
+        case GatherKernel::Octet3:
+            hipLaunchKernelGGL((k_gather8<NW, 3>), dim3((n + 7) / 8), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), q,
+                               qc, g.first, phase, ready);
+            break;
+        case GatherKernel::Lane:
+            hipLaunchKernelGGL(k_gather<NW>, dim3(grid(n)), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), q, qc,
+                               gather_rounds, g.first, phase, ready);
+            break;
         }
+        HIP_TRY(hipEventRecord(gather_ev[gather_ev_used + 1], g.stream));
+        gather_ev_used += 2;
         HIP_TRY(hipEventRecord(g.gathered, g.stream));
         if (g.adv_pending)
             if (int rc = launch_late_advance(g)) return rc;
-        if (gatherw)
+        if (gather == GatherKernel::Wide)
             hipLaunchKernelGGL(k_pack_leaves<NW>, dim3((n + 63) / 64), dim3(64), 0, g.stream, slots.p, g.end, bases(), g.first, q, qc);
         const uint32_t n_max = (uint32_t)((size_t)n * cfg.batch_size);
         if (cache_entries && net != nullptr) {
@@ -2018,38 +1994,25 @@ struct Engine {
             hipLaunchKernelGGL(k_finish<NW>, dim3(grid(n)), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), g.first, phase);
             // (fresh roots that draw Dirichlet noise were left alone above; k_finish ignores a slot with a batch pending)
             if (cfg.noise_epsilon > 0.0f)
-                hipLaunchKernelGGL(k_backup<NW>, dim3((n + 63) / 64), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), zig.p,
-                                   ev, 64u, g.first, phase);
+                hipLaunchKernelGGL(k_backup<NW>, dim3(grid(n)), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), zig.p, ev,
+                                   g.first, phase);
         } else
-            hipLaunchKernelGGL(k_backup<NW>, dim3((n + backup_lanes - 1) / backup_lanes), dim3(64), 0, g.stream, slots.p, g.end,
-                               cfg, bases(), zig.p, ev, backup_lanes, g.first, phase);
-        // blocks the group's trees left at the last step go back on the free stacks (nothing reads them any more, and
-        // this stream is the only one that pops or returns in the group's zones)
-        if (side && adv_late) {
+            hipLaunchKernelGGL(k_backup<NW>, dim3(grid(n)), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), zig.p, ev,
+                               g.first, phase);
+        if (side) {
             // The tree reuse of this step is launched behind the NEXT gather of the group (launch_late_advance),
             // so that it runs beside the evaluator, which leaves the memory system alone, instead of beside the tree walk,
             // which it slows down by a fifth (profiles/r03_sweeps.md: the gather launch with and without k_advance beside it)
             HIP_TRY(hipEventRecord(g.backed_up, g.stream));
             g.adv_pending = true;
             g.adv_phase = phase;
-            g.step += 1;
-            return AR_OK;
-        }
-        if (merge_per_group && pool.bits) {
-            const uint32_t z0 = g.first / POOL_ZONE_SLOTS, z1 = (g.end + POOL_ZONE_SLOTS - 1) / POOL_ZONE_SLOTS;
-            if (side) {
-                HIP_TRY(hipEventRecord(g.backed_up, g.stream));
-                HIP_TRY(hipStreamWaitEvent(g.adv_stream, g.backed_up, 0));
-            }
-            hipLaunchKernelGGL(k_pool_merge, dim3(z1 - z0), dim3(64), 0, side ? g.adv_stream : g.stream, pool, z0, z1 - z0);
-        }
-        if (side) {
-            HIP_TRY(hipEventRecord(g.backed_up, g.stream));
-            HIP_TRY(hipStreamWaitEvent(g.adv_stream, g.backed_up, 0));
-            hipLaunchKernelGGL(k_advance<NW>, dim3(n), dim3(64), 0, g.adv_stream, slots.p, g.end, bases(), cfg, g.first,
-                               phase, ready);
-            HIP_TRY(hipEventRecord(g.adv_ev[phase], g.adv_stream));
         } else {
+            // blocks the group's trees left at the last step go back on the free stacks (nothing reads them any more, and
+            // this stream is the only one that pops or returns in the group's zones)
+            if (merge_per_group && pool.bits) {
+                const uint32_t z0 = g.first / POOL_ZONE_SLOTS, z1 = (g.end + POOL_ZONE_SLOTS - 1) / POOL_ZONE_SLOTS;
+                hipLaunchKernelGGL(k_pool_merge, dim3(z1 - z0), dim3(64), 0, g.stream, pool, z0, z1 - z0);
+            }
             hipLaunchKernelGGL(k_advance<NW>, dim3(n), dim3(64), 0, g.stream, slots.p, g.end, bases(), cfg, g.first, 0u,
                                (uint32_t)SLOT_ACTIVE);
         }
@@ -2075,13 +2038,13 @@ struct Engine {
     }
 
     void launch_gather(bool to_queue) {
-        hipLaunchKernelGGL(k_gather<NW>, dim3((S + lanes - 1) / lanes), dim3(64), 0, stream, slots.p, S, cfg, bases(),
+        hipLaunchKernelGGL(k_gather<NW>, dim3(grid(S)), dim3(64), 0, stream, slots.p, S, cfg, bases(),
                            to_queue ? queue.p : (LeafReq<NW>*)nullptr, to_queue ? queue_count.p : (uint32_t*)nullptr,
-                           gather_rounds, lanes, 0u, 0u, (uint32_t)SLOT_ACTIVE);
+                           gather_rounds, 0u, 0u, (uint32_t)SLOT_ACTIVE);
     }
     void launch_backup(bool from_queue) {
-        hipLaunchKernelGGL(k_backup<NW>, dim3((S + lanes - 1) / lanes), dim3(64), 0, stream, slots.p, S, cfg, bases(),
-                           zig.p, from_queue ? ev_queue.p : (const EvalOut*)nullptr, lanes, 0u, 0u);
+        hipLaunchKernelGGL(k_backup<NW>, dim3(grid(S)), dim3(64), 0, stream, slots.p, S, cfg, bases(), zig.p,
+                           from_queue ? ev_queue.p : (const EvalOut*)nullptr, 0u, 0u);
     }
     void launch_advance() {
         if (pool.bits) hipLaunchKernelGGL(k_pool_merge, dim3(pool.zones), dim3(64), 0, stream, pool, 0u, pool.zones);
@@ -2421,10 +2384,6 @@ int parse_device(const char* device, int device_index, int& out) {
 // ------------------------------------------------------------------------------------------------
 // self-play driver
 // ------------------------------------------------------------------------------------------------
-// Round limit of one gather launch: a few rounds per wanted descent covers the typical batch (a
-// descent is one round per tree level) and cuts the long tail; measured in DESIGN.md section 7.
-static uint32_t default_gather_rounds(const SearchCfg&) { return 0xFFFFFFFFu; }
-
 // A self-play run as an object that outlives one call: the engine, its resident games and the supply of
 // new games stay alive between ar_selfplay_step calls, so a caller can run the sampler in bounded slices
 // (the benchmark's "step") or to the end (ar_selfplay_run = open + step until finished + close).
@@ -2466,8 +2425,8 @@ struct SelfPlaySession : SessionBase {
     void info(ArSessionInfo* out) const override {
         out->resident_games = S;
         out->groups = (uint32_t)(eng.groups.empty() ? 1 : eng.groups.size());
-        out->gather_kind = !eng.use_queue() ? 3u : eng.gatherw ? 2u : eng.gather8 ? 1u : 0u;
-        out->gather_pass_limit = eng.gatherw ? eng.gatherw_passes : 0xFFFFFFFFu;
+        out->gather_kind = !eng.use_queue() ? 3u : eng.gather == GatherKernel::Wide ? 2u : eng.gather == GatherKernel::Lane ? 0u : 1u;
+        out->gather_pass_limit = eng.gather == GatherKernel::Wide ? eng.gatherw_passes : 0xFFFFFFFFu;
         out->tree_region_bytes = eng.region_bytes;
         out->host_grown_arenas = eng.grows;
         out->idle_slots = (uint32_t)idle_slots.size();
@@ -2643,15 +2602,15 @@ struct SelfPlaySession : SessionBase {
             if (atof(e) > 0.0) pool_bytes = (size_t)(atof(e) * 1073741824.0);
         eng.per_slot_maze = gen_maze;
         eng.maze_stride = (uint32_t)hw * 4u;
+        // rounds per gather launch (dev_search.h gather_machine_limited): no limit unless AR_GATHER_ROUNDS sets one
+        // (0 = no limit); a limit keeps the walk on the lane kernel
+        if (const char* e = getenv("AR_GATHER_ROUNDS")) eng.gather_rounds = atoi(e) > 0 ? (uint32_t)atoi(e) : 0xFFFFFFFFu;
         {
             // generated mazes: one pool entry per slot (filled when a game starts there); open: the one shared maze
             const std::vector<uint8_t> pool_init = gen_maze ? std::vector<uint8_t>((size_t)S * hw * 4, (uint8_t)0) : cost;
             if (int rc = eng.setup(device, S, cfg, p.max_turns, pool_init, arena_nodes, net != nullptr || eng.uniform_queue, pool_bytes)) return rc;
         }
         tm[0] = since(tp);
-        // rounds per gather launch (dev_search.h gather_machine_limited); AR_GATHER_ROUNDS overrides, 0 = no limit
-        eng.gather_rounds = default_gather_rounds(cfg);
-        if (const char* e = getenv("AR_GATHER_ROUNDS")) eng.gather_rounds = atoi(e) > 0 ? (uint32_t)atoi(e) : 0xFFFFFFFFu;
         {
             // groups of games pipelined against each other (Engine::group_step); AR_GROUPS overrides
             // two groups from 8192 games up (one group's evaluator runs beside the other group's tree walks: +6..18 %,
@@ -2661,16 +2620,8 @@ struct SelfPlaySession : SessionBase {
                 if (atoi(e) >= 1 && atoi(e) <= 64) ng = (uint32_t)atoi(e);
             if (eng.cache_entries) ng = 1;  // one probe/fill pair in flight at a time: a reader never overlaps an eviction
             if (getenv("AR_NO_ADVANCE_OVERLAP")) eng.overlap_advance = false;
-            if (getenv("AR_STAGGER")) eng.stagger_gathers = true;
-            if (const char* e = getenv("AR_ADV_LATE")) eng.adv_late = atoi(e) != 0;
-            if (const char* e = getenv("AR_CUMASK")) eng.cu_split = std::string(e) == "lohi" ? 1 : std::string(e) == "evenodd" ? 2 : 0;
             if (int rc = eng.make_groups(ng)) return rc;
         }
-        if (const char* e = getenv("AR_LANES_PER_WAVE"))
-            if (atoi(e) >= 1 && atoi(e) <= 64) eng.lanes = eng.backup_lanes = (uint32_t)atoi(e);
-        if (const char* e = getenv("AR_BACKUP_LANES"))
-            if (atoi(e) >= 1 && atoi(e) <= 64) eng.backup_lanes = (uint32_t)atoi(e);
-        if (eng.gather_rounds != 0xFFFFFFFFu) eng.gather8 = eng.gatherw = false;  // the round limit parks the walk: lane kernel only
         if (to_disk) writer.start();
         slot_game.resize(S);
         slot_busy.assign(S, 0);

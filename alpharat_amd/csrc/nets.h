@@ -1234,13 +1234,6 @@ static int net_build(const arnet::Blob& b, ArNet* net) {
             c.L = 128 * c.MT / c.hw;
             if (c.L > CNN_TILE_MAX) c.L = CNN_TILE_MAX;
             while (c.L > 1 && (size_t)c.L * c.C * chs * 4 > 64 * 1024) c.L -= 1;
-            if (const char* e = getenv("AR_CNN_L")) {  // tuning knob: leaves per workgroup (more rows per tile, fewer workgroups per CU)
-                const int want = atoi(e);
-                if (want >= 1 && want <= CNN_TILE_MAX && want * c.hw <= 256) {
-                    c.L = want;
-                    c.MT = want * c.hw > 128 ? 2 : 1;
-                }
-            }
         } else if (c.C % 32 == 0 && (c.width > 8 || c.height > 8)) {
             return nets_fail(AR_E_BACKEND, "AR_CNN_LDS: the three-image CNN kernel handles 32 / 64 channels on boards up to 8x8");
         }
@@ -1381,11 +1374,10 @@ static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcou
     using namespace arnet;
     if (n_max == 0) return AR_OK;
     const bool mlp_mfma = net->dev.arch == ARCH_MLP && mlp_all_mfma(net->dev.H);
-    static const int mlp_mt = getenv("AR_MLP_MT") && atoi(getenv("AR_MLP_MT")) == 1 ? 1 : MLP_MFMA_MT;  // tuning knob
     // (k_symmetric_mfma2 stages the shared encoder's operand, hw + 1 values, at the head of a row of its buffer)
     const bool sym_mfma = net->dev.arch == ARCH_SYMMETRIC && symmetric_mfma_ok(net->dev.H) && !getenv("AR_SYM_FMA") &&
                           ((net->dev.hw + 2) & ~1) <= net->dev.H + 4;
-    const int tile = mlp_mfma ? 32 * mlp_mt : net->dev.arch == ARCH_MLP ? TILE_MLP : net->dev.arch == ARCH_CNN ? net->cnn.L
+    const int tile = mlp_mfma ? 32 * MLP_MFMA_MT : net->dev.arch == ARCH_MLP ? TILE_MLP : net->dev.arch == ARCH_CNN ? net->cnn.L
                                                                         : sym_mfma ? 32 : TILE_SYM;
     const uint32_t blocks = (n_max + tile - 1) / tile;
     if (net->dev.arch == ARCH_CNN && net->cnn.MT) {
@@ -1405,7 +1397,7 @@ static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcou
         hipLaunchKernelGGL(k_cnn<NW>, dim3(blocks), dim3(NTHREADS), net->smem, stream, net->cnn, q, qcount, n_max, boards,
                            board_stride, net->bound_pool, out, logits);
     } else if (mlp_mfma) {
-        const size_t smem = (size_t)32 * mlp_mt * (net->dev.H + 4) * 4;
+        const size_t smem = (size_t)32 * MLP_MFMA_MT * (net->dev.H + 4) * 4;
         // first-layer variant (k_mlp_mfma's FL): 2 unless AR_MLP_FL says otherwise (read per launch: a test toggles it);
         // 0 needs the whole observation's non-maze part in a row of `act`
         int fl = getenv("AR_MLP_FL") ? atoi(getenv("AR_MLP_FL")) : 2;
@@ -1414,24 +1406,13 @@ static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcou
         if (fl < 0 || fl > 2) fl = 2;
         if (fl == 2 && K2e > net->dev.H + 4) fl = 1;  // (the staged operand is a row of `act`: narrow hidden layers on big boards)
         if (fl == 0 && K1e > net->dev.H + 4) fl = 1;
-        const void* fns[2][3] = {{(const void*)k_mlp_mfma<NW, 1, 0>, (const void*)k_mlp_mfma<NW, 1, 1>, (const void*)k_mlp_mfma<NW, 1, 2>},
-                                 {(const void*)k_mlp_mfma<NW, 2, 0>, (const void*)k_mlp_mfma<NW, 2, 1>, (const void*)k_mlp_mfma<NW, 2, 2>}};
-        const void* fn = fns[mlp_mt == 1 ? 0 : 1][fl];
-        if (smem > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+        decltype(&k_mlp_mfma<NW, MLP_MFMA_MT, 0>) const fns[3] = {k_mlp_mfma<NW, MLP_MFMA_MT, 0>, k_mlp_mfma<NW, MLP_MFMA_MT, 1>,
+                                                                   k_mlp_mfma<NW, MLP_MFMA_MT, 2>};
+        if (smem > 48 * 1024 &&
+            hipFuncSetAttribute((const void*)fns[fl], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
             return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the MLP kernel");
-#define AR_MLP_LAUNCH(MT_, FL_)                                                                                          \
-    hipLaunchKernelGGL((k_mlp_mfma<NW, MT_, FL_>), dim3(blocks), dim3(NTHREADS), smem, stream, net->dev, q, qcount, n_max, \
-                       boards, board_stride, out, logits)
-        if (mlp_mt == 1) {
-            if (fl == 0) AR_MLP_LAUNCH(1, 0);
-            else if (fl == 1) AR_MLP_LAUNCH(1, 1);
-            else AR_MLP_LAUNCH(1, 2);
-        } else {
-            if (fl == 0) AR_MLP_LAUNCH(2, 0);
-            else if (fl == 1) AR_MLP_LAUNCH(2, 1);
-            else AR_MLP_LAUNCH(2, 2);
-        }
-#undef AR_MLP_LAUNCH
+        hipLaunchKernelGGL(fns[fl], dim3(blocks), dim3(NTHREADS), smem, stream, net->dev, q, qcount, n_max, boards, board_stride,
+                           out, logits);
     } else if (net->dev.arch == ARCH_MLP) {
         if (net->smem > 48 * 1024 &&
             hipFuncSetAttribute((const void*)k_mlp<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)net->smem) !=

@@ -111,9 +111,10 @@ def test_network_selfplay_records_bit_exact(name, blob, sims, search, n_games, n
 
 @pytest.mark.parametrize("shape", ["wide", "octet3", "lane"])
 def test_network_selfplay_other_gather_shapes_bit_exact_vs_oracle(shape, monkeypatch):
-    """The gather kernels with four, two and one lane per game (AR_GATHER; eight lanes is the default the cases above run
-    on) against the oracle at record level: tuned constants + noise, 600 simulations, more games than slots. (That all
-    shapes produce the same records as each other is test_selfplay_records_do_not_depend_on_scheduling.)"""
+    """The gather kernels AR_GATHER selects -- the work queue over tree levels (wide), eight lanes per game with the
+    three-wavefront register budget (octet3) and one lane per game (lane) -- against the oracle at record level: tuned
+    constants + noise, 600 simulations, more games than slots. (That all shapes produce the same records as each other
+    is test_selfplay_records_do_not_depend_on_scheduling.)"""
     from alpharat_amd.sampling import rust_self_play
 
     monkeypatch.setenv("AR_GATHER", shape)
