@@ -30,7 +30,9 @@ static int nets_fail(int code, const std::string& msg);
 
 namespace arnet {
 
-enum { ARCH_MLP = 0, ARCH_SYMMETRIC = 1, ARCH_CNN = 2 };
+enum { ARCH_MLP = 0, ARCH_SYMMETRIC = 1, ARCH_CNN = 2, ARCH_CNN_KATAGO = 3 };
+// the convolutional nets (PyRatCNN, KataGoCNN) read the maze planes themselves and run on the CNN kernels
+__host__ __device__ inline bool is_cnn(int arch) { return arch == ARCH_CNN || arch == ARCH_CNN_KATAGO; }
 static const int TILE_MLP = 32;  // leaves per block
 static const int TILE_SYM = 16;
 static const int NTHREADS = 256;
@@ -90,6 +92,15 @@ struct Blob {
     const std::vector<float>* get(const std::string& k) const {
         auto it = t.find(k);
         return it == t.end() ? nullptr : &it->second;
+    }
+    // tensor `k` of exactly this shape, or nullptr with `err` naming the shape wanted
+    const std::vector<float>* get(const std::string& k, std::initializer_list<uint32_t> shape, std::string& err) const {
+        auto it = dims.find(k);
+        if (it != dims.end() && it->second == std::vector<uint32_t>(shape)) return &t.at(k);
+        err = "weight blob: " + k + " must be [";
+        for (const uint32_t* d = shape.begin(); d != shape.end(); ++d) err += (d == shape.begin() ? "" : ", ") + std::to_string(*d);
+        err += it == dims.end() ? "] (missing)" : "]";
+        return nullptr;
     }
 };
 
@@ -1148,6 +1159,73 @@ struct ArNet {
     }
 };
 
+// PyRatCNN's trunk blocks (blocks.N.*: ResBlock / GPoolResBlock, shared by KataGoCNN) -> net->cnn.blk, every tensor's
+// size checked; raises `small_floats` to the gpool branches' LDS need and `g_max` to the widest gpool branch
+static int cnn_load_blocks(const arnet::Blob& b, ArNet* net, size_t& small_floats, size_t& g_max) {
+    using namespace arnet;
+    CnnDev& c = net->cnn;
+    const size_t TL = (size_t)c.L;
+    const uint32_t C = (uint32_t)c.C;
+    std::string err;
+    bool ok = true;
+    for (int bi = 0;; ++bi) {
+        const std::string p = "blocks." + std::to_string(bi);
+        if (!b.get(p + ".conv1.weight")) break;
+        if (bi >= CNN_MAX_BLOCKS) return nets_fail(AR_E_BACKEND, "too many trunk blocks");
+        const std::vector<float>*w1 = b.get(p + ".conv1.weight", {C, C, 3, 3}, err), *w2 = w1 ? b.get(p + ".conv2.weight", {C, C, 3, 3}, err) : nullptr;
+        if (!w2) return nets_fail(AR_E_BACKEND, err);
+        CnnBlockDev& k = c.blk[bi];
+        std::vector<double> a1, b1, a2, b2;
+        if (!bn_affine(b, p + ".bn1", c.C, a1, b1, err) || !bn_affine(b, p + ".bn2", c.C, a2, b2, err))
+            return nets_fail(AR_E_BACKEND, err);
+        k.bn1_a = net->upload(std::vector<float>(a1.begin(), a1.end()), ok);
+        k.bn1_b = net->upload(std::vector<float>(b1.begin(), b1.end()), ok);
+        k.w1 = net->upload(conv_t(*w1, c.C, c.C, &a2), ok);
+        k.b1 = net->upload(std::vector<float>(b2.begin(), b2.end()), ok);
+        k.w2 = net->upload(conv_t(*w2, c.C, c.C, nullptr), ok);
+        k.gpool = 0;
+        if (b.get(p + ".pool_conv.weight")) {
+            const std::vector<uint32_t>& pd = b.dims.at(p + ".pool_conv.weight");
+            const uint32_t G = pd.size() == 4 ? pd[0] : 0;
+            const std::vector<float>* pw = G ? b.get(p + ".pool_conv.weight", {G, C, 1, 1}, err) : nullptr;
+            if (!pw) return nets_fail(AR_E_BACKEND, G ? err : "weight blob: " + p + ".pool_conv.weight must be [G, C, 1, 1]");
+            k.gpool = (int)G;
+            std::vector<double> pa, pb;
+            if (!bn_affine(b, p + ".pool_bn", c.C, pa, pb, err)) return nets_fail(AR_E_BACKEND, err);
+            k.pbn_a = net->upload(std::vector<float>(pa.begin(), pa.end()), ok);
+            k.pbn_b = net->upload(std::vector<float>(pb.begin(), pb.end()), ok);
+            std::vector<float> wpt((size_t)c.C * G);
+            for (uint32_t g = 0; g < G; ++g)
+                for (int ci = 0; ci < c.C; ++ci) wpt[(size_t)ci * G + g] = (*pw)[(size_t)g * c.C + ci];
+            k.wp = net->upload(wpt, ok);
+            const std::vector<float>* lw = b.get(p + ".pool_linear.weight", {C, 2 * G}, err);
+            const std::vector<float>* lb = lw ? b.get(p + ".pool_linear.bias", {C}, err) : nullptr;
+            if (!lb) return nets_fail(AR_E_BACKEND, err);
+            std::vector<float> wlt((size_t)2 * G * c.C);
+            for (int o = 0; o < c.C; ++o)
+                for (uint32_t kk = 0; kk < 2 * G; ++kk) wlt[(size_t)kk * c.C + o] = (*lw)[(size_t)o * 2 * G + kk];
+            k.wl = net->upload(wlt, ok);
+            k.bl = net->upload(*lb, ok);
+            if (TL * (c.C + 2 * G) > small_floats) small_floats = TL * (c.C + 2 * G);
+            if ((size_t)G > g_max) g_max = (size_t)G;
+            if (c.MT && G > 64) return nets_fail(AR_E_BACKEND, "gpool_channels above 64");
+        }
+        c.n_blocks = bi + 1;
+    }
+    if (!ok) return nets_fail(AR_E_NOMEM, "device allocation failed while loading weights");
+    return AR_OK;
+}
+
+// k_cnn_mfma's tile for a board of up to 256 cells: MT row tiles of 32 per wavefront, L leaves (L * hw <= 128 MT rows)
+// per workgroup, chosen so that the image stays under 64 KB (several workgroups per CU) unless a single leaf needs more
+static void cnn_mfma_tile(arnet::CnnDev& c) {
+    const size_t chs = (size_t)(c.height + 2) * (c.width + 2);
+    c.MT = c.hw > 128 ? 2 : 1;
+    c.L = 128 * c.MT / c.hw;
+    if (c.L > arnet::CNN_TILE_MAX) c.L = arnet::CNN_TILE_MAX;
+    while (c.L > 1 && (size_t)c.L * c.C * chs * 4 > 64 * 1024) c.L -= 1;
+}
+
 static int net_build(const arnet::Blob& b, ArNet* net) {
     using namespace arnet;
     std::string err;
@@ -1229,11 +1307,9 @@ static int net_build(const arnet::Blob& b, ArNet* net) {
         c.MT = 0;
         c.L = CNN_TILE;
         const size_t chs = (size_t)(c.height + 2) * (c.width + 2);
-        if (c.C % 32 == 0 && c.hw <= 256 && !getenv("AR_CNN_LDS")) {  // (AR_CNN_LDS: the three-image kernel, A/B knob; boards <= 8x8)
-            c.MT = c.hw > 128 ? 2 : 1;
-            c.L = 128 * c.MT / c.hw;
-            if (c.L > CNN_TILE_MAX) c.L = CNN_TILE_MAX;
-            while (c.L > 1 && (size_t)c.L * c.C * chs * 4 > 64 * 1024) c.L -= 1;
+        // (AR_CNN_LDS: the three-image kernel, A/B knob; boards <= 8x8. No effect on KataGoCNN, which has no such kernel)
+        if (c.C % 32 == 0 && c.hw <= 256 && !getenv("AR_CNN_LDS")) {
+            cnn_mfma_tile(c);
         } else if (c.C % 32 == 0 && (c.width > 8 || c.height > 8)) {
             return nets_fail(AR_E_BACKEND, "AR_CNN_LDS: the three-image CNN kernel handles 32 / 64 channels on boards up to 8x8");
         }
@@ -1244,46 +1320,7 @@ static int net_build(const arnet::Blob& b, ArNet* net) {
         c.stem_w = net->upload(conv_t(*sw, c.C, 5, &sa), ok);
         c.stem_b = net->upload(std::vector<float>(sb.begin(), sb.end()), ok);
         size_t small_floats = 0;
-        for (int bi = 0;; ++bi) {
-            const std::string p = "blocks." + std::to_string(bi);
-            const std::vector<float>*w1 = b.get(p + ".conv1.weight"), *w2 = b.get(p + ".conv2.weight");
-            if (!w1) break;
-            if (bi >= CNN_MAX_BLOCKS) return nets_fail(AR_E_BACKEND, "too many trunk blocks");
-            if (!w2) return nets_fail(AR_E_BACKEND, "weight blob lacks " + p + ".conv2.weight");
-            CnnBlockDev& k = c.blk[bi];
-            std::vector<double> a1, b1, a2, b2;
-            if (!bn_affine(b, p + ".bn1", c.C, a1, b1, err) || !bn_affine(b, p + ".bn2", c.C, a2, b2, err))
-                return nets_fail(AR_E_BACKEND, err);
-            k.bn1_a = net->upload(std::vector<float>(a1.begin(), a1.end()), ok);
-            k.bn1_b = net->upload(std::vector<float>(b1.begin(), b1.end()), ok);
-            k.w1 = net->upload(conv_t(*w1, c.C, c.C, &a2), ok);
-            k.b1 = net->upload(std::vector<float>(b2.begin(), b2.end()), ok);
-            k.w2 = net->upload(conv_t(*w2, c.C, c.C, nullptr), ok);
-            k.gpool = 0;
-            if (const std::vector<float>* pw = b.get(p + ".pool_conv.weight")) {
-                const int G = (int)b.dims.at(p + ".pool_conv.weight")[0];
-                k.gpool = G;
-                std::vector<double> pa, pb;
-                if (!bn_affine(b, p + ".pool_bn", c.C, pa, pb, err)) return nets_fail(AR_E_BACKEND, err);
-                k.pbn_a = net->upload(std::vector<float>(pa.begin(), pa.end()), ok);
-                k.pbn_b = net->upload(std::vector<float>(pb.begin(), pb.end()), ok);
-                std::vector<float> wpt((size_t)c.C * G);
-                for (int g = 0; g < G; ++g)
-                    for (int ci = 0; ci < c.C; ++ci) wpt[(size_t)ci * G + g] = (*pw)[(size_t)g * c.C + ci];
-                k.wp = net->upload(wpt, ok);
-                const std::vector<float>*lw = b.get(p + ".pool_linear.weight"), *lb = b.get(p + ".pool_linear.bias");
-                if (!lw || !lb) return nets_fail(AR_E_BACKEND, "weight blob lacks " + p + ".pool_linear");
-                std::vector<float> wlt((size_t)2 * G * c.C);
-                for (int o = 0; o < c.C; ++o)
-                    for (int kk = 0; kk < 2 * G; ++kk) wlt[(size_t)kk * c.C + o] = (*lw)[(size_t)o * 2 * G + kk];
-                k.wl = net->upload(wlt, ok);
-                k.bl = net->upload(*lb, ok);
-                if (TL * (c.C + 2 * G) > small_floats) small_floats = TL * (c.C + 2 * G);
-                if ((size_t)G > g_max) g_max = (size_t)G;
-                if (c.MT && G > 64) return nets_fail(AR_E_BACKEND, "gpool_channels above 64");
-            }
-            c.n_blocks = bi + 1;
-        }
+        if (int rc = cnn_load_blocks(b, net, small_floats, g_max)) return rc;
         if (!fold_linear(b, "player_encoder.0", "", wt, bias, in, out, err) || in != 3) return nets_fail(AR_E_BACKEND, "bad player_encoder");
         c.PD = (int)out;
         c.pe_w = net->upload(wt, ok);
@@ -1327,6 +1364,77 @@ static int net_build(const arnet::Blob& b, ArNet* net) {
             net->smem = (TL * c.C * c.hw + 2 * TL * c.C * chs + small_floats + 64) * 4;
         }
         d.H = 4;  // unused by the CNN path
+    } else if (b.arch == ARCH_CNN_KATAGO) {
+        // KataGoCNN (cnn/katago.py): k_cnn_mfma<.., true>, so C = 32 / 64 on boards up to 256 cells
+        CnnDev& c = net->cnn;
+        memset(&c, 0, sizeof c);
+        c.width = d.width;
+        c.height = d.height;
+        c.hw = d.hw;
+        auto st = b.dims.find("stem.weight");
+        if (st == b.dims.end() || st->second.size() != 4 || st->second[1] != 7 || st->second[2] != 3 || st->second[3] != 3)
+            return nets_fail(AR_E_BACKEND, "weight blob: KataGoCNN stem.weight must be [C, 7, 3, 3]");
+        c.C = (int)st->second[0];
+        if (c.C != 32 && c.C != 64)
+            return nets_fail(AR_E_BACKEND, "KataGoCNN with " + std::to_string(c.C) +
+                                               " trunk channels is not supported (supported widths: 32, 64)");
+        if (c.hw > 256) return nets_fail(AR_E_BACKEND, "KataGoCNN: boards up to 256 cells are supported");
+        const uint32_t C = (uint32_t)c.C;
+        cnn_mfma_tile(c);
+        const size_t TL = (size_t)c.L, chs = (size_t)(c.height + 2) * (c.width + 2);
+        std::vector<double> sa, sb;
+        if (!bn_affine(b, "stem_bn", c.C, sa, sb, err)) return nets_fail(AR_E_BACKEND, err);
+        const std::vector<float>* sw = b.get("stem.weight");
+        const std::vector<float>* ew = b.get("scalar_encoder.weight", {C, 6}, err);
+        const std::vector<float>* eb = ew ? b.get("scalar_encoder.bias", {C}, err) : nullptr;
+        if (!eb) return nets_fail(AR_E_BACKEND, err);
+        // a (conv + Ws s + bs) + c = (a conv) + (a Ws) s + (a bs + c)
+        std::vector<float> sbias(C), scw((size_t)6 * C);
+        for (uint32_t co = 0; co < C; ++co) {
+            sbias[co] = (float)(sa[co] * (double)(*eb)[co] + sb[co]);
+            for (int k = 0; k < 6; ++k) scw[(size_t)k * C + co] = (float)(sa[co] * (double)(*ew)[(size_t)co * 6 + k]);
+        }
+        c.stem_w = net->upload(conv_t(*sw, c.C, 7, &sa), ok);
+        c.stem_b = net->upload(sbias, ok);
+        c.sc_w = net->upload(scw, ok);
+        size_t small_floats = TL * C, g_max = 0;  // (the stem's per-leaf bias)
+        if (int rc = cnn_load_blocks(b, net, small_floats, g_max)) return rc;
+        auto pm = b.dims.find("pool_mlp.0.weight");
+        c.HD = pm != b.dims.end() && pm->second.size() == 2 ? (int)pm->second[0] : 0;
+        if (c.HD < 1 || c.HD > 1024) return nets_fail(AR_E_BACKEND, "weight blob: KataGoCNN pool_mlp.0.weight must be [HD, 2C], HD <= 1024");
+        const uint32_t HD = (uint32_t)c.HD;
+        const std::vector<float>*mw = b.get("pool_mlp.0.weight", {HD, 2 * C}, err), *mb = nullptr, *pw = nullptr,
+                          *pb = nullptr, *vw = nullptr, *vb = nullptr;
+        if (mw) mb = b.get("pool_mlp.0.bias", {HD}, err);
+        if (mb) pw = b.get("policy_head.weight", {10, HD}, err);
+        if (pw) pb = b.get("policy_head.bias", {10}, err);
+        if (pb) vw = b.get("value_head.weight", {2, HD}, err);
+        if (vw) vb = b.get("value_head.bias", {2}, err);
+        if (!vb) return nets_fail(AR_E_BACKEND, err);
+        std::vector<float> mwt((size_t)2 * C * HD);
+        for (uint32_t o = 0; o < HD; ++o)
+            for (uint32_t k = 0; k < 2 * C; ++k) mwt[(size_t)k * HD + o] = (*mw)[(size_t)o * 2 * C + k];
+        c.cb_w = net->upload(mwt, ok);
+        c.cb_b = net->upload(*mb, ok);
+        // head rows in katago_heads' order: P1 logits, P1 value, P2 logits, P2 value
+        std::vector<float> wh((size_t)12 * HD), bh(12);
+        for (int p = 0; p < 2; ++p) {
+            for (int a = 0; a < 5; ++a) {
+                memcpy(&wh[(size_t)(6 * p + a) * HD], &(*pw)[(size_t)(5 * p + a) * HD], (size_t)HD * 4);
+                bh[6 * p + a] = (*pb)[5 * p + a];
+            }
+            memcpy(&wh[(size_t)(6 * p + 5) * HD], &(*vw)[(size_t)p * HD], (size_t)HD * 4);
+            bh[6 * p + 5] = (*vb)[p];
+        }
+        c.hd_w = net->upload(wh, ok);
+        c.hd_b = net->upload(bh, ok);
+        const size_t head_floats = TL * (2 * C + HD + 12);
+        if (head_floats > small_floats) small_floats = head_floats;
+        size_t pf = TL * C * chs;
+        if (TL * (C + g_max) * c.hw > pf) pf = TL * (C + g_max) * c.hw;
+        c.p_floats = (int)pf;
+        net->smem = (pf + small_floats + 64) * 4;
+        d.H = 4;  // unused by the CNN path
     } else {
         return nets_fail(AR_E_BACKEND, "unknown architecture id in the weight blob");
     }
@@ -1340,7 +1448,7 @@ static int net_build(const arnet::Blob& b, ArNet* net) {
 // (always recomputed: a pool at the same address with the same count may hold other mazes -- an engine that
 // died and a new one whose allocation landed on the same block; the kernel is tiny)
 static int net_bind_mazes(ArNet* net, const uint8_t* d_maze_pool, int n_mazes, hipStream_t stream) {
-    if (net->dev.arch == arnet::ARCH_CNN) {  // the CNN reads the maze planes itself
+    if (arnet::is_cnn(net->dev.arch)) {  // the CNN reads the maze planes itself
         net->bound_pool = d_maze_pool;
         net->bound_mazes = n_mazes;
         return AR_OK;
@@ -1361,7 +1469,7 @@ static int net_bind_mazes(ArNet* net, const uint8_t* d_maze_pool, int n_mazes, h
 
 // mazes `d_ids[0..n)` of the bound pool changed (a slot got a new game): refresh their first-layer constants
 static int net_rebind_mazes(ArNet* net, const uint32_t* d_ids, int n, hipStream_t stream) {
-    if (n <= 0 || net->dev.arch == arnet::ARCH_CNN || !net->cmaze) return AR_OK;
+    if (n <= 0 || arnet::is_cnn(net->dev.arch) || !net->cmaze) return AR_OK;
     hipLaunchKernelGGL(arnet::k_maze_const, dim3(n), dim3(256), 0, stream, net->dev.w1t, net->dev.b1, net->dev.H,
                        net->dev.hw, net->bound_pool, n, net->cmaze, d_ids);
     if (hipGetLastError() != hipSuccess) return nets_fail(AR_E_DEVICE, "k_maze_const launch failed");
@@ -1377,19 +1485,18 @@ static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcou
     // (k_symmetric_mfma2 stages the shared encoder's operand, hw + 1 values, at the head of a row of its buffer)
     const bool sym_mfma = net->dev.arch == ARCH_SYMMETRIC && symmetric_mfma_ok(net->dev.H) && !getenv("AR_SYM_FMA") &&
                           ((net->dev.hw + 2) & ~1) <= net->dev.H + 4;
-    const int tile = mlp_mfma ? 32 * MLP_MFMA_MT : net->dev.arch == ARCH_MLP ? TILE_MLP : net->dev.arch == ARCH_CNN ? net->cnn.L
+    const int tile = mlp_mfma ? 32 * MLP_MFMA_MT : net->dev.arch == ARCH_MLP ? TILE_MLP : is_cnn(net->dev.arch) ? net->cnn.L
                                                                         : sym_mfma ? 32 : TILE_SYM;
     const uint32_t blocks = (n_max + tile - 1) / tile;
-    if (net->dev.arch == ARCH_CNN && net->cnn.MT) {
-        const void* fn = net->cnn.MT == 2 ? (const void*)k_cnn_mfma<NW, 2> : (const void*)k_cnn_mfma<NW, 1>;
-        if (net->smem > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)net->smem) != hipSuccess)
+    if (is_cnn(net->dev.arch) && net->cnn.MT) {
+        const bool kg = net->dev.arch == ARCH_CNN_KATAGO;
+        decltype(&k_cnn_mfma<NW, 1, false>) const fn = net->cnn.MT == 2 ? (kg ? k_cnn_mfma<NW, 2, true> : k_cnn_mfma<NW, 2, false>)
+                                                                        : (kg ? k_cnn_mfma<NW, 1, true> : k_cnn_mfma<NW, 1, false>);
+        if (net->smem > 48 * 1024 &&
+            hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)net->smem) != hipSuccess)
             return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the CNN kernel");
-        if (net->cnn.MT == 2)
-            hipLaunchKernelGGL((k_cnn_mfma<NW, 2>), dim3(blocks), dim3(NTHREADS), net->smem, stream, net->cnn, q, qcount, n_max,
-                               boards, board_stride, net->bound_pool, out, logits);
-        else
-            hipLaunchKernelGGL((k_cnn_mfma<NW, 1>), dim3(blocks), dim3(NTHREADS), net->smem, stream, net->cnn, q, qcount, n_max,
-                               boards, board_stride, net->bound_pool, out, logits);
+        hipLaunchKernelGGL(fn, dim3(blocks), dim3(NTHREADS), net->smem, stream, net->cnn, q, qcount, n_max, boards, board_stride,
+                           net->bound_pool, out, logits);
     } else if (net->dev.arch == ARCH_CNN) {
         if (net->smem > 48 * 1024 && hipFuncSetAttribute((const void*)k_cnn<NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                          (int)net->smem) != hipSuccess)

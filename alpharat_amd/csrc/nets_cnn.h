@@ -13,6 +13,11 @@
 // front of a ReLU on the residual stream (bn1, pool_bn) is a per-channel affine applied while the
 // padded copy is written. The 3x3 convolutions run on v_mfma_f32_32x32x2_f32 when C is a multiple of 32
 // (conv3x3_tile_mfma), otherwise on fp32 FMA (conv3x3_tile); both give the same bits.
+//
+// KataGoCNN (alpharat/nn/models/cnn/katago.py, architecture "cnn_katago") shares the trunk and runs on
+// k_cnn_mfma's KataGo instantiation: seven input planes (the player one-hots join maze and cheese), the six
+// scalars added to the stem per leaf through the scalar encoder, and heads on the mean and max of the trunk's
+// output over the board (katago_heads) instead of the features at the player cells.
 #pragma once
 // (included from nets.h after the shared helpers)
 
@@ -47,6 +52,10 @@ struct CnnDev {
     // k_cnn_mfma (trunk state in registers): MT row tiles per wavefront (0: k_cnn), L leaves per workgroup,
     // floats of the image / scratch region P
     int MT, L, p_floats;
+    // KataGoCNN: stem_w is [7][9][C] and stem_b = a * scalar_encoder.bias + c (stem_bn's affine a, c folded into both),
+    // sc_w the folded scalar encoder [6][C] (a * W, transposed); cb_w / cb_b hold pool_mlp.0 [2C][HD], [HD] and
+    // hd_w / hd_b the head rows in katago_heads' order [12][HD]: P1 logits 0-4, value 1, P2 logits 6-10, value 2
+    const float* sc_w;
 };
 
 // zero-bordered patch conv: out[l][co][y][x] = bias[co] + sum_ci sum_tap w[ci][tap][co] * in[l][ci][y+dy][x+dx]
@@ -572,7 +581,65 @@ __device__ inline void conv3x3_rows_mfma(const float* __restrict__ wt, const flo
     }
 }
 
-template <int NW, int MT>
+// KataGoCNN's heads (katago.py:156-175) on the trunk's output `A` [L][C][hw] in LDS: mean and max per channel over the
+// board (cells in order), pool_mlp.0 + ReLU, 12 rows as cnn_heads lays them out (P1 logits, value, P2 logits, value).
+// LDS: L * (2C + HD + 12) floats of `small`. All threads of the block call this.
+template <int NW>
+__device__ inline void katago_heads(const CnnDev& net, int L, int cnt, const float* A, int a_leaf, float* small, int tid,
+                                    uint32_t base, ar::EvalOut* out, float* logits) {
+    const int C = net.C, hw = net.hw, HD = net.HD;
+    float* pool = small;               // [L][2C]: mean, max
+    float* hid = pool + L * 2 * C;     // [L][HD]
+    float* hl = hid + L * HD;          // [L][12]
+    for (int i = tid; i < L * C; i += NTHREADS) {
+        const int l = i / C, c = i % C;
+        const float* a = &A[(size_t)l * a_leaf + (size_t)c * hw];
+        float s = 0.0f, mx = a[0];
+        for (int k = 0; k < hw; ++k) {
+            s += a[k];
+            mx = fmaxf(mx, a[k]);
+        }
+        pool[l * 2 * C + c] = s / (float)hw;
+        pool[l * 2 * C + C + c] = mx;
+    }
+    __syncthreads();
+    for (int i = tid; i < L * HD; i += NTHREADS) {
+        const int l = i / HD, o = i % HD;
+        const float* pl = pool + (size_t)l * 2 * C;
+        float acc = net.cb_b[o];
+#pragma unroll 16
+        for (int k = 0; k < 2 * C; ++k) acc = fmaf(net.cb_w[(size_t)k * HD + o], pl[k], acc);
+        hid[i] = fmaxf(acc, 0.0f);
+    }
+    __syncthreads();
+    for (int i = tid; i < L * 12; i += NTHREADS) {
+        const int l = i / 12, o = i % 12;
+        const float* hi = hid + (size_t)l * HD;
+        const float* wr = net.hd_w + (size_t)o * HD;
+        float acc = net.hd_b[o];
+#pragma unroll 16
+        for (int k = 0; k < HD; ++k) acc = fmaf(wr[k], hi[k], acc);
+        hl[i] = acc;
+    }
+    __syncthreads();
+    if (tid < cnt) {
+        const float* hh = hl + tid * 12;
+        ar::EvalOut o;
+        softmax5(hh, o.p1);
+        softmax5(hh + 6, o.p2);
+        o.v1 = softplusf(hh[5]);
+        o.v2 = softplusf(hh[11]);
+        out[base + tid] = o;
+        if (logits)
+            for (int k = 0; k < 5; ++k) {
+                logits[(size_t)(base + tid) * 10 + k] = hh[k];
+                logits[(size_t)(base + tid) * 10 + 5 + k] = hh[6 + k];
+            }
+    }
+}
+
+// KATAGO: KataGoCNN (seven input planes, a per-leaf stem bias, katago_heads); otherwise PyRatCNN
+template <int NW, int MT, bool KATAGO>
 __global__ void __launch_bounds__(NTHREADS, MT == 1 ? 3 : 2) k_cnn_mfma(CnnDev net, const ar::LeafReq<NW>* q, const uint32_t* qcount,
                                                        uint32_t n_fixed, const char* boards, size_t board_stride,
                                                        const uint8_t* maze_pool, ar::EvalOut* out, float* logits) {
@@ -606,8 +673,10 @@ __global__ void __launch_bounds__(NTHREADS, MT == 1 ? 3 : 2) k_cnn_mfma(CnnDev n
         leaf_features<NW>(rq.st, b, hw, feat[tid]);
     }
     __syncthreads();
-    for (int i = tid; i < L * 5 * hw; i += NTHREADS) {
-        const int l = i / (5 * hw), rem = i % (5 * hw), c = rem / hw, cell = rem % hw;
+    // input planes: maze up/right/down/left, cheese (+ KataGo: p1, p2 one-hot)
+    constexpr int NP = KATAGO ? 7 : 5;
+    for (int i = tid; i < L * NP * hw; i += NTHREADS) {
+        const int l = i / (NP * hw), rem = i % (NP * hw), c = rem / hw, cell = rem % hw;
         const int ll = l < cnt ? l : 0;
         const ar::LeafReq<NW>& rq = q[base + ll];
         const ar::Board& b = *(const ar::Board*)(boards + (size_t)rq.slot * board_stride);
@@ -615,10 +684,22 @@ __global__ void __launch_bounds__(NTHREADS, MT == 1 ? 3 : 2) k_cnn_mfma(CnnDev n
         if (c < 4) {
             const uint8_t cst = maze_pool[b.maze_off + (uint32_t)cell * 4u + (uint32_t)c];
             v = cst ? (float)cst / 10.0f : -1.0f;
-        } else {
+        } else if (!KATAGO || c == 4) {
             v = ar::st_has_cheese(rq.st, cell) ? 1.0f : 0.0f;
+        } else {
+            v = cell == (c == 5 ? feat[l].p1 : feat[l].p2) ? 1.0f : 0.0f;
         }
         P[(size_t)l * p_leaf + (size_t)c * chs + (size_t)(cell / w + 1) * WP + (cell % w + 1)] = v;
+    }
+    if (KATAGO) {
+        // per-leaf stem bias [L][C] in `small`: a * bs + c + sum_k (a * Ws)[k] * scalars[k]
+        for (int i = tid; i < L * C; i += NTHREADS) {
+            const int l = i / C, co = i % C;
+            float acc = net.stem_b[co];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) acc = fmaf(net.sc_w[k * C + co], feat[l].sc[k], acc);
+            small[i] = acc;
+        }
     }
     // this lane's operand rows (window origin in P) and how many of the wavefront's tiles hold rows at all
     int arow[MT], urow[MT];
@@ -643,16 +724,29 @@ __global__ void __launch_bounds__(NTHREADS, MT == 1 ? 3 : 2) k_cnn_mfma(CnnDev n
     // result rows of this lane: tile t, register v -> row mo
     auto row_of = [&](int t, int v) -> int { return (wave + 4 * t) * 32 + (v & 3) + 8 * (v >> 2) + 4 * h2; };
     f32x16 xs[MT][2], acc[MT][2];
-    // stem: conv(5 -> C) + folded stem_bn + ReLU
-    conv(net.stem_w, net.stem_b, 5, acc);
+    if (KATAGO) {
+        // stem: conv(7 -> C) with stem_bn folded, + the leaf's bias, ReLU
+        conv(net.stem_w, nullptr, 7, acc);
 #pragma unroll
-    for (int t = 0; t < MT; ++t)
+        for (int t = 0; t < MT; ++t)
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            xs[t][0][v] = fmaxf(acc[t][0][v], 0.0f);
-            xs[t][1][v] = fmaxf(acc[t][1][v], 0.0f);
-        }
-    __syncthreads();  // every wavefront is done reading P
+            for (int v = 0; v < 16; ++v) {
+                const int mo = row_of(t, v), l = row_l[mo < M ? mo : 0];
+                xs[t][0][v] = fmaxf(acc[t][0][v] + small[l * C + r], 0.0f);
+                xs[t][1][v] = fmaxf(acc[t][1][v] + small[l * C + (two ? r + 32 : r)], 0.0f);
+            }
+    } else {
+        // stem: conv(5 -> C) + folded stem_bn + ReLU
+        conv(net.stem_w, net.stem_b, 5, acc);
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                xs[t][0][v] = fmaxf(acc[t][0][v], 0.0f);
+                xs[t][1][v] = fmaxf(acc[t][1][v], 0.0f);
+            }
+    }
+    __syncthreads();  // every wavefront is done reading P (and the stem bias in `small`)
     for (int bi = 0; bi < net.n_blocks; ++bi) {
         const CnnBlockDev& blk = net.blk[bi];
         float* pout = small;  // [L][C] pooled-branch output (gpool blocks)
@@ -794,7 +888,8 @@ __global__ void __launch_bounds__(NTHREADS, MT == 1 ? 3 : 2) k_cnn_mfma(CnnDev n
             }
         }
     __syncthreads();
-    cnn_heads<NW>(net, L, cnt, A, a_leaf, small, feat, tid, base, out, logits);
+    if (KATAGO) katago_heads<NW>(net, L, cnt, A, a_leaf, small, tid, base, out, logits);
+    else cnn_heads<NW>(net, L, cnt, A, a_leaf, small, feat, tid, base, out, logits);
 }
 
 // ---- host: blob -> device weights ---------------------------------------------------------------
@@ -817,7 +912,7 @@ inline bool bn_affine(const Blob& b, const std::string& p, int n, std::vector<do
                       std::string& err) {
     const std::vector<float>*g = b.get(p + ".weight"), *be = b.get(p + ".bias"), *m = b.get(p + ".running_mean"),
                       *v = b.get(p + ".running_var");
-    if (!g || !be || !m || !v || (int)g->size() != n) {
+    if (!g || !be || !m || !v || (int)g->size() != n || (int)be->size() != n || (int)m->size() != n || (int)v->size() != n) {
         err = "weight blob lacks " + p;
         return false;
     }

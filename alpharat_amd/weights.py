@@ -5,9 +5,13 @@ Replaces the reference's ONNX export step for the sampling path
 the HIP evaluators read this blob instead of an ONNX graph.
 
 Blob layout ("ARNET001", little endian):
-    char[8] magic, u32 arch (0 mlp, 1 symmetric, 2 cnn), u32 width, u32 height, u32 n_tensors,
+    char[8] magic, u32 arch (0 mlp, 1 symmetric, 2 cnn, 3 cnn_katago), u32 width, u32 height, u32 n_tensors,
     then per tensor: u32 name_len, name, u32 ndim, u32 dims[ndim], f32 data (C order).
 Tensor names are the torch ``state_dict`` keys; integer buffers (num_batches_tracked) are dropped.
+
+A ``local_value`` checkpoint (LocalValueMLP, ``alpharat/nn/models/local_value.py``) becomes an ``mlp`` blob: at
+inference it is PyRatMLP (same trunk, policy and value heads; ``predict()`` takes its values from
+``value_head``), so its auxiliary ``ownership_head.*`` and the ``outcome_values`` buffer are left out.
 """
 from __future__ import annotations
 
@@ -17,8 +21,12 @@ from typing import Mapping
 
 import numpy as np
 
-ARCH_IDS = {"mlp": 0, "symmetric": 1, "cnn": 2}
+ARCH_IDS = {"mlp": 0, "symmetric": 1, "cnn": 2, "cnn_katago": 3}
 MAGIC = b"ARNET001"
+# tensors a checkpoint of these architectures must hold: a state_dict of another model under their name is refused here
+# rather than written into a blob the loader would reject
+_REQUIRED = {"cnn_katago": ("stem.weight", "scalar_encoder.weight", "pool_mlp.0.weight", "policy_head.weight"),
+             "local_value": ("trunk.0.weight", "policy_p1_head.weight", "value_head.weight", "ownership_head.0.weight")}
 
 
 def write_blob(path: str | Path, arch: str, width: int, height: int, tensors: Mapping[str, np.ndarray]) -> Path:
@@ -87,4 +95,10 @@ def checkpoint_to_blob(checkpoint_path: str | Path, blob_path: str | Path | None
     if arch is None:
         raise ValueError(f"Checkpoint {pt} missing config.model.architecture.")
     sd = {k.removeprefix("_orig_mod."): v.detach().cpu().numpy() for k, v in ckpt["model_state_dict"].items()}
+    missing = [k for k in _REQUIRED.get(arch, ()) if k not in sd]
+    if missing:
+        raise ValueError(f"unsupported architecture {arch!r} layout in {pt}: the state_dict lacks {', '.join(missing)}")
+    if arch == "local_value":  # PyRatMLP at inference time
+        arch = "mlp"
+        sd = {k: v for k, v in sd.items() if not k.startswith("ownership_head.") and k != "outcome_values"}
     return write_blob(blob, arch, int(width), int(height), sd)
