@@ -1234,6 +1234,11 @@ static int net_build(const arnet::Blob& b, ArNet* net) {
     d.arch = (int)b.arch;
     d.width = (int)b.width;
     d.height = (int)b.height;
+    // every evaluator holds a board in at most four 64-bit cheese words
+    const uint64_t cells = (uint64_t)b.width * b.height;
+    if (cells < 1 || cells > 256)
+        return nets_fail(AR_E_BACKEND, "weight blob for a " + std::to_string(b.width) + "x" + std::to_string(b.height) +
+                                           " board: boards of 1 to 256 cells are supported");
     d.hw = d.width * d.height;
     bool ok = true;
     std::vector<float> wt, bias;
@@ -1378,7 +1383,6 @@ static int net_build(const arnet::Blob& b, ArNet* net) {
         if (c.C != 32 && c.C != 64)
             return nets_fail(AR_E_BACKEND, "KataGoCNN with " + std::to_string(c.C) +
                                                " trunk channels is not supported (supported widths: 32, 64)");
-        if (c.hw > 256) return nets_fail(AR_E_BACKEND, "KataGoCNN: boards up to 256 cells are supported");
         const uint32_t C = (uint32_t)c.C;
         cnn_mfma_tile(c);
         const size_t TL = (size_t)c.L, chs = (size_t)(c.height + 2) * (c.width + 2);

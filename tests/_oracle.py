@@ -177,6 +177,10 @@ class Game:
         assert lib().or_game_random_cheese(self.g, count, int(symmetric), seed)
         return self
 
+    def add_cheese(self, x, y):
+        lib().or_game_add_cheese(self.g, x, y)
+        return self
+
     def random_maze(self, wall_density=0.7, mud_density=0.1, symmetric=True, seed=0):
         """Own generator (the engine's is absent): oracle/pyrat_engine.hpp make_maze. Call before random_cheese."""
         lib().or_game_random_maze(self.g, wall_density, mud_density, int(symmetric), seed)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import _oracle as O
+from _random_nets import random_mlp
 from test_gpu_parity import _assert_result, _check_game, _pyrat
 from test_gpu_pipeline_parity import GOLD, HipEvaluator
 
@@ -163,24 +164,10 @@ def test_wide_gather_refused_beyond_its_pick_bound(monkeypatch):
 
 
 def _random_mlp(tmp_path, w, h, hidden, seed):
-    """seeded random PyRatMLP weights (as test_gpu_nets.py builds them) for a w x h board"""
+    """seeded random PyRatMLP weights (tests/_random_nets.py) for a w x h board"""
     from alpharat_amd.weights import write_blob
 
-    rng = np.random.default_rng(seed)
-    d = w * h * 7 + 6
-    t = {}
-    for name, (o, i) in {"trunk.0": (hidden, d), "trunk.4": (hidden, hidden)}.items():
-        t[f"{name}.weight"] = (rng.standard_normal((o, i)) * np.sqrt(2.0 / i)).astype(np.float32)
-        t[f"{name}.bias"] = (rng.standard_normal(o) * 0.1).astype(np.float32)
-    for bn in ("trunk.1", "trunk.5"):
-        t[f"{bn}.weight"] = (1 + 0.1 * rng.standard_normal(hidden)).astype(np.float32)
-        t[f"{bn}.bias"] = (0.1 * rng.standard_normal(hidden)).astype(np.float32)
-        t[f"{bn}.running_mean"] = (0.1 * rng.standard_normal(hidden)).astype(np.float32)
-        t[f"{bn}.running_var"] = (1 + 0.1 * rng.random(hidden)).astype(np.float32)
-    for name, o in (("policy_p1_head", 5), ("policy_p2_head", 5), ("value_head", 2)):
-        t[f"{name}.weight"] = (rng.standard_normal((o, hidden)) * 0.2).astype(np.float32)
-        t[f"{name}.bias"] = (0.1 * rng.standard_normal(o)).astype(np.float32)
-    return write_blob(tmp_path / f"mlp_{w}x{h}_h{hidden}.arnet", "mlp", w, h, t)
+    return write_blob(tmp_path / f"mlp_{w}x{h}_h{hidden}.arnet", "mlp", w, h, random_mlp(w, h, hidden, seed))
 
 
 @pytest.mark.parametrize("w,h,cheese,turns", [(9, 10, 12, 40), (15, 11, 21, 40)])

@@ -202,21 +202,12 @@ def test_device_mlp_other_hidden_widths_match_the_oracle_net(hidden, tmp_path):
     from alpharat_amd.nets import Net, encode
     from alpharat_amd.weights import write_blob
 
-    rng = np.random.default_rng(hidden)
+    from _random_nets import random_mlp
+
     w = h = 7
-    d = w * h * 7 + 6
-    t = {}
-    for name, (o, i) in {"trunk.0": (hidden, d), "trunk.4": (hidden, hidden)}.items():
-        t[f"{name}.weight"] = (rng.standard_normal((o, i)) * np.sqrt(2.0 / i)).astype(np.float32)
-        t[f"{name}.bias"] = (rng.standard_normal(o) * 0.1).astype(np.float32)
-    for bn in ("trunk.1", "trunk.5"):
-        t[f"{bn}.weight"] = (1 + 0.1 * rng.standard_normal(hidden)).astype(np.float32)
-        t[f"{bn}.bias"] = (0.1 * rng.standard_normal(hidden)).astype(np.float32)
-        t[f"{bn}.running_mean"] = (0.1 * rng.standard_normal(hidden)).astype(np.float32)
-        t[f"{bn}.running_var"] = (1 + 0.1 * rng.random(hidden)).astype(np.float32)
-    for name, o in (("policy_p1_head", 5), ("policy_p2_head", 5), ("value_head", 2)):
-        t[f"{name}.weight"] = (rng.standard_normal((o, hidden)) * 0.2).astype(np.float32)
-        t[f"{name}.bias"] = (0.1 * rng.standard_normal(o)).astype(np.float32)
+    # the positions draw from the generator the weights were drawn from, after them (tests/_random_nets.py)
+    rng = np.random.default_rng(hidden)
+    t = random_mlp(w, h, hidden, seed=rng)
     blob = write_blob(tmp_path / f"mlp_h{hidden}.arnet", "mlp", w, h, t)
     games = []
     for i in range(70):
