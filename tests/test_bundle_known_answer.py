@@ -4,12 +4,11 @@ data) and the assertions of tests/data/test_rust_bundle_parity.py:66-230 on what
 plus the container contract of recording.rs / npz_writer.rs (26 arrays, dtypes, v1.0 headers padded to
 256 bytes, deflate)."""
 import ctypes as C
-import struct
-import zipfile
 
 import numpy as np
 import pytest
 
+from _bundles import check_container, view_of
 from alpharat_amd import _lib
 
 UNCOLLECTED, P1WIN, SIMULTANEOUS = 2, 0, 1
@@ -49,30 +48,13 @@ def _game1():
 
 
 def _view(g, keep):
-    v = _lib.ArGameRecordView()
-    v.width, v.height, v.max_turns, v.game_index = g["width"], g["height"], g["max_turns"], g["game_index"]
-    p = g["pos"]
-    v.n_positions = len(p["turn"])
-    v.final_p1_score, v.final_p2_score = g["final"]
-    v.result, v.cheese_available = g["result"], g["cheese_available"]
-    v.total_simulations, v.total_nn_evals, v.total_terminals, v.total_collisions = g["sims"], 0, 0, 0
-
-    def ptr(arr, dt, ct):
-        a = np.ascontiguousarray(np.asarray(arr), dtype=dt)
-        keep.append(a)
-        return a.ctypes.data_as(C.POINTER(ct))
-
-    v.maze = ptr(g["maze"], np.int8, C.c_int8)
-    v.initial_cheese = ptr(g["initial_cheese"], np.uint8, C.c_uint8)
-    v.cheese_outcomes = ptr(g["cheese_outcomes"], np.uint8, C.c_uint8)
-    for k in ("p1_pos", "p2_pos", "p1_mud", "p2_mud", "action_p1", "action_p2"):
-        setattr(v, k, ptr(p[k], np.uint8, C.c_uint8))
-    v.cheese_mask = ptr(np.stack(p["cheese_mask"]), np.uint8, C.c_uint8)
-    v.turn = ptr(p["turn"], np.uint16, C.c_uint16)
-    for k in ("p1_score", "p2_score", "value_p1", "value_p2", "visit_counts_p1", "visit_counts_p2", "prior_p1", "prior_p2",
-              "policy_p1", "policy_p2"):
-        setattr(v, k, ptr(p[k], np.float32, C.c_float))
-    return v
+    """The nested layout above as the flat game dict tests/_bundles.py works on."""
+    flat = dict(width=g["width"], height=g["height"], max_turns=g["max_turns"], game_index=g["game_index"],
+                maze=g["maze"], initial_cheese=g["initial_cheese"], cheese_outcomes=g["cheese_outcomes"],
+                final_p1_score=g["final"][0], final_p2_score=g["final"][1], result=g["result"],
+                cheese_available=g["cheese_available"], total_simulations=g["sims"], **g["pos"])
+    flat["cheese_mask"] = np.stack(flat["cheese_mask"])
+    return view_of(flat, keep)
 
 
 @pytest.fixture(scope="module")
@@ -87,28 +69,7 @@ def bundle(tmp_path_factory):
 
 
 def test_container_contract(bundle):
-    with zipfile.ZipFile(bundle) as z:
-        infos = z.infolist()
-        assert len(infos) == 26 and all(i.filename.endswith(".npy") for i in infos)
-        assert all(i.compress_type == zipfile.ZIP_DEFLATED for i in infos)
-        for i in infos:
-            raw = z.read(i)
-            assert raw[:6] == b"\x93NUMPY" and raw[6:8] == b"\x01\x00"            # npy format 1.0
-            hlen = struct.unpack("<H", raw[8:10])[0]
-            assert (10 + hlen) % 256 == 0 and raw[10 + hlen - 1:10 + hlen] == b"\n"  # header padded to 256 bytes
-            assert b"'fortran_order':False" in raw[10:10 + hlen].replace(b" ", b"")
-    z = np.load(bundle)
-    want_dtypes = dict(game_lengths=np.int32, maze=np.int8, initial_cheese=np.bool_, cheese_outcomes=np.int8,
-                       max_turns=np.int16, result=np.int8, final_p1_score=np.float32, final_p2_score=np.float32,
-                       p1_pos=np.int8, p2_pos=np.int8, p1_score=np.float32,
-                       p2_score=np.float32, p1_mud=np.int8, p2_mud=np.int8, cheese_mask=np.bool_, turn=np.int16,
-                       value_p1=np.float32, value_p2=np.float32, visit_counts_p1=np.float32, visit_counts_p2=np.float32,
-                       prior_p1=np.float32, prior_p2=np.float32, policy_p1=np.float32, policy_p2=np.float32,
-                       action_p1=np.int8, action_p2=np.int8)
-    got = {k: z[k].dtype for k in z.files}
-    assert sorted(got) == sorted(want_dtypes)  # the 26 names of recording.rs, no more, no fewer
-    for k, dt in got.items():
-        assert dt == np.dtype(want_dtypes[k]), (k, dt)
+    check_container(bundle)
 
 
 def test_known_answers(bundle):

@@ -103,6 +103,7 @@ def _check_game(g, want):
     np.testing.assert_array_equal(g["p1_pos"], want["ints"][:, 0:2])
     np.testing.assert_array_equal(g["p2_pos"], want["ints"][:, 2:4])
     np.testing.assert_array_equal(g["p1_mud"], want["ints"][:, 4])
+    np.testing.assert_array_equal(g["p2_mud"], want["ints"][:, 5])
     np.testing.assert_array_equal(g["turn"], want["ints"][:, 6])
     np.testing.assert_array_equal(g["action_p1"], want["ints"][:, 7])
     np.testing.assert_array_equal(g["action_p2"], want["ints"][:, 8])
@@ -220,6 +221,10 @@ def test_bundles_on_disk_roundtrip(tmp_path):
         assert z["maze"].dtype == np.int8 and z["cheese_mask"].dtype == np.bool_ and z["turn"].dtype == np.int16
         assert z["policy_p1"].shape == (int(z["game_lengths"].sum()), 5)
     assert n_games == 10 and n_pos == stats.total_positions
+    # the values: what is on disk is what the sink received (tests/test_bundle_contents.py goes on from here)
+    from _bundles import assert_same_games, from_sink, read_games
+
+    assert_same_games([g for f in files for g in read_games(f)], [from_sink(g) for g in games.values()], "disk against sink")
 
 
 def test_invalid_arguments_raise():
