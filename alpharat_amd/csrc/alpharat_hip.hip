@@ -1395,7 +1395,8 @@ SearchCfg to_cfg(const ArSearchConfig& c, uint32_t sims, uint32_t batch) {
 
 int check_cfg(const SearchCfg& c) {
     if (c.n_sims == 0) return fail(AR_E_INVALID, "simulations must be > 0");
-    if (c.batch_size == 0 || c.batch_size > 4096) return fail(AR_E_INVALID, "batch_size must be in 1..4096");
+    static_assert(MAX_BATCH_SIZE == 4096, "the message below states the limit");
+    if (c.batch_size == 0 || c.batch_size > MAX_BATCH_SIZE) return fail(AR_E_INVALID, "batch_size must be in 1..4096");
     if (c.coll_max > 65536) return fail(AR_E_INVALID, "collision_limit_max must be <= 65536");
     if (c.coll_min > c.coll_max) return fail(AR_E_INVALID, "collision_limit_min must be <= collision_limit_max");
     if (c.noise_epsilon > 0.0f && !(c.noise_concentration / 5.0f > 1.0f))
@@ -1759,6 +1760,12 @@ struct Engine {
         {
             pool.page_nodes = arena_nodes ? cap0 : (uint32_t)POOL_PAGE_NODES;  // (test knob: small pages, fresh games on a single one)
             pool.fresh_pages = arena_nodes ? 1u : (initial_arena_nodes(cfg) + POOL_PAGE_NODES - 1) / POOL_PAGE_NODES;
+            // (initial_arena_nodes carries 2 * batch_size + 64 nodes of slack. A search adds at most one node per simulation
+            // and a gather stalls only when hi + min(remaining, batch_size) > cap, so 1 + n_sims nodes are what a fresh game
+            // needs: where the slack alone goes past the longest run -- batch sizes in the thousands -- the run is taken whole)
+            if (pool.fresh_pages > POOL_WORD_PAGES &&
+                (uint64_t)1 + cfg.n_sims + cfg.batch_size <= (uint64_t)POOL_WORD_PAGES * POOL_PAGE_NODES)
+                pool.fresh_pages = POOL_WORD_PAGES;
             if (pool.fresh_pages > POOL_WORD_PAGES) return fail(AR_E_INVALID, "simulations per move beyond what one run of tree pages holds");
             cap0 = pool.fresh_pages * pool.page_nodes;
             pool.page_bytes = arena_bytes(pool.page_nodes);

@@ -66,12 +66,12 @@ __device__ inline void backup16(bool active, Slot<NW>& S, const Mem<NW>& m, cons
             // depth-first gathers' entries is in order already; the work-queue gather writes at most 16, in arrival order)
             ProcEntry pe;
             pe.node = NIL;
-            pe.kind = 0xFFFF0000u;
+            pe.kind = proc_none();
             if (mine) pe = m.proc[e];
             uint32_t rank = 0;
             for (uint32_t j = 0; j < 16; ++j) {
-                const uint32_t kj = grp_pick(pe.kind, j) >> 16;
-                rank += (kj < (pe.kind >> 16) || (kj == (pe.kind >> 16) && j < w)) ? 1u : 0u;
+                const uint32_t kj = proc_key(grp_pick(pe.kind, j));
+                rank += (kj < proc_key(pe.kind) || (kj == proc_key(pe.kind) && j < w)) ? 1u : 0u;
             }
             uint32_t src = 0;
             for (uint32_t j = 0; j < 16; ++j) src = grp_pick(rank, j) == w ? j : src;

@@ -397,12 +397,14 @@ __device__ inline void gather8_round(Oct<NW>& o, OctShared<NW>& sh, const Outcom
             if (emit_kind != PROC_NONE) {
                 if (o.n_proc >= cfg.batch_size) {
                     o.error = 1;
+                } else if (!proc_fits(o.b_nn, o.n_proc)) {  // (excluded by check_cfg: batch_size <= MAX_BATCH_SIZE)
+                    o.error = 10;
                 } else {
                     const uint32_t i = o.n_proc++;
                     if (ol == 0) {
                         ProcEntry pe;
                         pe.node = emit_node;
-                        pe.kind = (emit_kind == PROC_EVAL ? emit_kind | (o.b_nn << 8) : emit_kind) | (i << 16);
+                        pe.kind = proc_pack(emit_kind, o.b_nn, i);
                         m.proc()[i] = pe;
                     }
                     if (emit_kind == PROC_EVAL) {

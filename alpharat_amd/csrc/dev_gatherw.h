@@ -539,11 +539,9 @@ AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of 
         // the batch entry (search.rs:598-633, 681-701) and the collision record, in arrival order; the entry carries its
         // place in the depth-first order (pick number, visit slot) and the index of its evaluation request
         if (ln.fin_kind != PROC_NONE) {
-            uint32_t word = ln.fin_kind;
             if (ln.fin_kind == PROC_EVAL) {
                 ln.arr = GW_ATOMIC_ADD(&G.b_nn, 1u);
                 m.leaves(G)[ln.arr] = ln.pos;
-                word |= ln.arr << 8;
             } else {
                 GW_ATOMIC_ADD(&G.b_term, 1u);
             }
@@ -553,7 +551,7 @@ AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of 
             } else {
                 ProcEntry pe;
                 pe.node = ln.fin_node;
-                pe.kind = word | ((((uint32_t)G.pick << 4) | ln.t) << 16);
+                pe.kind = proc_pack(ln.fin_kind, ln.arr, ((uint32_t)G.pick << 4) | ln.t);
                 m.proc(G)[i] = pe;
             }
         }
@@ -667,6 +665,11 @@ AR_HD void gw_begin(GwGame<NW>& G, const Slot<NW>& S, uint32_t slot, const Searc
     G.stalled = 0;
     G.began = 0;
     G.left = 0;
+    if (cfg.batch_size > GW_SLOTS) {  // (excluded by the engine's choice of gather: a pick has GW_SLOTS visit slots)
+        G.error = 11;  // the batch ends empty and with the error; nothing of the tree is touched
+        G.began = 1;
+        return;
+    }
     if (G.hi + G.batch > G.cap && !S.gather_pending) {  // (a parked gather passed this check when it began)
         G.stalled = 1;
         return;

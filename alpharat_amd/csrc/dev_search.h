@@ -75,16 +75,33 @@ struct SearchCfg {
 enum { SLOT_EMPTY = 0, SLOT_ACTIVE = 1, SLOT_DONE = 2, SLOT_STALL = 3, SLOT_FAILED = 4, SLOT_ADVANCE = 5 };
 enum { PROC_TERMINAL = 0, PROC_EVAL = 1 };
 
+// The largest batch size every entry point accepts (check_cfg). A batch evaluates at most batch_size leaves, so an
+// entry's evaluation index runs to MAX_BATCH_SIZE - 1, and so does the entry number the depth-first gathers use as key.
+enum { MAX_BATCH_SIZE = 4096 };
+
 struct ProcEntry {
     uint32_t node;
-    // PROC_TERMINAL or PROC_EVAL | (index of the leaf's evaluation in this batch's requests) << 8 | order key << 16: the
-    // backup takes a batch's entries by increasing key (the depth-first gathers write them in that order: key = index;
-    // the work-queue gather writes them as their leaves are reached: key = pick number, visit slot)
+    // kind (PROC_TERMINAL / PROC_EVAL, bits 0..3) | index of the leaf's evaluation in this batch's requests (bits 4..15,
+    // PROC_EVAL only) | order key (bits 16..31): the backup takes a batch's entries by increasing key (the depth-first
+    // gathers write them in that order: key = entry number; the work-queue gather writes them as their leaves are
+    // reached: key = pick number << 4 | visit slot). proc_pack and the three readers below are the only code that knows
+    // the layout.
     uint32_t kind;
 };
-AR_HD uint32_t proc_kind(uint32_t k) { return k & 0xffu; }
-AR_HD uint32_t proc_eval_index(uint32_t k) { return (k >> 8) & 0xffu; }
-AR_HD uint32_t proc_key(uint32_t k) { return k >> 16; }
+enum { PROC_KIND_BITS = 4, PROC_INDEX_BITS = 12, PROC_KEY_BITS = 16 };
+static_assert(PROC_KIND_BITS + PROC_INDEX_BITS + PROC_KEY_BITS == 32, "an entry word is kind | evaluation index | key");
+static_assert(MAX_BATCH_SIZE <= (1 << PROC_INDEX_BITS), "every evaluation index of the largest batch fits its field");
+static_assert(MAX_BATCH_SIZE <= (1 << PROC_KEY_BITS), "every entry number of the largest batch fits the key");
+AR_HD uint32_t proc_kind(uint32_t k) { return k & ((1u << PROC_KIND_BITS) - 1u); }
+AR_HD uint32_t proc_eval_index(uint32_t k) { return (k >> PROC_KIND_BITS) & ((1u << PROC_INDEX_BITS) - 1u); }
+AR_HD uint32_t proc_key(uint32_t k) { return k >> (PROC_KIND_BITS + PROC_INDEX_BITS); }
+AR_HD bool proc_fits(uint32_t eval_index, uint32_t key) { return (eval_index >> PROC_INDEX_BITS) == 0 && (key >> PROC_KEY_BITS) == 0; }
+// (eval_index is ignored for a PROC_TERMINAL entry; both numbers must pass proc_fits)
+AR_HD uint32_t proc_pack(uint32_t kind, uint32_t eval_index, uint32_t key) {
+    return kind | (kind == PROC_EVAL ? eval_index << PROC_KIND_BITS : 0u) | (key << (PROC_KIND_BITS + PROC_INDEX_BITS));
+}
+// an entry word that sorts behind every real entry (a lane of the sixteen-lane backup that has no entry)
+AR_HD uint32_t proc_none() { return proc_pack(PROC_TERMINAL, 0, (1u << PROC_KEY_BITS) - 1u); }
 struct CollEntry {
     uint32_t node;
     uint32_t mv;
@@ -497,10 +514,14 @@ AR_HD void emit_proc(Slot<NW>& s, const Mem<NW>& m, const SearchCfg& cfg, int ev
         s.error = 1;
         return;
     }
+    if (!proc_fits(s.b_nn, s.n_proc)) {  // (excluded by check_cfg: batch_size <= MAX_BATCH_SIZE)
+        s.error = 10;
+        return;
+    }
     const uint32_t i = s.n_proc++;
     ProcEntry pe;
     pe.node = node;
-    pe.kind = (kind == PROC_EVAL ? kind | (s.b_nn << 8) : kind) | (i << 16);
+    pe.kind = proc_pack(kind, s.b_nn, i);
     m.proc[i] = pe;
     if (kind == PROC_EVAL) {
         const uint32_t j = s.b_nn++;

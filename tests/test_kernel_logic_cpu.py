@@ -130,6 +130,7 @@ def test_constant_value_backend_search():
 # batch_size + budget <= GW_MAX_PICKS (dev_gatherw.h), and beyond that a gather that would wrap the key must stop with an
 # error. The harness forces the work-queue modes at every budget, so there a case is either bit-exact or an error.
 GW_MAX_PICKS = 4095
+GW_SLOTS = 16               # visit slots per pick of the work-queue gather: the largest batch size it serves
 UNIFORM_MODES = (0, 2, 3)   # SmartUniform inline, the fused kernel body, the gather cut off and resumed
 HASHED_MODES = (6, 7, 8, 9)  # hashed_eval: work-queue gather (whole / random cuts / one record, pass limit), lane gather
 WIDE_MODES = (6, 7, 9)
@@ -142,20 +143,26 @@ def _coll(lo, hi=None, start=800, end=50000, power=1.0, **kw):
 
 
 def _check_searches(cfg, sims, batch, positions=None, seed=42):
-    """Every eval mode against the oracle for one search from each of the games() positions (or the named ones)."""
+    """Every eval mode against the oracle for one search from each of the games() positions (or the named ones).
+    Returns the largest number of leaves one batch of the hashed-evaluator searches sent to its evaluator."""
     limit = max(cfg.collision_limit_min, cfg.collision_limit_max)
+    largest = 0
     for name, g, mt in games():
         if positions is not None and name not in positions:
             continue
         want = O.search_once(g, cfg, sims, batch, seed=seed)
         for mode in UNIFORM_MODES:
             _same_search(want, H.run(g, mt, cfg, sims, batch, seed, single=True, eval_mode=mode), (name, mode))
-        want = O.search_once(g, cfg, sims, batch, seed=seed, backend=4, net=O.CallbackBackend(H.hashed_eval(g.w)))
+        backend = O.CallbackBackend(H.hashed_eval(g.w))
+        want = O.search_once(g, cfg, sims, batch, seed=seed, backend=4, net=backend)
+        assert max(backend.sizes, default=0) <= batch, name
+        largest = max(largest, max(backend.sizes, default=0))
         for mode in HASHED_MODES:
             got = H.run(g, mt, cfg, sims, batch, seed, single=True, eval_mode=mode)
-            if mode in WIDE_MODES and batch + limit > GW_MAX_PICKS and got["error"] != 0:
+            if mode in WIDE_MODES and (batch > GW_SLOTS or batch + limit > GW_MAX_PICKS) and got["error"] != 0:
                 continue  # (the engine never takes the work-queue gather here; it must not return a wrong tree)
             _same_search(want, got, (name, mode))
+    return largest
 
 
 @pytest.mark.parametrize("limit", [2, 16, 255, 256, 257, 1000, 4079, 4080, 65536])
@@ -232,3 +239,84 @@ def test_collisions_left_matches_the_oracle_everywhere(power):
         bad = np.flatnonzero(want != got)
         assert bad.size == 0, (lo, hi, start, end, [(int(i), int(want[i]), int(got[i])) for i in bad[:5]])
         assert want[start] == lo and want[min(end, 60000)] == hi
+
+
+# ---- batch sizes above 16 (check_cfg accepts 1..4096) ---------------------------------------------------------------
+# The batch size sets how many entries a batch holds (ProcEntry[batch]), how many leaves go to the evaluator at once and
+# how far an entry's evaluation index runs: an entry packs kind | evaluation index | order key into one word
+# (dev_search.h proc_pack), and the index must hold every value up to batch_size - 1. The work-queue modes serve batches
+# of at most GW_SLOTS entries: above that they must end in an error (and the engine never takes that gather).
+@pytest.mark.parametrize("batch", [17, 32, 33, 64])
+def test_batch_above_16_default_budget(batch):
+    _check_searches(O.make_config(**TUNED), 2000, batch)
+
+
+@pytest.mark.parametrize("batch,budget,sims,positions", [
+    (255, 2000, 3000, None),
+    (256, 2000, 3000, None),
+    (257, 2000, 3000, None),   # the first batch size whose evaluation index needs a ninth bit
+    (512, 2000, 5120, None),
+    (1024, 2000, 10240, None),
+    (4096, 4096, 40960, ("open5_corner", "short", "mud_wall", "7x7")),
+])
+def test_batches_that_fill_beyond_256_entries(batch, budget, sims, positions):
+    """A fixed collision budget of at least the batch size and ten batches' worth of simulations: batches really fill,
+    so from 257 on evaluation indices above 255 occur (asserted on the oracle's evaluator calls)."""
+    assert budget >= min(batch, 2000) and sims >= 10 * batch
+    largest = _check_searches(_coll(budget), sims, batch, positions=positions)
+    if batch > 256:
+        assert largest > 256, largest
+
+
+def test_batch_512_default_budget_mud_wall():
+    # the default budget (1..256, scaling from 800 nodes) lets the SmartUniform batches pass 256 entries once the tree has
+    # grown: the old eight-bit evaluation index gave a different tree here
+    _check_searches(O.make_config(**TUNED), 4000, 512, positions=("mud_wall",))
+
+
+@pytest.mark.parametrize("sims,batch", [(10, 64), (100, 4096)])
+def test_batch_larger_than_the_simulations_left(sims, batch):
+    # simulate_batch is cut to the simulations that remain (search.rs:961-968)
+    _check_searches(O.make_config(**TUNED), sims, batch)
+    assert _check_searches(_coll(batch), sims, batch) <= sims
+
+
+@pytest.mark.parametrize("batch,budget,sims", [(32, None, 600), (300, 2000, 3000)])
+def test_whole_games_above_batch_16(batch, budget, sims):
+    """Tree reuse between moves, Dirichlet noise at every root, batches of 32 and of up to 300 entries."""
+    g = O.Game(7, 7, 50).random_cheese(10, True, 6)
+    cfg = O.make_config(noise_epsilon=0.25, **TUNED) if budget is None else _coll(budget, noise_epsilon=0.25)
+    want = O.play_game(g, cfg, sims, batch, 91)
+    for mode in UNIFORM_MODES:
+        _same_game(want, H.run(g, 50, cfg, sims, batch, 91, eval_mode=mode))
+    backend = O.CallbackBackend(H.hashed_eval(7))
+    want = O.play_game(g, cfg, sims, batch, 91, backend=4, net=backend)
+    assert max(backend.sizes) <= batch
+    if batch > 256:
+        assert max(backend.sizes) > 256, max(backend.sizes)
+    _same_game(want, H.run(g, 50, cfg, sims, batch, 91, eval_mode=8))
+
+
+def test_arena_growth_at_batch_64():
+    g = O.Game(7, 7, 50).random_cheese(10, True, 9)
+    cfg = O.make_config(**TUNED)
+    want = O.play_game(g, cfg, 500, 64, 5)
+    got = H.run(g, 50, cfg, 500, 64, 5, arena_nodes=64)
+    assert got["grows"] >= 1
+    _same_game(want, got)
+
+
+def test_fresh_arena_of_one_search_never_stalls_without_the_slack():
+    """The runtime sizes a fresh game's arena as 1 + n_sims + 2 * batch + 64 nodes, and takes its longest run of tree pages
+    (64 pages of 768 nodes) whole where only the slack goes past it: 1 + n_sims nodes are what one search needs."""
+    cfg = _coll(4096)
+    for name, g, mt in games():
+        if name not in ("open5_corner", "7x7"):
+            continue
+        got = H.run(g, mt, cfg, 40960, 4096, 42, single=True, arena_nodes=64 * 768)
+        assert 1 + 40960 + 4096 <= 64 * 768 < 1 + 40960 + 2 * 4096 + 64
+        assert got["grows"] == 0, name
+        _same_search(O.search_once(g, cfg, 40960, 4096, seed=42), got, name)
+        got = H.run(g, mt, cfg, 2000, 64, 42, single=True, arena_nodes=2048)  # 1 + n_sims rounded up to 64 nodes
+        assert got["grows"] == 0, name
+        _same_search(O.search_once(g, cfg, 2000, 64, seed=42), got, name)
