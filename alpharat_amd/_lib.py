@@ -123,6 +123,57 @@ class ArGameRecordView(C.Structure):
 
 ArGameSink = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(ArGameRecordView))
 
+
+class ArMatchAgent(C.Structure):
+    _fields_ = [
+        ("weights_path", C.c_char_p), ("simulations", C.c_uint32), ("batch_size", C.c_uint32),
+        ("search", ArSearchConfig), ("rng_seed_base", C.c_uint64),
+    ]
+
+
+class ArMatchParams(C.Structure):
+    _fields_ = [
+        ("width", C.c_uint8), ("height", C.c_uint8), ("cheese_count", C.c_uint16), ("max_turns", C.c_uint16),
+        ("cheese_symmetric", C.c_int), ("maze_type", C.c_char_p), ("positions", C.c_char_p),
+        ("wall_density", C.c_float), ("mud_density", C.c_float), ("maze_symmetric", C.c_int),
+        ("num_games", C.c_uint32), ("first_game_index", C.c_uint32), ("has_seed", C.c_int),
+        ("game_seed_base", C.c_uint64), ("swap_sides", C.c_int), ("concurrent_games", C.c_uint32),
+        ("device", C.c_char_p), ("device_index", C.c_int), ("a", ArMatchAgent), ("b", ArMatchAgent),
+    ]
+
+
+class ArMatchSearchView(C.Structure):
+    _fields_ = [(k, C.POINTER(C.c_float)) for k in (
+        "policy_p1", "policy_p2", "value_p1", "value_p2", "visit_counts_p1", "visit_counts_p2", "prior_p1", "prior_p2")
+    ] + [(k, C.POINTER(C.c_uint32)) for k in ("total_visits", "nn_evals", "terminals", "collisions")]
+
+
+class ArMatchGameView(C.Structure):
+    _fields_ = [
+        ("width", C.c_uint8), ("height", C.c_uint8), ("max_turns", C.c_uint16),
+        ("game_index", C.c_uint32), ("n_positions", C.c_uint32), ("a_is_p1", C.c_uint8), ("result", C.c_uint8),
+        ("final_p1_score", C.c_float), ("final_p2_score", C.c_float),
+        ("p1_pos", C.POINTER(C.c_uint8)), ("p2_pos", C.POINTER(C.c_uint8)),
+        ("p1_score", C.POINTER(C.c_float)), ("p2_score", C.POINTER(C.c_float)),
+        ("p1_mud", C.POINTER(C.c_uint8)), ("p2_mud", C.POINTER(C.c_uint8)),
+        ("turn", C.POINTER(C.c_uint16)), ("cheese_mask", C.POINTER(C.c_uint8)),
+        ("action_p1", C.POINTER(C.c_uint8)), ("action_p2", C.POINTER(C.c_uint8)),
+        ("a", ArMatchSearchView), ("b", ArMatchSearchView),
+    ]
+
+
+class ArMatchStats(C.Structure):
+    _fields_ = [
+        ("total_games", C.c_uint32), ("wins_a", C.c_uint32), ("wins_b", C.c_uint32), ("draws", C.c_uint32),
+        ("cheese_a", C.c_float), ("cheese_b", C.c_float), ("total_positions", C.c_uint64),
+        ("simulations_a", C.c_uint64), ("simulations_b", C.c_uint64), ("nn_evals_a", C.c_uint64),
+        ("nn_evals_b", C.c_uint64), ("terminals_a", C.c_uint64), ("terminals_b", C.c_uint64),
+        ("collisions_a", C.c_uint64), ("collisions_b", C.c_uint64), ("elapsed_secs", C.c_double),
+    ]
+
+
+ArMatchSink = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(ArMatchGameView))
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -149,6 +200,7 @@ EXPORTS = {
     "ar_selfplay_step": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ArSelfPlayStats), C.POINTER(C.c_int)]),
     "ar_selfplay_close": (C.c_int, [C.c_void_p, C.POINTER(ArSelfPlayStats)]),
     "ar_selfplay_info": (C.c_int, [C.c_void_p, C.POINTER(ArSessionInfo)]),
+    "ar_match_run": (C.c_int, [C.POINTER(ArMatchParams), ArMatchSink, C.c_void_p, C.POINTER(ArMatchStats)]),
     "ar_write_bundle": (C.c_int, [C.POINTER(ArGameRecordView), C.c_uint32, C.c_char_p]),
 }
 

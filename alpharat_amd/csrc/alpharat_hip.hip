@@ -31,6 +31,7 @@
 #include "dev_gather8.h"
 #include "dev_gatherw.h"
 #include "dev_backup16.h"
+#include "dev_match.h"
 #include "zig_norm_tables.inc"
 
 using namespace ar;
@@ -1193,6 +1194,89 @@ template <int NW>
 __global__ void k_import_evals(const Slot<NW>* slots, uint32_t slot, Bases B, const EvalOut* in, uint32_t n) {
     const Mem<NW> m = resolve_mem<NW>(slots[slot], B.arena, B.scratch, slot, B.L, B.maze);
     for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) m.ev_local[j] = in[j];
+}
+
+// ---- head-to-head matches (dev_match.h): two slot sets, slot k of either holds game k ---------------------------
+// Replaces the host loop of eval/game.py:47-87 around SearcherAgent.get_move (searcher_agent.py:40-56).
+// All of these run while both engines' streams are at rest on the slots they touch (the host orders them with events):
+// ownership passes at kernel boundaries only, as everywhere else.
+struct MatchInit {
+    uint32_t slot, game_index, a_is_p1, pad;
+};
+template <int NW>
+__global__ void k_match_init(MatchGame<NW>* games, Slot<NW>* sa, Slot<NW>* sb, const MatchInit* init, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const MatchInit mi = init[i];
+    MatchGame<NW> g;
+    g.status = MATCH_PLAYING;
+    g.game_index = mi.game_index;
+    g.n_pos = 0;
+    g.a_is_p1 = mi.a_is_p1;
+    g.error = 0;
+    g.pad[0] = g.pad[1] = g.pad[2] = 0;
+    g.final_st = sa[mi.slot].st;
+    if (st_over(sa[mi.slot].board, g.final_st)) {  // while not game.is_over(): nothing to search
+        g.status = MATCH_FINISHED;
+        sa[mi.slot].status = SLOT_DONE;
+        sb[mi.slot].status = SLOT_DONE;
+    }
+    games[mi.slot] = g;
+}
+// One lane per game: the move of every game whose two searches are complete (dev_match.h match_move). The re-armed slots
+// are tagged for the re-rooting kernel launched behind this one on each engine's stream (stream order, phase 0).
+template <int NW>
+__global__ void __launch_bounds__(64) k_match_move(Slot<NW>* sa, Slot<NW>* sb, MatchGame<NW>* games, MatchPos<NW>* recs,
+                                                   uint32_t n, uint32_t max_turns, const uint8_t* maze, uint32_t sims_a,
+                                                   uint32_t sims_b) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!match_ready(games[i], sa[i], sb[i])) return;
+    // (in place: a move touches the two streams, the two results and a few header words of each slot, not the whole records)
+    match_move(games[i], sa[i], sb[i], maze + sa[i].board.maze_off, recs + (size_t)i * max_turns, sims_a, sims_b,
+               tag_status(SLOT_ADVANCE, 0u));
+}
+// counts[0] finished games (their slots in done_list), [1] games being played, [2] games with the bug guard set
+template <int NW>
+__global__ void k_match_scan(const MatchGame<NW>* games, uint32_t n, uint32_t* counts, uint32_t* done_list) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t st = games[i].status;
+    if (st == MATCH_FINISHED) done_list[atomicAdd(&counts[0], 1u)] = i;
+    else if (st == MATCH_PLAYING) atomicAdd(&counts[1], 1u);
+    if (st != MATCH_EMPTY && games[i].error) atomicAdd(&counts[2], 1u);
+}
+// one block per finished game: header and position records to the staging buffers, the game leaves the match buffer
+template <int NW>
+__global__ void k_match_pack(MatchGame<NW>* games, const uint32_t* done_list, uint32_t n_done, MatchGame<NW>* info,
+                             const MatchPos<NW>* recs, MatchPos<NW>* staging, uint32_t max_turns) {
+    const uint32_t d = blockIdx.x;
+    if (d >= n_done) return;
+    const uint32_t slot = done_list[d];
+    const MatchGame<NW> g = games[slot];
+    const uint32_t n = g.n_pos < max_turns ? g.n_pos : max_turns;
+    const uint32_t words = n * (uint32_t)(sizeof(MatchPos<NW>) / 4);
+    const uint32_t* src = (const uint32_t*)(recs + (size_t)slot * max_turns);
+    uint32_t* dst = (uint32_t*)(staging + (size_t)d * max_turns);
+    for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) dst[w] = src[w];
+    if (threadIdx.x == 0) {
+        info[d] = g;
+        info[d].pad[0] = slot;
+        games[slot].status = MATCH_EMPTY;
+    }
+}
+// the slots of the finished games, one engine at a time: tree pages go back, the slot is free (as k_pack_done leaves it)
+template <int NW>
+__global__ void k_match_release(Slot<NW>* slots, const uint32_t* done_list, uint32_t n_done, Bases B) {
+    const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n_done) return;
+    Slot<NW>& s = slots[done_list[d]];
+    Slot<NW> unused = s;
+    leave_arena(s, unused, B);
+    if (unused.release_grown) s.release_grown = 1;
+    s.cap = 0;
+    s.pool_blk = 0;
+    s.status = SLOT_EMPTY;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3020,6 +3104,389 @@ int search_impl(const ArGameSpec* games, uint32_t n, const SearchCfg& cfg, const
     return AR_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// head-to-head matches
+// ------------------------------------------------------------------------------------------------
+struct MatchSideHost {  // owning twin of ArMatchSearchView
+    std::vector<float> po1, po2, v1, v2, vc1, vc2, pr1, pr2;
+    std::vector<uint32_t> tv, nn, term, coll;
+    void resize(size_t n) {
+        for (auto* v : {&po1, &po2, &vc1, &vc2, &pr1, &pr2}) v->resize(n * 5);
+        v1.resize(n);
+        v2.resize(n);
+        for (auto* v : {&tv, &nn, &term, &coll}) v->resize(n);
+    }
+    void set(size_t i, const MoveResult& m) {
+        memcpy(&po1[i * 5], m.policy[0], 20);
+        memcpy(&po2[i * 5], m.policy[1], 20);
+        v1[i] = m.value[0];
+        v2[i] = m.value[1];
+        memcpy(&vc1[i * 5], m.visit_counts[0], 20);
+        memcpy(&vc2[i * 5], m.visit_counts[1], 20);
+        memcpy(&pr1[i * 5], m.prior[0], 20);
+        memcpy(&pr2[i * 5], m.prior[1], 20);
+        tv[i] = m.total_visits;
+        nn[i] = m.nn_evals;
+        term[i] = m.terminals;
+        coll[i] = m.collisions;
+    }
+    ArMatchSearchView view() const {
+        ArMatchSearchView v;
+        v.policy_p1 = po1.data();
+        v.policy_p2 = po2.data();
+        v.value_p1 = v1.data();
+        v.value_p2 = v2.data();
+        v.visit_counts_p1 = vc1.data();
+        v.visit_counts_p2 = vc2.data();
+        v.prior_p1 = pr1.data();
+        v.prior_p2 = pr2.data();
+        v.total_visits = tv.data();
+        v.nn_evals = nn.data();
+        v.terminals = term.data();
+        v.collisions = coll.data();
+        return v;
+    }
+};
+
+// The match driver: tournament.py:329-373 (one game per worker) and eval/game.py:47-87 (the turn loop) for every
+// resident game at once. Two engines, one per agent, hold the same game in the same slot number; each runs its own
+// step pipeline on its own stream (no side streams: two streams in all, what a self-play session of one group uses),
+// so one agent's evaluator runs beside the other's tree walk. After every step of both, k_match_move (on A's stream,
+// behind an event of B's) moves the games whose two searches are complete, and each engine's re-rooting kernel gives the
+// re-armed slots their fresh roots. The host visits every few steps, as in self-play: stalls, finished games, refills.
+template <int NW>
+struct MatchRun {
+    ArMatchParams p;
+    SearchCfg cfg_a, cfg_b;
+    Engine<NW> ea, eb;
+    std::vector<uint8_t> cost;
+    int hw = 0;
+    uint32_t S = 0;
+    uint64_t gseed = 0, seed_a = 0, seed_b = 0;
+    bool random_pos = false, gen_maze = false, maze_sym = true;
+    float wall_d = 0.0f, mud_d = 0.0f;
+    DevBuf<MatchGame<NW>> games, info;
+    DevBuf<MatchPos<NW>> recs, staging;
+    DevBuf<MatchInit> init;
+    DevBuf<uint32_t> counts, done_list;
+    PinBuf<uint32_t> h_counts;
+    PinBuf<MatchGame<NW>> h_info;
+    PinBuf<MatchPos<NW>> h_staging;
+    hipEvent_t ev_b = nullptr, ev_m = nullptr;
+    ArMatchSink sink = nullptr;
+    void* sink_user = nullptr;
+    ArMatchStats st;
+    uint32_t next_game = 0, finished = 0;
+    std::string err;
+
+    ~MatchRun() {
+        if (ea.stream) hipStreamSynchronize(ea.stream);
+        if (eb.stream) hipStreamSynchronize(eb.stream);
+        if (ev_b) hipEventDestroy(ev_b);
+        if (ev_m) hipEventDestroy(ev_m);
+    }
+
+    bool make_game(uint32_t index, HostGame& g) {  // the game self-play generates for this index (SelfPlaySession::make_game)
+        if (gen_maze) g.cost = generate_maze(p.width, p.height, wall_d, mud_d, maze_sym, gseed + index);
+        g.width = p.width;
+        g.height = p.height;
+        g.max_turns = p.max_turns;
+        g.turn = 0;
+        g.m1 = g.m2 = 0;
+        g.s1 = g.s2 = 0.0f;
+        g.p1 = 0;
+        g.p2 = (uint8_t)(hw - 1);
+        if (random_pos) {
+            HostRng rng((gseed + index) ^ 0x9E3779B97F4A7C15ULL);
+            g.p1 = (uint8_t)rng.below((uint32_t)hw);
+            g.p2 = (uint8_t)(hw - 1 - g.p1);
+            if (!p.cheese_symmetric) g.p2 = (uint8_t)rng.below((uint32_t)hw);
+        }
+        return place_cheese(g, p.cheese_count, p.cheese_symmetric != 0, gseed + index, err);
+    }
+
+    int setup_engine(Engine<NW>& e, const SearchCfg& cfg, ArNet* net, int device) {
+        e.net = net;
+        e.uniform_queue = net == nullptr && default_uniform_queue(S);
+        if (const char* env = getenv("AR_UNIFORM")) e.uniform_queue = net == nullptr && std::string(env) == "queue";
+        e.overlap_advance = false;  // one stream per engine: every hand-off is in stream order (phase 0)
+        e.per_slot_maze = gen_maze;
+        e.maze_stride = (uint32_t)hw * 4u;
+        const std::vector<uint8_t> pool_init = gen_maze ? std::vector<uint8_t>((size_t)S * hw * 4, (uint8_t)0) : cost;
+        const uint32_t arena_nodes = getenv("AR_ARENA_NODES") ? (uint32_t)atoi(getenv("AR_ARENA_NODES")) : 0u;  // test knob
+        return e.setup(device, S, cfg, p.max_turns, pool_init, arena_nodes, e.use_queue());
+    }
+
+    int open(const ArMatchParams& params, int device, ArNet* net_a, ArNet* net_b, ArMatchSink sk, void* sk_user) {
+        p = params;
+        sink = sk;
+        sink_user = sk_user;
+        memset(&st, 0, sizeof st);
+        cfg_a = to_cfg(p.a.search, p.a.simulations, p.a.batch_size);
+        cfg_b = to_cfg(p.b.search, p.b.simulations, p.b.batch_size);
+        cost = open_maze_cost(p.width, p.height);
+        hw = p.width * p.height;
+        gseed = p.game_seed_base;
+        seed_a = p.a.rng_seed_base;
+        seed_b = p.b.rng_seed_base;
+        if (!p.has_seed) {
+            std::random_device rd;
+            gseed = ((uint64_t)rd() << 32) | rd();
+            seed_a = ((uint64_t)rd() << 32) | rd();
+            seed_b = ((uint64_t)rd() << 32) | rd();
+        }
+        random_pos = p.positions && std::string(p.positions) == "random";
+        const std::string maze_type = p.maze_type ? p.maze_type : "open";
+        gen_maze = maze_type != "open";
+        wall_d = maze_type == "classic" ? 0.7f : p.wall_density;
+        mud_d = maze_type == "classic" ? 0.1f : p.mud_density;
+        maze_sym = maze_type == "classic" ? true : p.maze_symmetric != 0;
+        p.maze_type = p.positions = p.device = p.a.weights_path = p.b.weights_path = nullptr;  // caller-owned strings
+
+        S = p.concurrent_games ? p.concurrent_games : 4096u;
+        if (S > p.num_games) S = p.num_games;
+        if (S == 0) return AR_OK;
+        {
+            // what a resident game takes on the device: per agent a fresh tree (with the region's slack) and the slot's
+            // scratch and queue share, plus its match records
+            size_t free_b = 0, total_b = 0;
+            HIP_TRY(hipSetDevice(device));
+            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+            free_b += arena_cached_bytes(device);
+            const size_t per_game = arena_bytes(initial_arena_nodes(cfg_a)) * 5 / 4 + arena_bytes(initial_arena_nodes(cfg_b)) * 5 / 4 +
+                                    Engine<NW>::per_game_overhead(cfg_a, p.max_turns, true) +
+                                    Engine<NW>::per_game_overhead(cfg_b, p.max_turns, true) +
+                                    2 * sizeof(MatchPos<NW>) * p.max_turns + 2 * sizeof(MatchGame<NW>);
+            const size_t reserve = (size_t)4 << 30;
+            const size_t usable = free_b > reserve ? free_b - reserve : 0;
+            if ((size_t)S * per_game > usable) S = (uint32_t)(usable / per_game);
+            if (S == 0) return fail(AR_E_NOMEM, "not enough device memory for a single match game");
+        }
+        if (int rc = setup_engine(ea, cfg_a, net_a, device)) return rc;
+        if (int rc = setup_engine(eb, cfg_b, net_b, device)) return rc;
+        HIP_TRY(hipEventCreateWithFlags(&ev_b, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ev_m, hipEventDisableTiming));
+        const size_t mt = p.max_turns > 0 ? p.max_turns : 1;
+        HIP_TRY(games.alloc(S));
+        HIP_TRY(hipMemset(games.p, 0, sizeof(MatchGame<NW>) * S));
+        HIP_TRY(info.alloc(S));
+        HIP_TRY(recs.alloc((size_t)S * mt));
+        HIP_TRY(staging.alloc((size_t)S * mt));
+        HIP_TRY(init.alloc(S));
+        HIP_TRY(counts.alloc(8));
+        HIP_TRY(done_list.alloc(S));
+        HIP_TRY(h_counts.alloc(8));
+        HIP_TRY(h_info.alloc(S));
+        HIP_TRY(h_staging.alloc((size_t)S * mt));
+        std::vector<uint32_t> all(S);
+        for (uint32_t i = 0; i < S; ++i) all[i] = i;
+        return refill(all);
+    }
+
+    int refill(const std::vector<uint32_t>& free_slots) {
+        std::vector<GameInit<NW>> ia, ib;
+        std::vector<MatchInit> mi;
+        std::vector<uint8_t> mazes;
+        for (uint32_t sl : free_slots) {
+            if (next_game >= p.num_games) break;
+            const uint32_t index = p.first_game_index + next_game;
+            HostGame g;
+            if (!make_game(index, g)) return fail(AR_E_INVALID, err);
+            GameInit<NW> gi;
+            memset(&gi, 0, sizeof gi);
+            fill_state<NW>(g, gi.board, gi.st, gen_maze ? sl * ea.maze_stride : 0u);
+            if (gen_maze) mazes.insert(mazes.end(), g.cost.begin(), g.cost.end());
+            gi.game_index = index;
+            gi.slot = sl;
+            gi.single = 1;  // the search stops in SLOT_DONE; the move is the match's
+            gi.rng_seed = seed_a + index;
+            ia.push_back(gi);
+            gi.rng_seed = seed_b + index;
+            ib.push_back(gi);
+            MatchInit m;
+            m.slot = sl;
+            m.game_index = index;
+            m.a_is_p1 = (p.swap_sides && (index & 1u)) ? 0u : 1u;  // tournament.py:397
+            m.pad = 0;
+            mi.push_back(m);
+            ++next_game;
+        }
+        if (mi.empty()) return AR_OK;
+        if (int rc = ea.start_games(ia, gen_maze ? &mazes : nullptr)) return rc;
+        if (int rc = eb.start_games(ib, gen_maze ? &mazes : nullptr)) return rc;
+        // (both engines' streams are at rest: start_games waits for its kernel)
+        HIP_TRY(hipMemcpyAsync(init.p, mi.data(), sizeof(MatchInit) * mi.size(), hipMemcpyHostToDevice, ea.stream));
+        hipLaunchKernelGGL(k_match_init<NW>, dim3(ea.grid((uint32_t)mi.size())), dim3(64), 0, ea.stream, games.p, ea.slots.p,
+                           eb.slots.p, init.p, (uint32_t)mi.size());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(ea.stream));
+        return AR_OK;
+    }
+
+    // one simulate_batch step of both agents, then the moves of the games whose two searches are complete
+    int tick() {
+        if (int rc = ea.run_steps(1, 1)) return rc;
+        if (int rc = eb.run_steps(1, 1)) return rc;
+        HIP_TRY(hipEventRecord(ev_b, eb.stream));
+        HIP_TRY(hipStreamWaitEvent(ea.stream, ev_b, 0));
+        hipLaunchKernelGGL(k_match_move<NW>, dim3(ea.grid(S)), dim3(64), 0, ea.stream, ea.slots.p, eb.slots.p, games.p, recs.p, S,
+                           (uint32_t)p.max_turns, (const uint8_t*)ea.maze.p, cfg_a.n_sims, cfg_b.n_sims);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev_m, ea.stream));
+        HIP_TRY(hipStreamWaitEvent(eb.stream, ev_m, 0));  // B's stream leaves its slots alone until the moves are made
+        ea.launch_advance();
+        eb.launch_advance();
+        HIP_TRY(hipGetLastError());
+        return AR_OK;
+    }
+
+    void account(const MatchGame<NW>& g, const MatchPos<NW>* pos) {
+        const float f1 = g.final_st.s1, f2 = g.final_st.s2;
+        const uint8_t result = f1 > f2 ? 1 : f2 > f1 ? 2 : 0;
+        st.total_games += 1;
+        st.total_positions += g.n_pos;
+        if (result == 0) st.draws += 1;
+        else if ((result == 1) == (g.a_is_p1 != 0)) st.wins_a += 1;
+        else st.wins_b += 1;
+        st.cheese_a += g.a_is_p1 ? f1 : f2;
+        st.cheese_b += g.a_is_p1 ? f2 : f1;
+        const size_t n = g.n_pos;
+        for (size_t i = 0; i < n; ++i) {
+            st.simulations_a += pos[i].a.total_visits;
+            st.simulations_b += pos[i].b.total_visits;
+            st.nn_evals_a += pos[i].a.nn_evals;
+            st.nn_evals_b += pos[i].b.nn_evals;
+            st.terminals_a += pos[i].a.terminals;
+            st.terminals_b += pos[i].b.terminals;
+            st.collisions_a += pos[i].a.collisions;
+            st.collisions_b += pos[i].b.collisions;
+        }
+        if (!sink) return;
+        const int w = p.width;
+        std::vector<uint8_t> p1_pos(n * 2), p2_pos(n * 2), p1_mud(n), p2_mud(n), mask(n * hw), a1(n), a2(n);
+        std::vector<float> s1(n), s2(n);
+        std::vector<uint16_t> turn(n);
+        MatchSideHost sa, sb;
+        sa.resize(n);
+        sb.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            const MatchPos<NW>& q = pos[i];
+            p1_pos[i * 2] = q.st.p1 % w;
+            p1_pos[i * 2 + 1] = q.st.p1 / w;
+            p2_pos[i * 2] = q.st.p2 % w;
+            p2_pos[i * 2 + 1] = q.st.p2 / w;
+            p1_mud[i] = q.st.m1;
+            p2_mud[i] = q.st.m2;
+            turn[i] = q.st.turn;
+            s1[i] = q.st.s1;
+            s2[i] = q.st.s2;
+            for (int c = 0; c < hw; ++c) mask[i * hw + c] = st_has_cheese(q.st, c) ? 1 : 0;
+            a1[i] = q.a1;
+            a2[i] = q.a2;
+            sa.set(i, q.a);
+            sb.set(i, q.b);
+        }
+        ArMatchGameView v;
+        memset(&v, 0, sizeof v);
+        v.width = p.width;
+        v.height = p.height;
+        v.max_turns = p.max_turns;
+        v.game_index = g.game_index;
+        v.n_positions = g.n_pos;
+        v.a_is_p1 = (uint8_t)g.a_is_p1;
+        v.result = result;
+        v.final_p1_score = f1;
+        v.final_p2_score = f2;
+        v.p1_pos = p1_pos.data();
+        v.p2_pos = p2_pos.data();
+        v.p1_score = s1.data();
+        v.p2_score = s2.data();
+        v.p1_mud = p1_mud.data();
+        v.p2_mud = p2_mud.data();
+        v.turn = turn.data();
+        v.cheese_mask = mask.data();
+        v.action_p1 = a1.data();
+        v.action_p2 = a2.data();
+        v.a = sa.view();
+        v.b = sb.view();
+        sink(sink_user, &v);
+    }
+
+    // stalls, finished games, refills: everything the host does between two runs of ticks
+    int visit() {
+        uint32_t ca[4], cb[4];
+        if (int rc = ea.scan(ca)) return rc;
+        if (int rc = eb.scan(cb)) return rc;
+        if (ca[3] || cb[3]) return fail(AR_E_DEVICE, "internal capacity guard tripped in a tree kernel (slot.error != 0)");
+        if (ca[1])
+            if (int rc = ea.handle_stalls(ca[1], ca[2] > 0)) return rc;
+        if (cb[1])
+            if (int rc = eb.handle_stalls(cb[1], cb[2] > 0)) return rc;
+        HIP_TRY(hipMemsetAsync(counts.p, 0, 32, ea.stream));
+        hipLaunchKernelGGL(k_match_scan<NW>, dim3(ea.grid(S)), dim3(64), 0, ea.stream, (const MatchGame<NW>*)games.p, S, counts.p,
+                           done_list.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_counts.p, counts.p, 32, hipMemcpyDeviceToHost, ea.stream));
+        HIP_TRY(hipStreamSynchronize(ea.stream));
+        const uint32_t n_done = h_counts.p[0], playing = h_counts.p[1];
+        if (h_counts.p[2]) return fail(AR_E_DEVICE, "a match game recorded more positions than max_turns");
+        if (n_done) {
+            const size_t mt = p.max_turns > 0 ? p.max_turns : 1;
+            hipLaunchKernelGGL(k_match_pack<NW>, dim3(n_done), dim3(128), 0, ea.stream, games.p, (const uint32_t*)done_list.p, n_done,
+                               info.p, (const MatchPos<NW>*)recs.p, staging.p, (uint32_t)p.max_turns);
+            hipLaunchKernelGGL(k_match_release<NW>, dim3(ea.grid(n_done)), dim3(64), 0, ea.stream, ea.slots.p,
+                               (const uint32_t*)done_list.p, n_done, ea.bases());
+            hipLaunchKernelGGL(k_match_release<NW>, dim3(eb.grid(n_done)), dim3(64), 0, eb.stream, eb.slots.p,
+                               (const uint32_t*)done_list.p, n_done, eb.bases());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h_info.p, info.p, sizeof(MatchGame<NW>) * n_done, hipMemcpyDeviceToHost, ea.stream));
+            HIP_TRY(hipMemcpyAsync(h_staging.p, staging.p, sizeof(MatchPos<NW>) * (size_t)n_done * mt, hipMemcpyDeviceToHost,
+                                   ea.stream));
+            HIP_TRY(hipStreamSynchronize(ea.stream));
+            HIP_TRY(hipStreamSynchronize(eb.stream));
+            std::vector<uint32_t> free_slots;
+            for (uint32_t d = 0; d < n_done; ++d) {
+                account(h_info.p[d], h_staging.p + (size_t)d * mt);
+                free_slots.push_back(h_info.p[d].pad[0]);
+                ++finished;
+            }
+            if (int rc = refill(free_slots)) return rc;
+        } else if (playing == 0 && finished < p.num_games) {
+            return fail(AR_E_DEVICE, "match stalled: no game is being played but not all games are finished");
+        }
+        return AR_OK;
+    }
+
+    int run(ArMatchStats* out) {
+        const auto t0 = std::chrono::steady_clock::now();
+        // steps between host visits: a move takes n_sims / batch_size steps of the slower agent, so a visit every few
+        // moves costs little and keeps refills timely
+        const uint32_t visit_every = 16;
+        // (bug guard: every batch step of a search produces at least one simulation, so a generation of games is over
+        // after max_turns moves of at most n_sims steps each; stalls and refills wait for a visit -- four times that)
+        const uint64_t per_generation = ((uint64_t)p.max_turns + 1) * ((uint64_t)std::max(cfg_a.n_sims, cfg_b.n_sims) + visit_every) * 4;
+        const uint64_t max_ticks = S ? ((uint64_t)p.num_games / S + 2) * per_generation : 0;
+        uint64_t ticks = 0;
+        while (S > 0 && finished < p.num_games) {
+            for (uint32_t k = 0; k < visit_every; ++k)
+                if (int rc = tick()) return rc;
+            if (int rc = visit()) return rc;
+            ticks += visit_every;
+            if (ticks > max_ticks) return fail(AR_E_DEVICE, "match made no progress: games left unfinished after every step they could need");
+        }
+        st.elapsed_secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        *out = st;
+        return AR_OK;
+    }
+};
+
+template <int NW>
+int match_impl(const ArMatchParams& p, int dev, ArNet* net_a, ArNet* net_b, ArMatchSink sink, void* user, ArMatchStats* out) {
+    MatchRun<NW> run;  // (destroyed before the caller frees the evaluators: ~Engine synchronises its streams)
+    if (int rc = run.open(p, dev, net_a, net_b, sink, user)) return rc;
+    return run.run(out);
+}
+
 }  // namespace
 
 // the evaluator must outlive the engine's streams: the session is destroyed first, then the net
@@ -3229,6 +3696,40 @@ int ar_selfplay_run(const ArSelfPlayParams* p, ArProgress* progress, ArGameSink 
     const int rc2 = ar_selfplay_close(s, out);
     if (rc != AR_OK) return fail(rc, msg);
     return rc2;
+}
+
+// ---- matches: tournament.py:329-373 / eval/game.py:47-87 / searcher_agent.py:40-56 on the device --------------
+int ar_match_run(const ArMatchParams* p, ArMatchSink sink, void* sink_user, ArMatchStats* out) {
+    if (!p || !out) return fail(AR_E_INVALID, "null argument");
+    memset(out, 0, sizeof *out);
+    const std::string mt = p->maze_type ? p->maze_type : "open";
+    if (mt != "open" && mt != "classic" && mt != "random") return fail(AR_E_INVALID, "unknown maze_type: " + mt);
+    const std::string pos = p->positions ? p->positions : "corners";
+    if (pos != "corners" && pos != "random") return fail(AR_E_INVALID, "unknown positions: " + pos);
+    if (p->width == 0 || p->height == 0 || (int)p->width * p->height > 256)
+        return fail(AR_E_INVALID, "board must have 1..256 cells");
+    if (int rc = check_cfg(to_cfg(p->a.search, p->a.simulations, p->a.batch_size))) return rc;
+    if (int rc = check_cfg(to_cfg(p->b.search, p->b.simulations, p->b.batch_size))) return rc;
+    int dev = 0;
+    if (int rc = parse_device(p->device, p->device_index, dev)) return rc;
+    struct Nets {
+        ArNet* n[2] = {nullptr, nullptr};
+        ~Nets() {
+            for (ArNet* x : n)
+                if (x) ar_net_free(x);
+        }
+    } nets;
+    const ArMatchAgent* agents[2] = {&p->a, &p->b};
+    for (int k = 0; k < 2; ++k) {
+        if (!agents[k]->weights_path) continue;
+        if (int rc = ar_net_load(agents[k]->weights_path, dev, &nets.n[k])) return rc;
+        if (nets.n[k]->dev.width != p->width || nets.n[k]->dev.height != p->height)
+            return fail(AR_E_INVALID, std::string("agent ") + (k ? "B" : "A") + ": the network was built for a " +
+                                          std::to_string(nets.n[k]->dev.width) + "x" + std::to_string(nets.n[k]->dev.height) +
+                                          " board, the games are " + std::to_string(p->width) + "x" + std::to_string(p->height));
+    }
+    return (int)p->width * p->height <= 64 ? match_impl<1>(*p, dev, nets.n[0], nets.n[1], sink, sink_user, out)
+                                           : match_impl<4>(*p, dev, nets.n[0], nets.n[1], sink, sink_user, out);
 }
 
 int ar_net_load(const char* blob_path, int device, ArNet** out) {

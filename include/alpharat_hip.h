@@ -250,6 +250,82 @@ typedef struct ArSessionInfo {
 } ArSessionInfo;
 int ar_selfplay_info(const ArSelfPlaySession* session, ArSessionInfo* out);
 
+/* ---- head-to-head matches (alpharat/eval/tournament.py:329-373 -> eval/game.py:47-87 play_game ->
+ * ai/searcher_agent.py:40-56 SearcherAgent.get_move) --------------------------------------------
+ * Two search agents play `num_games` games against each other, every game resident on the device from its first move
+ * to its last. Game i is the game self-play generates for index first_game_index + i (board, maze, positions, cheese
+ * from game_seed_base + index). Agent A plays P1, unless swap_sides != 0 and i is odd (tournament.py:397). Per turn each
+ * agent searches the position on a fresh tree with its own evaluator, budget and configuration, drawing from its own
+ * stream of this game (seeded rng_seed_base + index once per game, never re-seeded), and then samples its action from
+ * the policy of the side it plays with one more draw from that stream (temperature 1.0, searcher_agent.py:53-54).
+ * Neither agent's results depend on the other's stream, nor on how many games are resident. */
+typedef struct ArMatchAgent {
+    const char* weights_path; /* NULL = SmartUniform */
+    uint32_t simulations, batch_size;
+    ArSearchConfig search;
+    uint64_t rng_seed_base;
+} ArMatchAgent;
+
+typedef struct ArMatchParams {
+    /* game: as in ArSelfPlayParams */
+    uint8_t width, height;
+    uint16_t cheese_count, max_turns;
+    int cheese_symmetric;
+    const char* maze_type;
+    const char* positions;
+    float wall_density, mud_density;
+    int maze_symmetric;
+    uint32_t num_games, first_game_index;
+    int has_seed;              /* 0: entropy for the games and both agents' streams */
+    uint64_t game_seed_base;
+    int swap_sides;            /* non-zero: agent B plays P1 in the odd games */
+    uint32_t concurrent_games; /* device-resident games (0 = 4096) */
+    const char* device;
+    int device_index;
+    ArMatchAgent a, b;
+} ArMatchParams;
+
+/* what one agent's searches returned, n_positions rows */
+typedef struct ArMatchSearchView {
+    const float* policy_p1; const float* policy_p2;             /* [n*5] */
+    const float* value_p1;  const float* value_p2;              /* [n]   */
+    const float* visit_counts_p1; const float* visit_counts_p2; /* [n*5] */
+    const float* prior_p1;  const float* prior_p2;              /* [n*5] */
+    const uint32_t* total_visits; const uint32_t* nn_evals;     /* [n]   */
+    const uint32_t* terminals;    const uint32_t* collisions;   /* [n]   */
+} ArMatchSearchView;
+
+/* One finished game; arrays are only valid during the callback. */
+typedef struct ArMatchGameView {
+    uint8_t width, height;
+    uint16_t max_turns;
+    uint32_t game_index, n_positions;
+    uint8_t a_is_p1;
+    uint8_t result; /* 0 draw 1 P1 2 P2 */
+    float final_p1_score, final_p2_score;
+    const uint8_t* p1_pos;  /* [n*2] */
+    const uint8_t* p2_pos;  /* [n*2] */
+    const float* p1_score;  const float* p2_score;
+    const uint8_t* p1_mud;  const uint8_t* p2_mud;
+    const uint16_t* turn;
+    const uint8_t* cheese_mask;   /* [n*h*w] */
+    const uint8_t* action_p1; const uint8_t* action_p2;
+    ArMatchSearchView a, b;
+} ArMatchGameView;
+typedef void (*ArMatchSink)(void* user, const ArMatchGameView* game);
+
+/* tournament.py:61-72 MatchupResult as sums, plus the search counters per agent */
+typedef struct ArMatchStats {
+    uint32_t total_games, wins_a, wins_b, draws;
+    float cheese_a, cheese_b; /* sums of the final scores */
+    uint64_t total_positions;
+    uint64_t simulations_a, simulations_b, nn_evals_a, nn_evals_b, terminals_a, terminals_b, collisions_a, collisions_b;
+    double elapsed_secs;
+} ArMatchStats;
+
+/* Blocking. `sink` may be NULL. */
+int ar_match_run(const ArMatchParams* params, ArMatchSink sink, void* sink_user, ArMatchStats* out);
+
 /* Bundle writer on its own (recording.rs:23-162 write_bundle): used by the known-answer test. */
 int ar_write_bundle(const ArGameRecordView* games, uint32_t n, const char* path);
 
