@@ -8,4 +8,4 @@ for that path (alpharat_mcts.rust_mcts_search, alpharat_sampling.rust_self_play,
 
 __version__ = "0.1.0"
 
-from .match import MatchAgent, MatchResult, play_match  # noqa: E402,F401
+from .match import MatchAgent, MatchResult, play_match, play_round_robin, standard_agents  # noqa: E402,F401

@@ -127,8 +127,11 @@ ArGameSink = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(ArGameRecordView))
 class ArMatchAgent(C.Structure):
     _fields_ = [
         ("weights_path", C.c_char_p), ("simulations", C.c_uint32), ("batch_size", C.c_uint32),
-        ("search", ArSearchConfig), ("rng_seed_base", C.c_uint64),
+        ("search", ArSearchConfig), ("rng_seed_base", C.c_uint64), ("kind", C.c_uint32), ("temperature", C.c_float),
     ]
+
+
+AR_AGENT_SEARCH, AR_AGENT_RANDOM, AR_AGENT_GREEDY = 0, 1, 2
 
 
 class ArMatchParams(C.Structure):

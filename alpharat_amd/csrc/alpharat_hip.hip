@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <cmath>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -32,6 +33,7 @@
 #include "dev_gatherw.h"
 #include "dev_backup16.h"
 #include "dev_match.h"
+#include "dev_agents.h"
 #include "zig_norm_tables.inc"
 
 using namespace ar;
@@ -1196,46 +1198,11 @@ __global__ void k_import_evals(const Slot<NW>* slots, uint32_t slot, Bases B, co
     for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) m.ev_local[j] = in[j];
 }
 
-// ---- head-to-head matches (dev_match.h): two slot sets, slot k of either holds game k ---------------------------
+// ---- head-to-head matches (dev_match.h): one slot set per searching agent, slot k of either holds game k ----------
 // Replaces the host loop of eval/game.py:47-87 around SearcherAgent.get_move (searcher_agent.py:40-56).
-// All of these run while both engines' streams are at rest on the slots they touch (the host orders them with events):
-// ownership passes at kernel boundaries only, as everywhere else.
-struct MatchInit {
-    uint32_t slot, game_index, a_is_p1, pad;
-};
-template <int NW>
-__global__ void k_match_init(MatchGame<NW>* games, Slot<NW>* sa, Slot<NW>* sb, const MatchInit* init, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const MatchInit mi = init[i];
-    MatchGame<NW> g;
-    g.status = MATCH_PLAYING;
-    g.game_index = mi.game_index;
-    g.n_pos = 0;
-    g.a_is_p1 = mi.a_is_p1;
-    g.error = 0;
-    g.pad[0] = g.pad[1] = g.pad[2] = 0;
-    g.final_st = sa[mi.slot].st;
-    if (st_over(sa[mi.slot].board, g.final_st)) {  // while not game.is_over(): nothing to search
-        g.status = MATCH_FINISHED;
-        sa[mi.slot].status = SLOT_DONE;
-        sb[mi.slot].status = SLOT_DONE;
-    }
-    games[mi.slot] = g;
-}
-// One lane per game: the move of every game whose two searches are complete (dev_match.h match_move). The re-armed slots
-// are tagged for the re-rooting kernel launched behind this one on each engine's stream (stream order, phase 0).
-template <int NW>
-__global__ void __launch_bounds__(64) k_match_move(Slot<NW>* sa, Slot<NW>* sb, MatchGame<NW>* games, MatchPos<NW>* recs,
-                                                   uint32_t n, uint32_t max_turns, const uint8_t* maze, uint32_t sims_a,
-                                                   uint32_t sims_b) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (!match_ready(games[i], sa[i], sb[i])) return;
-    // (in place: a move touches the two streams, the two results and a few header words of each slot, not the whole records)
-    match_move(games[i], sa[i], sb[i], maze + sa[i].board.maze_off, recs + (size_t)i * max_turns, sims_a, sims_b,
-               tag_status(SLOT_ADVANCE, 0u));
-}
+// All of these run while the engines' streams are at rest on the slots they touch (the host orders them with events):
+// ownership passes at kernel boundaries only, as everywhere else. (The kernels of the move itself follow below, with
+// the agents that do not search.)
 // counts[0] finished games (their slots in done_list), [1] games being played, [2] games with the bug guard set
 template <int NW>
 __global__ void k_match_scan(const MatchGame<NW>* games, uint32_t n, uint32_t* counts, uint32_t* done_list) {
@@ -1277,6 +1244,136 @@ __global__ void k_match_release(Slot<NW>* slots, const uint32_t* done_list, uint
     s.cap = 0;
     s.pool_blk = 0;
     s.status = SLOT_EMPTY;
+}
+
+
+// ---- matches with agents that do not search (dev_agents.h) --------------------------------------------------------
+// The match keeps the position, the random agents' streams and the greedy agents' moves of game k in aux[k], and the
+// mazes in a pool of its own (an agent without an engine has none). `sa` / `sb` are null for an agent that does not search.
+template <int NW>
+struct MatchAuxInit {
+    uint32_t slot, game_index, a_is_p1, pad;
+    Board board;
+    State<NW> st;
+    uint64_t seed_a, seed_b;
+};
+// one block per new game: its maze goes to the slot's pool entry (maze_stride != 0), lane 0 writes the game's records
+template <int NW>
+__global__ void __launch_bounds__(64) k_match_init_agents(MatchGame<NW>* games, MatchAux<NW>* aux, Slot<NW>* sa, Slot<NW>* sb,
+                                                          const MatchAuxInit<NW>* init, uint32_t n, const uint8_t* maze_stage,
+                                                          uint8_t* maze, uint32_t maze_stride) {
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;
+    const MatchAuxInit<NW> mi = init[i];
+    if (maze_stride) {
+        const uint32_t* src = (const uint32_t*)(maze_stage + (size_t)i * maze_stride);
+        uint32_t* dst = (uint32_t*)(maze + (size_t)mi.slot * maze_stride);
+        for (uint32_t w = threadIdx.x; w < maze_stride / 4u; w += blockDim.x) dst[w] = src[w];
+    }
+    if (threadIdx.x != 0) return;
+    MatchAux<NW> x;
+    x.board = mi.board;
+    x.st = mi.st;
+    rng_seed(x.rng[0], mi.seed_a);
+    rng_seed(x.rng[1], mi.seed_b);
+    x.greedy_act[0] = x.greedy_act[1] = DIR_STAY;
+    x.pad[0] = x.pad[1] = 0;
+    aux[mi.slot] = x;
+    MatchGame<NW> g;
+    g.status = MATCH_PLAYING;
+    g.game_index = mi.game_index;
+    g.n_pos = 0;
+    g.a_is_p1 = mi.a_is_p1;
+    g.error = 0;
+    g.pad[0] = g.pad[1] = g.pad[2] = 0;
+    g.final_st = mi.st;
+    if (st_over(mi.board, mi.st)) {  // while not game.is_over(): nothing to play
+        g.status = MATCH_FINISHED;
+        if (sa) sa[mi.slot].status = SLOT_DONE;
+        if (sb) sb[mi.slot].status = SLOT_DONE;
+    }
+    games[mi.slot] = g;
+}
+
+__device__ inline uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, m, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ inline uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
+    return v;
+}
+// greedy_agent.py:34-84 for the player on `start`, by the whole wavefront (dev_agents.h: levels of increasing distance,
+// pop order inside a level from the keys). At most `hw` levels: every level settles a cell. `bound_hit`: the loop ran out.
+template <int NW>
+__device__ uint32_t greedy_move_wave(GreedyShared& sh, const uint8_t* cost, const Board& board, const State<NW>& st,
+                                     uint32_t start, bool& bound_hit) {
+    const uint32_t lane = threadIdx.x, hw = (uint32_t)board.width * board.height;
+    const int w = board.width, h = board.height;
+    bound_hit = false;
+    __syncthreads();  // (the block of a previous call is no longer read)
+    greedy_load(sh, lane, cost, st, hw, start);
+    __syncthreads();
+    if (sh.cheese[start]) return DIR_STAY;
+    uint32_t settled = 1;
+    for (uint32_t round = 0; round < hw; ++round) {
+        const uint32_t level = wave_min_u32(greedy_tent(sh, lane, hw, w, h));
+        if (level == GREEDY_NONE) return DIR_STAY;  // the heap ran empty: no cheese can be reached
+        greedy_key(sh, lane, level, hw, w, h);
+        __syncthreads();
+        uint32_t cheese;
+        const uint32_t n = wave_sum_u32(greedy_rank(sh, lane, level, settled, hw, cheese));
+        cheese = wave_min_u32(cheese);
+        if (cheese != GREEDY_NO_CHEESE) return cheese & 0xffu;
+        settled += n;
+        __syncthreads();
+    }
+    bound_hit = true;
+    return DIR_STAY;
+}
+// One wavefront per resident game: the moves of the greedy agents of every game that is ready to move, left in aux for
+// k_match_move_agents behind it on the same stream.
+template <int NW>
+__global__ void __launch_bounds__(64) k_match_greedy(const Slot<NW>* sa, const Slot<NW>* sb, MatchGame<NW>* games,
+                                                     MatchAux<NW>* aux, uint32_t n, const uint8_t* maze, uint32_t kind_a,
+                                                     uint32_t kind_b) {
+    __shared__ GreedyShared sh;
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;
+    if (!match_ready_agents(games[i], sa ? sa + i : nullptr, sb ? sb + i : nullptr)) return;  // (uniform over the block)
+    const Board board = aux[i].board;
+    const State<NW> st = aux[i].st;
+    if ((uint32_t)board.width * board.height > GREEDY_CELLS) return;
+    const uint8_t* cost = maze + board.maze_off;
+    const int side_a = games[i].a_is_p1 ? 0 : 1;
+    for (int which = 0; which < 2; ++which) {
+        if ((which == 0 ? kind_a : kind_b) != AGENT_GREEDY) continue;
+        const int side = which == 0 ? side_a : 1 - side_a;
+        bool bound_hit;
+        const uint32_t mv = greedy_move_wave<NW>(sh, cost, board, st, side == 0 ? st.p1 : st.p2, bound_hit);
+        if (threadIdx.x == 0) {
+            aux[i].greedy_act[which] = mv;
+            if (bound_hit) games[i].error = 8;
+        }
+    }
+}
+// One lane per game: the move of every game that is ready (dev_agents.h match_move_agents), as k_match_move
+template <int NW>
+__global__ void __launch_bounds__(64) k_match_move_agents(Slot<NW>* sa, Slot<NW>* sb, MatchGame<NW>* games, MatchAux<NW>* aux,
+                                                          MatchPos<NW>* recs, uint32_t n, uint32_t max_turns,
+                                                          const uint8_t* maze, AgentDesc da, AgentDesc db) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Slot<NW>* a = sa ? sa + i : nullptr;
+    Slot<NW>* b = sb ? sb + i : nullptr;
+    if (!match_ready_agents(games[i], a, b)) return;
+    match_move_agents(games[i], aux[i], a, b, da, db, maze + aux[i].board.maze_off, recs + (size_t)i * max_turns,
+                      tag_status(SLOT_ADVANCE, 0u));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3149,16 +3246,22 @@ struct MatchSideHost {  // owning twin of ArMatchSearchView
 };
 
 // The match driver: tournament.py:329-373 (one game per worker) and eval/game.py:47-87 (the turn loop) for every
-// resident game at once. Two engines, one per agent, hold the same game in the same slot number; each runs its own
-// step pipeline on its own stream (no side streams: two streams in all, what a self-play session of one group uses),
-// so one agent's evaluator runs beside the other's tree walk. After every step of both, k_match_move (on A's stream,
-// behind an event of B's) moves the games whose two searches are complete, and each engine's re-rooting kernel gives the
-// re-armed slots their fresh roots. The host visits every few steps, as in self-play: stalls, finished games, refills.
+// resident game at once. Every agent that searches has an engine; two engines hold the same game in the same slot number
+// and each runs its own step pipeline on its own stream (no side streams: two streams in all, what a self-play session
+// of one group uses), so one agent's evaluator runs beside the other's tree walk. An agent that does not search
+// (ArMatchAgent::kind random / greedy) has no engine: no slots, no arenas, no leaf queue, no network. After every step of
+// the engines, k_match_greedy and k_match_move_agents (on the match's stream: A's, else B's, else one of its own; behind
+// an event of B's when both search) move the games in which every searching agent's search is complete, and each engine's
+// re-rooting kernel gives the re-armed slots their fresh roots. The host visits every few steps, as in self-play: stalls,
+// finished games, refills.
 template <int NW>
 struct MatchRun {
     ArMatchParams p;
     SearchCfg cfg_a, cfg_b;
-    Engine<NW> ea, eb;
+    Engine<NW> ea, eb;  // set up only for an agent that searches (has_a / has_b)
+    bool has_a = true, has_b = true;
+    AgentDesc da, db;
+    hipStream_t own_stream = nullptr, ms = nullptr;  // ms: the stream the match's own kernels run on
     std::vector<uint8_t> cost;
     int hw = 0;
     uint32_t S = 0;
@@ -3167,7 +3270,10 @@ struct MatchRun {
     float wall_d = 0.0f, mud_d = 0.0f;
     DevBuf<MatchGame<NW>> games, info;
     DevBuf<MatchPos<NW>> recs, staging;
-    DevBuf<MatchInit> init;
+    DevBuf<MatchAux<NW>> aux;
+    DevBuf<MatchAuxInit<NW>> init;
+    DevBuf<uint8_t> maze, maze_stage;  // the match's own maze pool: one entry, or one per slot for generated mazes
+    uint32_t maze_stride = 0;
     DevBuf<uint32_t> counts, done_list;
     PinBuf<uint32_t> h_counts;
     PinBuf<MatchGame<NW>> h_info;
@@ -3182,6 +3288,10 @@ struct MatchRun {
     ~MatchRun() {
         if (ea.stream) hipStreamSynchronize(ea.stream);
         if (eb.stream) hipStreamSynchronize(eb.stream);
+        if (own_stream) {
+            hipStreamSynchronize(own_stream);
+            hipStreamDestroy(own_stream);
+        }
         if (ev_b) hipEventDestroy(ev_b);
         if (ev_m) hipEventDestroy(ev_m);
     }
@@ -3222,8 +3332,12 @@ struct MatchRun {
         sink = sk;
         sink_user = sk_user;
         memset(&st, 0, sizeof st);
-        cfg_a = to_cfg(p.a.search, p.a.simulations, p.a.batch_size);
-        cfg_b = to_cfg(p.b.search, p.b.simulations, p.b.batch_size);
+        has_a = p.a.kind == AR_AGENT_SEARCH;
+        has_b = p.b.kind == AR_AGENT_SEARCH;
+        cfg_a = to_cfg(p.a.search, has_a ? p.a.simulations : 0u, has_a ? p.a.batch_size : 1u);
+        cfg_b = to_cfg(p.b.search, has_b ? p.b.simulations : 0u, has_b ? p.b.batch_size : 1u);
+        da = AgentDesc{p.a.kind, p.a.temperature, cfg_a.n_sims, 0u};
+        db = AgentDesc{p.b.kind, p.b.temperature, cfg_b.n_sims, 0u};
         cost = open_maze_cost(p.width, p.height);
         hw = p.width * p.height;
         gseed = p.game_seed_base;
@@ -3253,17 +3367,27 @@ struct MatchRun {
             HIP_TRY(hipSetDevice(device));
             HIP_TRY(hipMemGetInfo(&free_b, &total_b));
             free_b += arena_cached_bytes(device);
-            const size_t per_game = arena_bytes(initial_arena_nodes(cfg_a)) * 5 / 4 + arena_bytes(initial_arena_nodes(cfg_b)) * 5 / 4 +
-                                    Engine<NW>::per_game_overhead(cfg_a, p.max_turns, true) +
-                                    Engine<NW>::per_game_overhead(cfg_b, p.max_turns, true) +
-                                    2 * sizeof(MatchPos<NW>) * p.max_turns + 2 * sizeof(MatchGame<NW>);
+            size_t per_game = 2 * sizeof(MatchPos<NW>) * p.max_turns + 2 * sizeof(MatchGame<NW>) + sizeof(MatchAux<NW>) +
+                              sizeof(MatchAuxInit<NW>) + 2 * (size_t)hw * 4;
+            if (has_a) per_game += arena_bytes(initial_arena_nodes(cfg_a)) * 5 / 4 + Engine<NW>::per_game_overhead(cfg_a, p.max_turns, true);
+            if (has_b) per_game += arena_bytes(initial_arena_nodes(cfg_b)) * 5 / 4 + Engine<NW>::per_game_overhead(cfg_b, p.max_turns, true);
             const size_t reserve = (size_t)4 << 30;
             const size_t usable = free_b > reserve ? free_b - reserve : 0;
             if ((size_t)S * per_game > usable) S = (uint32_t)(usable / per_game);
             if (S == 0) return fail(AR_E_NOMEM, "not enough device memory for a single match game");
         }
-        if (int rc = setup_engine(ea, cfg_a, net_a, device)) return rc;
-        if (int rc = setup_engine(eb, cfg_b, net_b, device)) return rc;
+        if (has_a)
+            if (int rc = setup_engine(ea, cfg_a, net_a, device)) return rc;
+        if (has_b)
+            if (int rc = setup_engine(eb, cfg_b, net_b, device)) return rc;
+        if (!has_a && !has_b) HIP_TRY(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
+        ms = has_a ? ea.stream : has_b ? eb.stream : own_stream;
+        maze_stride = gen_maze ? (uint32_t)hw * 4u : 0u;
+        HIP_TRY(maze.alloc(gen_maze ? (size_t)S * maze_stride : cost.size()));
+        if (gen_maze) HIP_TRY(maze_stage.alloc((size_t)S * maze_stride));
+        else HIP_TRY(hipMemcpy(maze.p, cost.data(), cost.size(), hipMemcpyHostToDevice));
+        HIP_TRY(aux.alloc(S));
+        HIP_TRY(hipMemset(aux.p, 0, sizeof(MatchAux<NW>) * S));
         HIP_TRY(hipEventCreateWithFlags(&ev_b, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev_m, hipEventDisableTiming));
         const size_t mt = p.max_turns > 0 ? p.max_turns : 1;
@@ -3285,7 +3409,7 @@ struct MatchRun {
 
     int refill(const std::vector<uint32_t>& free_slots) {
         std::vector<GameInit<NW>> ia, ib;
-        std::vector<MatchInit> mi;
+        std::vector<MatchAuxInit<NW>> mi;
         std::vector<uint8_t> mazes;
         for (uint32_t sl : free_slots) {
             if (next_game >= p.num_games) break;
@@ -3294,7 +3418,7 @@ struct MatchRun {
             if (!make_game(index, g)) return fail(AR_E_INVALID, err);
             GameInit<NW> gi;
             memset(&gi, 0, sizeof gi);
-            fill_state<NW>(g, gi.board, gi.st, gen_maze ? sl * ea.maze_stride : 0u);
+            fill_state<NW>(g, gi.board, gi.st, gen_maze ? sl * ((uint32_t)hw * 4u) : 0u);
             if (gen_maze) mazes.insert(mazes.end(), g.cost.begin(), g.cost.end());
             gi.game_index = index;
             gi.slot = sl;
@@ -3303,39 +3427,60 @@ struct MatchRun {
             ia.push_back(gi);
             gi.rng_seed = seed_b + index;
             ib.push_back(gi);
-            MatchInit m;
+            MatchAuxInit<NW> m;
+            memset(&m, 0, sizeof m);
             m.slot = sl;
             m.game_index = index;
             m.a_is_p1 = (p.swap_sides && (index & 1u)) ? 0u : 1u;  // tournament.py:397
-            m.pad = 0;
+            m.board = gi.board;
+            m.st = gi.st;
+            m.seed_a = seed_a + index;
+            m.seed_b = seed_b + index;
             mi.push_back(m);
             ++next_game;
         }
         if (mi.empty()) return AR_OK;
-        if (int rc = ea.start_games(ia, gen_maze ? &mazes : nullptr)) return rc;
-        if (int rc = eb.start_games(ib, gen_maze ? &mazes : nullptr)) return rc;
-        // (both engines' streams are at rest: start_games waits for its kernel)
-        HIP_TRY(hipMemcpyAsync(init.p, mi.data(), sizeof(MatchInit) * mi.size(), hipMemcpyHostToDevice, ea.stream));
-        hipLaunchKernelGGL(k_match_init<NW>, dim3(ea.grid((uint32_t)mi.size())), dim3(64), 0, ea.stream, games.p, ea.slots.p,
-                           eb.slots.p, init.p, (uint32_t)mi.size());
+        if (has_a)
+            if (int rc = ea.start_games(ia, gen_maze ? &mazes : nullptr)) return rc;
+        if (has_b)
+            if (int rc = eb.start_games(ib, gen_maze ? &mazes : nullptr)) return rc;
+        // (the engines' streams are at rest: start_games waits for its kernel)
+        HIP_TRY(hipMemcpyAsync(init.p, mi.data(), sizeof(MatchAuxInit<NW>) * mi.size(), hipMemcpyHostToDevice, ms));
+        if (gen_maze) HIP_TRY(hipMemcpyAsync(maze_stage.p, mazes.data(), mazes.size(), hipMemcpyHostToDevice, ms));
+        hipLaunchKernelGGL(k_match_init_agents<NW>, dim3((uint32_t)mi.size()), dim3(64), 0, ms, games.p, aux.p, slots_a(), slots_b(),
+                           (const MatchAuxInit<NW>*)init.p, (uint32_t)mi.size(), (const uint8_t*)maze_stage.p, maze.p, maze_stride);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(ea.stream));
+        HIP_TRY(hipStreamSynchronize(ms));
         return AR_OK;
     }
 
-    // one simulate_batch step of both agents, then the moves of the games whose two searches are complete
+    Slot<NW>* slots_a() { return has_a ? ea.slots.p : nullptr; }
+    Slot<NW>* slots_b() { return has_b ? eb.slots.p : nullptr; }
+    static uint32_t grid(uint32_t n) { return (n + 63) / 64; }
+
+    // one simulate_batch step of every searching agent, then the moves of the games whose searches are complete (with no
+    // searching agent: one move of every resident game)
     int tick() {
-        if (int rc = ea.run_steps(1, 1)) return rc;
-        if (int rc = eb.run_steps(1, 1)) return rc;
-        HIP_TRY(hipEventRecord(ev_b, eb.stream));
-        HIP_TRY(hipStreamWaitEvent(ea.stream, ev_b, 0));
-        hipLaunchKernelGGL(k_match_move<NW>, dim3(ea.grid(S)), dim3(64), 0, ea.stream, ea.slots.p, eb.slots.p, games.p, recs.p, S,
-                           (uint32_t)p.max_turns, (const uint8_t*)ea.maze.p, cfg_a.n_sims, cfg_b.n_sims);
+        if (has_a)
+            if (int rc = ea.run_steps(1, 1)) return rc;
+        if (has_b)
+            if (int rc = eb.run_steps(1, 1)) return rc;
+        if (has_a && has_b) {
+            HIP_TRY(hipEventRecord(ev_b, eb.stream));
+            HIP_TRY(hipStreamWaitEvent(ea.stream, ev_b, 0));
+        }
+        if (da.kind == AGENT_GREEDY || db.kind == AGENT_GREEDY)
+            hipLaunchKernelGGL(k_match_greedy<NW>, dim3(S), dim3(64), 0, ms, (const Slot<NW>*)slots_a(), (const Slot<NW>*)slots_b(),
+                               games.p, aux.p, S, (const uint8_t*)maze.p, da.kind, db.kind);
+        hipLaunchKernelGGL(k_match_move_agents<NW>, dim3(grid(S)), dim3(64), 0, ms, slots_a(), slots_b(), games.p, aux.p, recs.p, S,
+                           (uint32_t)p.max_turns, (const uint8_t*)maze.p, da, db);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev_m, ea.stream));
-        HIP_TRY(hipStreamWaitEvent(eb.stream, ev_m, 0));  // B's stream leaves its slots alone until the moves are made
-        ea.launch_advance();
-        eb.launch_advance();
+        if (has_a && has_b) {
+            HIP_TRY(hipEventRecord(ev_m, ea.stream));
+            HIP_TRY(hipStreamWaitEvent(eb.stream, ev_m, 0));  // B's stream leaves its slots alone until the moves are made
+        }
+        if (has_a) ea.launch_advance();
+        if (has_b) eb.launch_advance();
         HIP_TRY(hipGetLastError());
         return AR_OK;
     }
@@ -3414,36 +3559,40 @@ struct MatchRun {
 
     // stalls, finished games, refills: everything the host does between two runs of ticks
     int visit() {
-        uint32_t ca[4], cb[4];
-        if (int rc = ea.scan(ca)) return rc;
-        if (int rc = eb.scan(cb)) return rc;
+        uint32_t ca[4] = {0, 0, 0, 0}, cb[4] = {0, 0, 0, 0};
+        if (has_a)
+            if (int rc = ea.scan(ca)) return rc;
+        if (has_b)
+            if (int rc = eb.scan(cb)) return rc;
         if (ca[3] || cb[3]) return fail(AR_E_DEVICE, "internal capacity guard tripped in a tree kernel (slot.error != 0)");
         if (ca[1])
             if (int rc = ea.handle_stalls(ca[1], ca[2] > 0)) return rc;
         if (cb[1])
             if (int rc = eb.handle_stalls(cb[1], cb[2] > 0)) return rc;
-        HIP_TRY(hipMemsetAsync(counts.p, 0, 32, ea.stream));
-        hipLaunchKernelGGL(k_match_scan<NW>, dim3(ea.grid(S)), dim3(64), 0, ea.stream, (const MatchGame<NW>*)games.p, S, counts.p,
+        HIP_TRY(hipMemsetAsync(counts.p, 0, 32, ms));
+        hipLaunchKernelGGL(k_match_scan<NW>, dim3(grid(S)), dim3(64), 0, ms, (const MatchGame<NW>*)games.p, S, counts.p,
                            done_list.p);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_counts.p, counts.p, 32, hipMemcpyDeviceToHost, ea.stream));
-        HIP_TRY(hipStreamSynchronize(ea.stream));
+        HIP_TRY(hipMemcpyAsync(h_counts.p, counts.p, 32, hipMemcpyDeviceToHost, ms));
+        HIP_TRY(hipStreamSynchronize(ms));
         const uint32_t n_done = h_counts.p[0], playing = h_counts.p[1];
-        if (h_counts.p[2]) return fail(AR_E_DEVICE, "a match game recorded more positions than max_turns");
+        if (h_counts.p[2])
+            return fail(AR_E_DEVICE, "a match game recorded more positions than max_turns, or a greedy move ran past its bound");
         if (n_done) {
             const size_t mt = p.max_turns > 0 ? p.max_turns : 1;
-            hipLaunchKernelGGL(k_match_pack<NW>, dim3(n_done), dim3(128), 0, ea.stream, games.p, (const uint32_t*)done_list.p, n_done,
+            hipLaunchKernelGGL(k_match_pack<NW>, dim3(n_done), dim3(128), 0, ms, games.p, (const uint32_t*)done_list.p, n_done,
                                info.p, (const MatchPos<NW>*)recs.p, staging.p, (uint32_t)p.max_turns);
-            hipLaunchKernelGGL(k_match_release<NW>, dim3(ea.grid(n_done)), dim3(64), 0, ea.stream, ea.slots.p,
-                               (const uint32_t*)done_list.p, n_done, ea.bases());
-            hipLaunchKernelGGL(k_match_release<NW>, dim3(eb.grid(n_done)), dim3(64), 0, eb.stream, eb.slots.p,
-                               (const uint32_t*)done_list.p, n_done, eb.bases());
+            if (has_a)
+                hipLaunchKernelGGL(k_match_release<NW>, dim3(grid(n_done)), dim3(64), 0, ea.stream, ea.slots.p,
+                                   (const uint32_t*)done_list.p, n_done, ea.bases());
+            if (has_b)
+                hipLaunchKernelGGL(k_match_release<NW>, dim3(grid(n_done)), dim3(64), 0, eb.stream, eb.slots.p,
+                                   (const uint32_t*)done_list.p, n_done, eb.bases());
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(h_info.p, info.p, sizeof(MatchGame<NW>) * n_done, hipMemcpyDeviceToHost, ea.stream));
-            HIP_TRY(hipMemcpyAsync(h_staging.p, staging.p, sizeof(MatchPos<NW>) * (size_t)n_done * mt, hipMemcpyDeviceToHost,
-                                   ea.stream));
-            HIP_TRY(hipStreamSynchronize(ea.stream));
-            HIP_TRY(hipStreamSynchronize(eb.stream));
+            HIP_TRY(hipMemcpyAsync(h_info.p, info.p, sizeof(MatchGame<NW>) * n_done, hipMemcpyDeviceToHost, ms));
+            HIP_TRY(hipMemcpyAsync(h_staging.p, staging.p, sizeof(MatchPos<NW>) * (size_t)n_done * mt, hipMemcpyDeviceToHost, ms));
+            HIP_TRY(hipStreamSynchronize(ms));
+            if (has_b) HIP_TRY(hipStreamSynchronize(eb.stream));
             std::vector<uint32_t> free_slots;
             for (uint32_t d = 0; d < n_done; ++d) {
                 account(h_info.p[d], h_staging.p + (size_t)d * mt);
@@ -3708,8 +3857,20 @@ int ar_match_run(const ArMatchParams* p, ArMatchSink sink, void* sink_user, ArMa
     if (pos != "corners" && pos != "random") return fail(AR_E_INVALID, "unknown positions: " + pos);
     if (p->width == 0 || p->height == 0 || (int)p->width * p->height > 256)
         return fail(AR_E_INVALID, "board must have 1..256 cells");
-    if (int rc = check_cfg(to_cfg(p->a.search, p->a.simulations, p->a.batch_size))) return rc;
-    if (int rc = check_cfg(to_cfg(p->b.search, p->b.simulations, p->b.batch_size))) return rc;
+    const ArMatchAgent* agents[2] = {&p->a, &p->b};
+    for (int k = 0; k < 2; ++k) {
+        const ArMatchAgent& ag = *agents[k];
+        const std::string who = std::string("agent ") + (k ? "B" : "A") + ": ";
+        if (ag.kind != AR_AGENT_SEARCH && ag.kind != AR_AGENT_RANDOM && ag.kind != AR_AGENT_GREEDY)
+            return fail(AR_E_INVALID, who + "unknown kind " + std::to_string(ag.kind));
+        if (!std::isfinite(ag.temperature) || ag.temperature < 0.0f)
+            return fail(AR_E_INVALID, who + "temperature must be finite and >= 0");
+        if (ag.kind != AR_AGENT_SEARCH) {
+            if (ag.weights_path) return fail(AR_E_INVALID, who + "weights_path given for a random or greedy agent, which has no evaluator");
+            continue;  // (simulations, batch_size and search are not read)
+        }
+        if (int rc = check_cfg(to_cfg(ag.search, ag.simulations, ag.batch_size))) return rc;
+    }
     int dev = 0;
     if (int rc = parse_device(p->device, p->device_index, dev)) return rc;
     struct Nets {
@@ -3719,7 +3880,6 @@ int ar_match_run(const ArMatchParams* p, ArMatchSink sink, void* sink_user, ArMa
                 if (x) ar_net_free(x);
         }
     } nets;
-    const ArMatchAgent* agents[2] = {&p->a, &p->b};
     for (int k = 0; k < 2; ++k) {
         if (!agents[k]->weights_path) continue;
         if (int rc = ar_net_load(agents[k]->weights_path, dev, &nets.n[k])) return rc;

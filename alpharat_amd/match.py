@@ -1,4 +1,4 @@
-"""Head-to-head matches between two search agents, played on the MI355X from the first move to the last.
+"""Head-to-head matches between two agents, played on the MI355X from the first move to the last.
 
 The reference plays evaluation games on the CPU: ``alpharat/eval/tournament.py:329-373`` runs one game per worker
 through ``alpharat/eval/game.py:47-87`` ``play_game``, whose agents (``alpharat/ai/searcher_agent.py:40-56``) search the
@@ -8,6 +8,11 @@ the game steps stay on the device; the host only drains finished games.
 
 Agent A plays P1 in even games and, with ``swap_sides``, P2 in odd ones (tournament.py:397). Each agent draws from
 its own random stream per game (``seed + game index``), which continues from move to move.
+
+Besides search agents there are the baselines of the reference's benchmark (``alpharat/eval/benchmark.py:78-125``):
+``MatchAgent.random`` (``ai/random_agent.py``), ``MatchAgent.greedy`` (``ai/greedy_agent.py``) and ``MatchAgent.nn``
+(``ai/config.py:88-106``: the network's policy alone, sampled at a temperature). ``standard_agents`` builds the
+benchmark's set and ``play_round_robin`` plays every pair of a set; ratings and tables are left to the caller.
 """
 from __future__ import annotations
 
@@ -21,6 +26,7 @@ import numpy as np
 
 from . import _lib
 
+_KINDS = {"search": _lib.AR_AGENT_SEARCH, "random": _lib.AR_AGENT_RANDOM, "greedy": _lib.AR_AGENT_GREEDY}
 _SEARCH_FIELDS = ("c_puct", "fpu_reduction", "force_k", "noise_epsilon", "noise_concentration", "collision_limit_min",
                   "collision_limit_max", "collision_scaling_start", "collision_scaling_end", "collision_scaling_power")
 
@@ -28,7 +34,9 @@ _SEARCH_FIELDS = ("c_puct", "fpu_reduction", "force_k", "noise_epsilon", "noise_
 @dataclass
 class MatchAgent:
     """One side of a match: a name, an evaluator (``checkpoint``: a ``.pt`` / ``.arnet`` path, None = smart-uniform
-    priors), the search arguments of ``HipSearcher`` and the base of its per-game random streams."""
+    priors), the search arguments of ``HipSearcher`` and the base of its per-game random streams. ``kind`` is
+    ``"search"``, ``"random"`` or ``"greedy"``; the last two take no checkpoint and ignore the search arguments.
+    ``temperature`` (search agents) is that of ``ai/utils.py:8-40``: 1.0 samples the policy, 0.0 takes its argmax."""
 
     name: str
     checkpoint: str | Path | None = None
@@ -45,12 +53,31 @@ class MatchAgent:
     collision_scaling_end: int = 50_000
     collision_scaling_power: float = 1.0
     seed: int = 0
+    kind: str = "search"
+    temperature: float = 1.0
+
+    @classmethod
+    def random(cls, name: str = "random", seed: int = 0) -> "MatchAgent":
+        """``RandomAgent``: a uniform draw over the five actions at every move."""
+        return cls(name=name, kind="random", seed=seed)
+
+    @classmethod
+    def greedy(cls, name: str = "greedy") -> "MatchAgent":
+        """``GreedyAgent``: the first step of the cheapest path to the nearest cheese."""
+        return cls(name=name, kind="greedy")
+
+    @classmethod
+    def nn(cls, checkpoint: str | Path, temperature: float = 0.0, name: str | None = None, seed: int = 0) -> "MatchAgent":
+        """``NNAgentConfig``: the network's policy without a search. One simulation on a fresh tree evaluates the root
+        and visits no child, so the search returns the network's prior on the position's outcomes."""
+        return cls(name=name if name is not None else "nn", checkpoint=checkpoint, simulations=1, batch_size=1,
+                   noise_epsilon=0.0, seed=seed, temperature=temperature)
 
     @classmethod
     def from_config(cls, mcts_config: Any, checkpoint: str | Path | None = None, name: str | None = None,
                     seed: int = 0) -> "MatchAgent":
         """From a ``RustMCTSConfig`` (``alpharat/mcts/config.py:69-90``) or anything with the same attributes, as
-        ``HipSearcher.from_config``."""
+        ``HipSearcher.from_config``. The temperature is 1.0 (searcher_agent.py:53-54)."""
         kw = {n: getattr(mcts_config, n) for n in ("simulations", "batch_size") + _SEARCH_FIELDS}
         return cls(name=name if name is not None else f"mcts_{kw['simulations']}", checkpoint=checkpoint, seed=seed, **kw)
 
@@ -65,9 +92,11 @@ class MatchAgent:
         return str(cp).encode()
 
     def _c(self) -> _lib.ArMatchAgent:
+        if self.kind not in _KINDS:
+            raise ValueError(f"agent {self.name!r}: unknown kind {self.kind!r} (one of {', '.join(_KINDS)})")
         cfg = _lib.ArSearchConfig(*[getattr(self, n) for n in _SEARCH_FIELDS])
         return _lib.ArMatchAgent(self._weights(), int(self.simulations), int(self.batch_size), cfg,
-                                 int(self.seed) & 0xFFFFFFFFFFFFFFFF)
+                                 int(self.seed) & 0xFFFFFFFFFFFFFFFF, _KINDS[self.kind], float(self.temperature))
 
 
 @dataclass
@@ -172,3 +201,47 @@ def play_match(agent_a: MatchAgent, agent_b: MatchAgent, *, width: int, height: 
         nn_evals_a=int(out.nn_evals_a), nn_evals_b=int(out.nn_evals_b), terminals_a=int(out.terminals_a),
         terminals_b=int(out.terminals_b), collisions_a=int(out.collisions_a), collisions_b=int(out.collisions_b),
         elapsed_secs=float(out.elapsed_secs), games=games)
+
+
+def standard_agents(checkpoint: str | Path, mcts_config: Any, baseline_checkpoint: str | Path | None = None,
+                    seed: int = 0) -> dict[str, MatchAgent]:
+    """The agent set of ``build_standard_agents`` (benchmark.py:78-125) under its names: ``random``, ``greedy``, ``mcts``
+    (the search without a network), ``nn`` (the network alone, temperature 1.0), ``mcts+nn``, and ``nn-prev`` /
+    ``mcts+nn-prev`` for a ``baseline_checkpoint``. Dirichlet noise is stripped (``for_evaluation()``); every agent's
+    stream base is ``seed`` plus its own offset, so no two agents share a stream."""
+    import dataclasses
+
+    def base(k: int) -> int:
+        return (int(seed) + (k << 40)) & 0xFFFFFFFFFFFFFFFF
+
+    def searcher(name: str, cp, k: int) -> MatchAgent:
+        return dataclasses.replace(MatchAgent.from_config(mcts_config, checkpoint=cp, name=name, seed=base(k)), noise_epsilon=0.0)
+
+    agents = {
+        "random": MatchAgent.random(seed=base(1)),
+        "greedy": dataclasses.replace(MatchAgent.greedy(), seed=base(0)),  # (a greedy agent draws nothing)
+        "mcts": searcher("mcts", None, 2),
+        "nn": MatchAgent.nn(checkpoint, temperature=1.0, name="nn", seed=base(3)),
+        "mcts+nn": searcher("mcts+nn", checkpoint, 4),
+    }
+    if baseline_checkpoint is not None:
+        agents["nn-prev"] = MatchAgent.nn(baseline_checkpoint, temperature=1.0, name="nn-prev", seed=base(5))
+        agents["mcts+nn-prev"] = searcher("mcts+nn-prev", baseline_checkpoint, 6)
+    return agents
+
+
+def play_round_robin(agents: dict[str, MatchAgent], *, games_per_matchup: int, **game_and_run_arguments: Any
+                     ) -> dict[tuple[str, str], MatchResult]:
+    """One ``play_match`` per unordered pair of ``agents``, pairs in insertion order, ``games_per_matchup`` games each
+    with ``swap_sides=True``; every pair plays the same games (the arguments of ``play_match`` are passed on as they
+    are). Returns ``{(name_a, name_b): MatchResult}``."""
+    for k in ("num_games", "swap_sides"):
+        if k in game_and_run_arguments:
+            raise TypeError(f"play_round_robin sets {k} itself")
+    names = list(agents)
+    out: dict[tuple[str, str], MatchResult] = {}
+    for i, na in enumerate(names):
+        for nb in names[i + 1:]:
+            out[(na, nb)] = play_match(agents[na], agents[nb], num_games=games_per_matchup, swap_sides=True,
+                                       **game_and_run_arguments)
+    return out

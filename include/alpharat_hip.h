@@ -258,12 +258,29 @@ int ar_selfplay_info(const ArSelfPlaySession* session, ArSessionInfo* out);
  * agent searches the position on a fresh tree with its own evaluator, budget and configuration, drawing from its own
  * stream of this game (seeded rng_seed_base + index once per game, never re-seeded), and then samples its action from
  * the policy of the side it plays with one more draw from that stream (temperature 1.0, searcher_agent.py:53-54).
- * Neither agent's results depend on the other's stream, nor on how many games are resident. */
+ * Neither agent's results depend on the other's stream, nor on how many games are resident.
+ *
+ * Agent kinds (alpharat/eval/benchmark.py:78-125, ai/config.py:64-137): besides a search agent, an agent can be
+ *   AR_AGENT_RANDOM  ai/random_agent.py:17-19: one uniform draw over the five actions per move from its stream;
+ *   AR_AGENT_GREEDY  ai/greedy_agent.py:23-84: the first step of the cheapest path (mud counted) to the nearest cheese,
+ *                    directions tried UP, RIGHT, DOWN, LEFT, ties broken as the reference's (cost, push counter) heap does.
+ * Both move at every turn, in mud or not. Neither has an evaluator, a tree or counters: weights_path must be NULL,
+ * simulations / batch_size / search are ignored, and the agent's ArMatchSearchView rows and ArMatchStats counters are 0.
+ * The reference's pure-network agent (ai/config.py:88-106) is a search agent with simulations = 1, batch_size = 1,
+ * noise_epsilon = 0 and a temperature: the policy of such a search is the network's prior at the root. */
+enum { AR_AGENT_SEARCH = 0, AR_AGENT_RANDOM = 1, AR_AGENT_GREEDY = 2 };
+
 typedef struct ArMatchAgent {
     const char* weights_path; /* NULL = SmartUniform */
     uint32_t simulations, batch_size;
     ArSearchConfig search;
     uint64_t rng_seed_base;
+    /* AR_AGENT_*; 0 (a search agent) is what every caller before these fields existed means */
+    uint32_t kind;
+    /* search agents only (ai/utils.py:26-40): 1.0 samples the policy of the side played as it is; 0.0 takes the first
+     * index of its largest entry and draws nothing; any other value >= 0 samples exp(log(p + 1e-10) / temperature),
+     * normalised, computed in double and rounded to float weights. Must be finite and >= 0. */
+    float temperature;
 } ArMatchAgent;
 
 typedef struct ArMatchParams {
