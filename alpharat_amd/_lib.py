@@ -177,6 +177,12 @@ class ArMatchStats(C.Structure):
 
 ArMatchSink = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(ArMatchGameView))
 
+
+class ArTrainRows(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("observation", "policy_p1", "policy_p2", "value_p1", "value_p2", "action_p1",
+                                          "action_p2", "cheese_outcomes")]
+
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -205,6 +211,15 @@ EXPORTS = {
     "ar_selfplay_info": (C.c_int, [C.c_void_p, C.POINTER(ArSessionInfo)]),
     "ar_match_run": (C.c_int, [C.POINTER(ArMatchParams), ArMatchSink, C.c_void_p, C.POINTER(ArMatchStats)]),
     "ar_write_bundle": (C.c_int, [C.POINTER(ArGameRecordView), C.c_uint32, C.c_char_p]),
+    "ar_rows_open": (C.c_int, [C.c_uint8, C.c_uint8, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]),
+    "ar_rows_add_games": (C.c_int, [C.c_void_p, C.POINTER(ArGameRecordView), C.c_uint32]),
+    "ar_rows_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ar_rows_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "ar_rows_games": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ar_rows_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ArTrainRows)]),
+    "ar_rows_build_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "ar_rows_clear": (C.c_int, [C.c_void_p]),
+    "ar_rows_close": (None, [C.c_void_p]),
 }
 
 _lib = None

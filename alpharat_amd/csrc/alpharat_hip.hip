@@ -34,6 +34,7 @@
 #include "dev_backup16.h"
 #include "dev_match.h"
 #include "dev_agents.h"
+#include "dev_rows.h"
 #include "zig_norm_tables.inc"
 
 using namespace ar;
@@ -992,6 +993,69 @@ __global__ void k_pack_done(Slot<NW>* slots, const uint32_t* done_list, uint32_t
         s.pool_blk = 0;
         s.status = SLOT_EMPTY;
     }
+}
+
+// ---- training rows (dev_rows.h) ------------------------------------------------------------------------------------
+// Where the host puts a drained game in a row set: game `d` of the drain becomes stored game `game`, its positions the
+// rows first_row .. first_row + n_rows.
+struct RowPlace {
+    uint64_t first_row;
+    uint32_t game, n_rows, d, pad;
+};
+
+// Behind k_pack_done, one block per drained game: its staged records, its maze and its header go into the row set, and its
+// cheese outcomes are computed here (the records of an attached run never visit the host for this).
+template <int NW>
+__global__ void k_rows_append(const DoneInfo<NW>* info, const PosRec<NW>* staging, uint32_t max_turns, const Slot<NW>* slots,
+                              const uint8_t* maze_pool, const RowPlace* place, uint32_t n_place, PosRec<NW>* recs,
+                              uint32_t* pos_game, RowGame* games, uint8_t* mazes, uint8_t* outcomes) {
+    if (blockIdx.x >= n_place) return;
+    const RowPlace pl = place[blockIdx.x];
+    const DoneInfo<NW>& di = info[pl.d];
+    const Board b = slots[di.slot].board;
+    const uint32_t hw = (uint32_t)b.width * b.height;
+    const PosRec<NW>* src_recs = staging + (size_t)pl.d * max_turns;
+    const uint32_t words = pl.n_rows * (uint32_t)(sizeof(PosRec<NW>) / 4);
+    const uint32_t* src = (const uint32_t*)src_recs;
+    uint32_t* dst = (uint32_t*)(recs + pl.first_row);
+    for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) dst[w] = src[w];
+    for (uint32_t i = threadIdx.x; i < pl.n_rows; i += blockDim.x) pos_game[pl.first_row + i] = pl.game;
+    const uint32_t* cost = (const uint32_t*)(maze_pool + b.maze_off);
+    uint32_t* maze_dst = (uint32_t*)(mazes + (size_t)pl.game * hw * 4u);
+    for (uint32_t c = threadIdx.x; c < hw; c += blockDim.x) maze_dst[c] = cost[c];
+    rows_game_outcomes<NW>(threadIdx.x, blockDim.x, src_recs, pl.n_rows, di.final_st, (int)hw, outcomes + (size_t)pl.game * hw);
+    if (threadIdx.x == 0) {
+        RowGame g;
+        g.width = b.width;
+        g.height = b.height;
+        g.max_turns = b.max_turns;
+        g.pad = 0;
+        g.final1 = di.final_st.s1;
+        g.final2 = di.final_st.s2;
+        g.game_index = di.game_index;
+        g.n_rows = pl.n_rows;
+        g.first_row = pl.first_row;
+        games[pl.game] = g;
+    }
+}
+
+// Output row row0 + i from stored position rows[row0 + i]: the caller's order is the gather index, so a shuffled training set
+// is written once. One wavefront per row, four rows per block; every output array is contiguous over rows and a wavefront
+// writes consecutive elements of its row (dword stores for the floats, byte stores for the i8 arrays, whose row stride of hw
+// bytes is no multiple of four in general). The kernel is bound by its stores (1.5 KB per 7x7 row); no LDS.
+enum { ROWS_PER_BLOCK = 4, ROWS_PER_LAUNCH = 262144 };
+template <int NW>
+__global__ void __launch_bounds__(ROWS_PER_BLOCK * ROWS_LANES)
+k_rows_build(const PosRec<NW>* recs, const uint32_t* pos_game, const RowGame* games, const uint8_t* mazes,
+             const uint8_t* outcomes, const uint64_t* rows, uint64_t row0, uint32_t n, RowOut out) {
+    const uint32_t i = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const uint64_t r = row0 + i;
+    const uint64_t src = rows[r];
+    const uint32_t gi = pos_game[src];
+    const RowGame& g = games[gi];
+    const size_t hw = (size_t)g.width * g.height;
+    rows_build_row<NW>(threadIdx.x & 63u, recs[src], g, mazes + (size_t)gi * hw * 4u, outcomes + (size_t)gi * hw, out, r);
 }
 
 // arena growth: what a stalled slot reports, and its new home once the host has copied the nodes
@@ -2462,27 +2526,10 @@ void record_from_device(const DoneInfo<NW>& d, const PosRec<NW>* pos, const Host
         r.a1[i] = p.a1;
         r.a2[i] = p.a2;
     }
-    // selfplay.rs:415-471 compute_cheese_outcomes: diff consecutive masks against the next positions
-    r.cheese_outcomes.assign(hw, 2);
-    for (size_t i = 0; i < n; ++i) {
-        const uint8_t* cur = &r.cheese_mask[i * hw];
-        uint8_t n1, n2;
-        std::vector<uint8_t> last_mask;
-        const uint8_t* next;
-        if (i + 1 < n) {
-            next = &r.cheese_mask[(i + 1) * hw];
-            n1 = pos[i + 1].st.p1;
-            n2 = pos[i + 1].st.p2;
-        } else {
-            last_mask.resize(hw);
-            for (int c = 0; c < hw; ++c) last_mask[c] = st_has_cheese(d.final_st, c) ? 1 : 0;
-            next = last_mask.data();
-            n1 = d.final_st.p1;
-            n2 = d.final_st.p2;
-        }
-        for (int c = 0; c < hw; ++c)
-            if (cur[c] == 1 && next[c] == 0) r.cheese_outcomes[c] = (n1 == c && n2 == c) ? 1 : n1 == c ? 0 : n2 == c ? 3 : 2;
-    }
+    // selfplay.rs:415-471 compute_cheese_outcomes: the rule is dev_rows.h rows_cell_outcome, which an attached row set runs on
+    // the device for the same records
+    r.cheese_outcomes.resize(hw);
+    for (int c = 0; c < hw; ++c) r.cheese_outcomes[c] = rows_cell_outcome<NW>(pos, (uint32_t)n, d.final_st, c);
 }
 
 std::string uuid4() {
@@ -2570,6 +2617,275 @@ int parse_device(const char* device, int device_index, int& out) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// row set: finished games kept on the device until their training rows are built (dev_rows.h)
+// ------------------------------------------------------------------------------------------------
+// Position records as the engine leaves them, one RowGame header per game, the game's maze bytes and its cheese outcomes,
+// and the game of every position. Everything is allocated once at open for `capacity` positions (a game has at least one
+// position, so `capacity` games at most); an append that does not fit is refused and changes nothing. The observations are
+// not stored: k_rows_build writes them when rows are asked for. Not thread-safe: one caller at a time, as a session.
+struct RowStore {
+    int device = 0, nw = 1;
+    uint8_t width = 0, height = 0;
+    uint32_t hw = 0;
+    uint64_t capacity = 0, n_pos = 0;
+    bool attached = false;
+    DevBuf<uint8_t> recs, mazes, outcomes;  // PosRec<nw>[capacity], [capacity][hw * 4], [capacity][hw]
+    DevBuf<uint32_t> pos_game;
+    DevBuf<RowGame> games;
+    std::vector<RowGame> h_games;
+    // attached appends: placements of one drain
+    PinBuf<RowPlace> h_place;
+    DevBuf<RowPlace> d_place;
+    uint32_t place_cap = 0;
+    // ar_rows_build: row indices and output rows on the device (kept between calls, grown to the largest request)
+    DevBuf<uint64_t> d_rows;
+    DevBuf<uint8_t> d_out;
+    uint64_t out_rows = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    double build_kernel_ms = 0.0;
+    hipEvent_t ev_append = nullptr;  // behind the last k_rows_append of an attached session, on its stream
+    bool has_append = false;
+    // uploads and builds run on the null stream: they wait for the attached session's last append, nothing else
+    hipError_t wait_appends() const { return has_append ? hipEventSynchronize(ev_append) : hipSuccess; }
+
+    size_t rec_bytes() const { return nw == 1 ? sizeof(PosRec<1>) : sizeof(PosRec<4>); }
+    ~RowStore() {
+        if (ev0) hipEventDestroy(ev0);
+        if (ev1) hipEventDestroy(ev1);
+        if (ev_append) hipEventDestroy(ev_append);
+    }
+    int open(uint8_t w, uint8_t h, uint64_t cap, int dev) {
+        device = dev;
+        width = w;
+        height = h;
+        hw = (uint32_t)w * h;
+        nw = hw <= 64 ? 1 : 4;
+        capacity = cap;
+        HIP_TRY(hipSetDevice(device));
+        if (recs.alloc(cap * rec_bytes()) != hipSuccess || pos_game.alloc(cap) != hipSuccess || games.alloc(cap) != hipSuccess ||
+            mazes.alloc(cap * hw * 4) != hipSuccess || outcomes.alloc(cap * hw) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(AR_E_NOMEM, "not enough device memory for a row set of " + std::to_string(cap) + " positions");
+        }
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventCreateWithFlags(&ev_append, hipEventDisableTiming));
+        return AR_OK;
+    }
+    bool fits(uint64_t positions, uint64_t n_games) const {
+        return n_pos + positions <= capacity && h_games.size() + n_games <= capacity;
+    }
+};
+
+// one host record as the engine's position records (the fields a row is built from, and the search results beside them)
+template <int NW>
+void rows_records_from_view(const ArGameRecordView& v, PosRec<NW>* out) {
+    const uint32_t hw = (uint32_t)v.width * v.height;
+    for (uint32_t i = 0; i < v.n_positions; ++i) {
+        PosRec<NW>& p = out[i];
+        memset(&p, 0, sizeof p);
+        const uint8_t* mask = v.cheese_mask + (size_t)i * hw;
+        for (uint32_t c = 0; c < hw; ++c)
+            if (mask[c]) {
+                p.st.cheese[c >> 6] |= 1ULL << (c & 63u);
+                p.st.remaining += 1;
+            }
+        p.st.s1 = v.p1_score[i];
+        p.st.s2 = v.p2_score[i];
+        p.st.turn = v.turn[i];
+        p.st.p1 = (uint8_t)(v.p1_pos[i * 2 + 1] * v.width + v.p1_pos[i * 2]);
+        p.st.p2 = (uint8_t)(v.p2_pos[i * 2 + 1] * v.width + v.p2_pos[i * 2]);
+        p.st.m1 = v.p1_mud[i];
+        p.st.m2 = v.p2_mud[i];
+        memcpy(p.res.policy[0], v.policy_p1 + (size_t)i * 5, 20);
+        memcpy(p.res.policy[1], v.policy_p2 + (size_t)i * 5, 20);
+        if (v.value_p1) p.res.value[0] = v.value_p1[i];
+        if (v.value_p2) p.res.value[1] = v.value_p2[i];
+        if (v.visit_counts_p1) memcpy(p.res.visit_counts[0], v.visit_counts_p1 + (size_t)i * 5, 20);
+        if (v.visit_counts_p2) memcpy(p.res.visit_counts[1], v.visit_counts_p2 + (size_t)i * 5, 20);
+        if (v.prior_p1) memcpy(p.res.prior[0], v.prior_p1 + (size_t)i * 5, 20);
+        if (v.prior_p2) memcpy(p.res.prior[1], v.prior_p2 + (size_t)i * 5, 20);
+        p.a1 = v.action_p1[i];
+        p.a2 = v.action_p2[i];
+    }
+}
+
+// ar_rows_add_games: host records (bundles read back, or a sink's) go to the tail of the store with plain copies; the
+// games' cheese outcomes are the view's
+template <int NW>
+int rows_add_games(RowStore& R, const ArGameRecordView* gs, uint32_t n) {
+    uint64_t positions = 0, n_games = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const ArGameRecordView& v = gs[k];
+        if (v.width != R.width || v.height != R.height)
+            return fail(AR_E_INVALID, "the row set holds " + std::to_string(R.width) + "x" + std::to_string(R.height) +
+                                          " games, this one is " + std::to_string(v.width) + "x" + std::to_string(v.height));
+        if (v.n_positions == 0) continue;
+        if (!v.maze || !v.cheese_outcomes || !v.cheese_mask || !v.p1_pos || !v.p2_pos || !v.p1_score || !v.p2_score ||
+            !v.p1_mud || !v.p2_mud || !v.turn || !v.policy_p1 || !v.policy_p2 || !v.action_p1 || !v.action_p2)
+            return fail(AR_E_INVALID, "a game record lacks an array the rows are built from");
+        positions += v.n_positions;
+        n_games += 1;
+    }
+    if (!R.fits(positions, n_games))
+        return fail(AR_E_NOMEM, "the row set is full: " + std::to_string(R.n_pos) + " + " + std::to_string(positions) +
+                                    " positions, capacity " + std::to_string(R.capacity));
+    if (positions == 0) return AR_OK;
+    const uint32_t hw = R.hw;
+    std::vector<PosRec<NW>> recs(positions);
+    std::vector<uint32_t> pos_game(positions);
+    std::vector<RowGame> hdr;
+    std::vector<uint8_t> mazes(n_games * hw * 4), outcomes(n_games * hw);
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const ArGameRecordView& v = gs[k];
+        if (v.n_positions == 0) continue;
+        const size_t j = hdr.size();
+        rows_records_from_view<NW>(v, recs.data() + at);
+        for (uint32_t i = 0; i < v.n_positions; ++i) pos_game[at + i] = (uint32_t)(R.h_games.size() + j);
+        for (uint32_t b = 0; b < hw * 4; ++b) mazes[j * hw * 4 + b] = v.maze[b] > 0 ? (uint8_t)v.maze[b] : (uint8_t)0;
+        memcpy(&outcomes[j * hw], v.cheese_outcomes, hw);
+        RowGame g;
+        g.width = v.width;
+        g.height = v.height;
+        g.max_turns = v.max_turns;
+        g.pad = 0;
+        g.final1 = v.final_p1_score;
+        g.final2 = v.final_p2_score;
+        g.game_index = v.game_index;
+        g.n_rows = v.n_positions;
+        g.first_row = R.n_pos + at;
+        hdr.push_back(g);
+        at += v.n_positions;
+    }
+    HIP_TRY(hipSetDevice(R.device));
+    HIP_TRY(R.wait_appends());
+    const size_t g0 = R.h_games.size();
+    HIP_TRY(hipMemcpy(R.recs.p + R.n_pos * sizeof(PosRec<NW>), recs.data(), positions * sizeof(PosRec<NW>), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(R.pos_game.p + R.n_pos, pos_game.data(), positions * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(R.games.p + g0, hdr.data(), hdr.size() * sizeof(RowGame), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(R.mazes.p + g0 * hw * 4, mazes.data(), mazes.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(R.outcomes.p + g0 * hw, outcomes.data(), outcomes.size(), hipMemcpyHostToDevice));
+    R.h_games.insert(R.h_games.end(), hdr.begin(), hdr.end());
+    R.n_pos += positions;
+    return AR_OK;
+}
+
+// the drained games of an attached session, in the order of the drain: k_rows_append on the engine's stream, behind
+// k_pack_done and in front of whatever overwrites the staging buffers next
+template <int NW>
+int rows_append_done(RowStore& R, const DoneInfo<NW>* h_info, const DoneInfo<NW>* d_info, const PosRec<NW>* staging,
+                     uint32_t n_done, uint32_t max_turns, const Slot<NW>* slots, const uint8_t* maze_pool, hipStream_t stream) {
+    uint64_t positions = 0;
+    uint32_t n_place = 0;
+    if (n_done > R.place_cap) return fail(AR_E_INVALID, "more games drained than the session has slots");
+    for (uint32_t d = 0; d < n_done; ++d) {
+        const uint32_t n = h_info[d].n_pos < max_turns ? h_info[d].n_pos : max_turns;
+        if (n == 0) continue;
+        RowPlace& pl = R.h_place.p[n_place];
+        pl.first_row = R.n_pos + positions;
+        pl.game = (uint32_t)R.h_games.size() + n_place;
+        pl.n_rows = n;
+        pl.d = d;
+        pl.pad = 0;
+        positions += n;
+        n_place += 1;
+    }
+    if (!R.fits(positions, n_place))
+        return fail(AR_E_NOMEM, "the attached row set is full: " + std::to_string(R.n_pos) + " + " + std::to_string(positions) +
+                                    " positions, capacity " + std::to_string(R.capacity));
+    if (n_place == 0) return AR_OK;
+    HIP_TRY(hipMemcpyAsync(R.d_place.p, R.h_place.p, sizeof(RowPlace) * n_place, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_rows_append<NW>, dim3(n_place), dim3(128), 0, stream, d_info, staging, max_turns, slots, maze_pool,
+                       (const RowPlace*)R.d_place.p, n_place, (PosRec<NW>*)R.recs.p, R.pos_game.p, R.games.p, R.mazes.p,
+                       R.outcomes.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(R.ev_append, stream));
+    R.has_append = true;
+    for (uint32_t j = 0; j < n_place; ++j) {
+        const RowPlace& pl = R.h_place.p[j];
+        const DoneInfo<NW>& di = h_info[pl.d];
+        RowGame g;
+        g.width = R.width;
+        g.height = R.height;
+        g.max_turns = (uint16_t)max_turns;
+        g.pad = 0;
+        g.final1 = di.final_st.s1;
+        g.final2 = di.final_st.s2;
+        g.game_index = di.game_index;
+        g.n_rows = pl.n_rows;
+        g.first_row = pl.first_row;
+        R.h_games.push_back(g);
+    }
+    R.n_pos += positions;
+    // the placements are read by the copy above when the stream gets there: the pinned buffer is written again only after
+    // the next drain, which waits for the stream
+    return AR_OK;
+}
+
+template <int NW>
+int rows_build(RowStore& R, const uint64_t* rows, uint64_t n, const ArTrainRows& o) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (rows[i] >= R.n_pos)
+            return fail(AR_E_INVALID, "row " + std::to_string(i) + " asks for position " + std::to_string(rows[i]) +
+                                          ", the set holds " + std::to_string(R.n_pos));
+    R.build_kernel_ms = 0.0;
+    if (n == 0) return AR_OK;
+    HIP_TRY(hipSetDevice(R.device));
+    HIP_TRY(R.wait_appends());
+    const size_t hw = R.hw, obs = rows_obs_dim(R.hw);
+    // the eight arrays behind each other in one allocation, the float arrays first (4-byte aligned)
+    const size_t off_obs = 0, off_p1 = off_obs + n * obs * 4, off_p2 = off_p1 + n * 20, off_v1 = off_p2 + n * 20,
+                 off_v2 = off_v1 + n * 4, off_a1 = off_v2 + n * 4, off_a2 = off_a1 + n, off_co = off_a2 + n,
+                 total = off_co + n * hw;
+    if (n > R.out_rows) {
+        if (R.d_rows.p) HIP_TRY(hipFree(R.d_rows.p));
+        if (R.d_out.p) HIP_TRY(hipFree(R.d_out.p));
+        R.d_rows.p = nullptr;
+        R.d_out.p = nullptr;
+        R.out_rows = 0;
+        if (R.d_rows.alloc(n) != hipSuccess || R.d_out.alloc(total) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(AR_E_NOMEM, "not enough device memory for " + std::to_string(n) + " output rows");
+        }
+        R.out_rows = n;
+    }
+    uint8_t* base = R.d_out.p;
+    RowOut out;
+    out.observation = (float*)(base + off_obs);
+    out.policy_p1 = (float*)(base + off_p1);
+    out.policy_p2 = (float*)(base + off_p2);
+    out.value_p1 = (float*)(base + off_v1);
+    out.value_p2 = (float*)(base + off_v2);
+    out.action_p1 = (int8_t*)(base + off_a1);
+    out.action_p2 = (int8_t*)(base + off_a2);
+    out.cheese_outcomes = (int8_t*)(base + off_co);
+    HIP_TRY(hipMemcpy(R.d_rows.p, rows, n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipEventRecord(R.ev0, nullptr));
+    for (uint64_t row0 = 0; row0 < n; row0 += ROWS_PER_LAUNCH) {
+        const uint32_t cnt = (uint32_t)(n - row0 < (uint64_t)ROWS_PER_LAUNCH ? n - row0 : (uint64_t)ROWS_PER_LAUNCH);
+        hipLaunchKernelGGL(k_rows_build<NW>, dim3((cnt + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(ROWS_PER_BLOCK * ROWS_LANES), 0,
+                           nullptr, (const PosRec<NW>*)R.recs.p, (const uint32_t*)R.pos_game.p, (const RowGame*)R.games.p,
+                           (const uint8_t*)R.mazes.p, (const uint8_t*)R.outcomes.p, (const uint64_t*)R.d_rows.p, row0, cnt, out);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(R.ev1, nullptr));
+    HIP_TRY(hipEventSynchronize(R.ev1));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, R.ev0, R.ev1));
+    R.build_kernel_ms = ms;
+    HIP_TRY(hipMemcpy(o.observation, out.observation, n * obs * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(o.policy_p1, out.policy_p1, n * 20, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(o.policy_p2, out.policy_p2, n * 20, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(o.value_p1, out.value_p1, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(o.value_p2, out.value_p2, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(o.action_p1, out.action_p1, n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(o.action_p2, out.action_p2, n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(o.cheese_outcomes, out.cheese_outcomes, n * hw, hipMemcpyDeviceToHost));
+    return AR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // self-play driver
 // ------------------------------------------------------------------------------------------------
 // A self-play run as an object that outlives one call: the engine, its resident games and the supply of
@@ -2582,6 +2898,7 @@ struct SessionBase {
     virtual void info(ArSessionInfo* out) const = 0;
     virtual int step(uint32_t batch_steps, ArSelfPlayStats* window, int* finished_out) = 0;
     virtual int close(ArSelfPlayStats* total) = 0;
+    virtual int attach_rows(RowStore* rows) = 0;
 };
 
 template <int NW>
@@ -2609,6 +2926,34 @@ struct SelfPlaySession : SessionBase {
     std::string err;
     bool timing = false, failed = false;
     double tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    RowStore* rows = nullptr;  // attached row set: every drained game is appended to it on the device
+    int device_id = 0;
+
+    int attach_rows(RowStore* r) override {
+        if (rows) return fail(AR_E_INVALID, "the session already has a row set");
+        if (r->attached) return fail(AR_E_INVALID, "the row set is already attached to a session");
+        if (eng.steps != 0 || finished != 0) return fail(AR_E_INVALID, "a row set is attached before the session's first step");
+        if (r->width != p.width || r->height != p.height)
+            return fail(AR_E_INVALID, "the row set holds " + std::to_string(r->width) + "x" + std::to_string(r->height) +
+                                          " games, the session plays " + std::to_string(p.width) + "x" + std::to_string(p.height));
+        if (r->device != device_id) return fail(AR_E_INVALID, "the row set and the session are on different devices");
+        if (S > r->place_cap) {  // (kept from an earlier session when large enough)
+            HIP_TRY(hipSetDevice(device_id));
+            if (r->h_place.p) HIP_TRY(hipHostFree(r->h_place.p));
+            if (r->d_place.p) HIP_TRY(hipFree(r->d_place.p));
+            r->h_place.p = nullptr;
+            r->d_place.p = nullptr;
+            r->place_cap = 0;
+            if (r->h_place.alloc(S) != hipSuccess || r->d_place.alloc(S) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(AR_E_NOMEM, "no memory for the row set's placement buffers");
+            }
+            r->place_cap = S;
+        }
+        r->attached = true;
+        rows = r;
+        return AR_OK;
+    }
 
     void info(ArSessionInfo* out) const override {
         out->resident_games = S;
@@ -2707,6 +3052,7 @@ struct SelfPlaySession : SessionBase {
         progress = prog;
         sink = sk;
         sink_user = sk_user;
+        device_id = device;
         memset(&st, 0, sizeof st);
         st.min_turns = 0xFFFFFFFFu;
         cfg = to_cfg(p.search, p.simulations, p.batch_size);
@@ -2941,6 +3287,9 @@ struct SelfPlaySession : SessionBase {
             if (c[0]) {
                 const uint32_t n_done = c[0];
                 if ((rc = eng.drain(n_done)) != AR_OK) break;
+                if (rows && (rc = rows_append_done<NW>(*rows, eng.h_info.p, eng.info.p, eng.staging.p, n_done, eng.max_turns,
+                                                       eng.slots.p, eng.maze.p, eng.stream)) != AR_OK)
+                    break;
                 tm[5] += since(tp);
                 tp = now();
                 std::vector<uint32_t> free_slots;
@@ -3004,6 +3353,11 @@ struct SelfPlaySession : SessionBase {
     // closed with games in flight simply drops them, like a sampler that is interrupted).
     int close(ArSelfPlayStats* total) override {
         int rc = AR_OK;
+        if (rows) {  // the row set is the caller's again (its appends are done: it may be attached to the next session)
+            if (eng.stream) (void)hipStreamSynchronize(eng.stream);
+            rows->attached = false;
+            rows = nullptr;
+        }
         if (to_disk) {
             writer.finish();
             to_disk = false;
@@ -3648,6 +4002,11 @@ struct ArSelfPlaySession {
     }
 };
 
+struct ArRowSet {
+    RowStore* impl = nullptr;
+    ~ArRowSet() { delete impl; }
+};
+
 // ------------------------------------------------------------------------------------------------
 // C-ABI
 // ------------------------------------------------------------------------------------------------
@@ -3846,6 +4205,76 @@ int ar_selfplay_run(const ArSelfPlayParams* p, ArProgress* progress, ArGameSink 
     if (rc != AR_OK) return fail(rc, msg);
     return rc2;
 }
+
+// ---- training rows: alpharat/data/sharding.py:513-595 on the device (dev_rows.h) --------------------------------
+int ar_rows_open(uint8_t width, uint8_t height, uint64_t capacity_positions, int device, ArRowSet** out) {
+    if (!out) return fail(AR_E_INVALID, "null argument");
+    *out = nullptr;
+    if (width == 0 || height == 0 || (int)width * height > 256) return fail(AR_E_INVALID, "board must have 1..256 cells");
+    if (capacity_positions > 0xFFFFFFFFull) return fail(AR_E_INVALID, "a row set holds at most 2^32 - 1 positions");
+    int dev = 0;
+    if (int rc = parse_device("hip", device, dev)) return rc;
+    std::unique_ptr<ArRowSet> s(new ArRowSet());
+    s->impl = new RowStore();
+    if (int rc = s->impl->open(width, height, capacity_positions, dev)) return rc;
+    *out = s.release();
+    return AR_OK;
+}
+
+int ar_rows_add_games(ArRowSet* s, const ArGameRecordView* games, uint32_t n) {
+    if (!s || !s->impl || (!games && n)) return fail(AR_E_INVALID, "null argument");
+    return s->impl->nw == 1 ? rows_add_games<1>(*s->impl, games, n) : rows_add_games<4>(*s->impl, games, n);
+}
+
+int ar_rows_attach(ArRowSet* s, ArSelfPlaySession* session) {
+    if (!s || !s->impl || !session || !session->impl) return fail(AR_E_INVALID, "null argument");
+    return session->impl->attach_rows(s->impl);
+}
+
+int ar_rows_count(const ArRowSet* s, uint32_t* games, uint64_t* positions) {
+    if (!s || !s->impl) return fail(AR_E_INVALID, "null argument");
+    if (games) *games = (uint32_t)s->impl->h_games.size();
+    if (positions) *positions = s->impl->n_pos;
+    return AR_OK;
+}
+
+int ar_rows_games(const ArRowSet* s, uint32_t* game_index, uint64_t* first_row, uint32_t* n_rows) {
+    if (!s || !s->impl) return fail(AR_E_INVALID, "null argument");
+    const std::vector<RowGame>& g = s->impl->h_games;
+    for (size_t i = 0; i < g.size(); ++i) {
+        if (game_index) game_index[i] = g[i].game_index;
+        if (first_row) first_row[i] = g[i].first_row;
+        if (n_rows) n_rows[i] = g[i].n_rows;
+    }
+    return AR_OK;
+}
+
+int ar_rows_build(ArRowSet* s, const uint64_t* rows, uint64_t n, const ArTrainRows* out) {
+    if (!s || !s->impl) return fail(AR_E_INVALID, "null argument");
+    if (n == 0) {
+        s->impl->build_kernel_ms = 0.0;
+        return AR_OK;
+    }
+    if (!rows || !out || !out->observation || !out->policy_p1 || !out->policy_p2 || !out->value_p1 || !out->value_p2 ||
+        !out->action_p1 || !out->action_p2 || !out->cheese_outcomes)
+        return fail(AR_E_INVALID, "null argument");
+    return s->impl->nw == 1 ? rows_build<1>(*s->impl, rows, n, *out) : rows_build<4>(*s->impl, rows, n, *out);
+}
+
+int ar_rows_build_time(const ArRowSet* s, double* kernel_ms) {
+    if (!s || !s->impl || !kernel_ms) return fail(AR_E_INVALID, "null argument");
+    *kernel_ms = s->impl->build_kernel_ms;
+    return AR_OK;
+}
+
+int ar_rows_clear(ArRowSet* s) {
+    if (!s || !s->impl) return fail(AR_E_INVALID, "null argument");
+    s->impl->h_games.clear();
+    s->impl->n_pos = 0;
+    return AR_OK;
+}
+
+void ar_rows_close(ArRowSet* s) { delete s; }
 
 // ---- matches: tournament.py:329-373 / eval/game.py:47-87 / searcher_agent.py:40-56 on the device --------------
 int ar_match_run(const ArMatchParams* p, ArMatchSink sink, void* sink_user, ArMatchStats* out) {

@@ -25,6 +25,7 @@
 
 #include "../../include/alpharat_hip.h"
 #include "dev_search.h"
+#include "dev_rows.h"
 
 static int nets_fail(int code, const std::string& msg);
 
@@ -1092,22 +1093,8 @@ __global__ void k_encode(const ar::LeafReq<NW>* q, uint32_t n, const ar::Board* 
     const ar::Board& b = boards[q[i].slot];
     const int hw = b.width * b.height;
     const uint8_t* cost = maze_pool + b.maze_off;
-    float* o = obs + (size_t)i * obs_stride;
-    for (int k = threadIdx.x; k < hw * 4; k += blockDim.x) o[k] = cost[k] ? (float)cost[k] / 10.0f : -1.0f;
-    for (int k = threadIdx.x; k < hw; k += blockDim.x) {
-        o[hw * 4 + k] = k == st.p1 ? 1.0f : 0.0f;
-        o[hw * 5 + k] = k == st.p2 ? 1.0f : 0.0f;
-        o[hw * 6 + k] = ar::st_has_cheese(st, k) ? 1.0f : 0.0f;
-    }
-    if (threadIdx.x == 0) {
-        float* s = o + hw * 7;
-        s[0] = st.s1 - st.s2;
-        s[1] = b.max_turns > 0 ? (float)st.turn / (float)b.max_turns : 0.0f;
-        s[2] = (float)st.m1 / 10.0f;
-        s[3] = (float)st.m2 / 10.0f;
-        s[4] = st.s1 / 10.0f;
-        s[5] = st.s2 / 10.0f;
-    }
+    // (the text is dev_rows.h flat_observation: the training rows are built by the same one)
+    ar::flat_observation<NW>(threadIdx.x, blockDim.x, st, hw, b.max_turns, cost, obs + (size_t)i * obs_stride);
 }
 
 }  // namespace arnet

@@ -274,6 +274,20 @@ class SelfPlaySession:
         self.finished = bool(fin.value)
         return SelfPlayStats(out)
 
+    def attach_rows(self, rowset) -> None:
+        """Before the first ``step``: every game this session finishes is appended to ``rowset`` (alpharat_amd.shards.RowSet)
+        on the device, cheese outcomes included, for ``shards.prepare_training_set_with_split(None, ..., rowset=rowset)``.
+        Needs a finite ``num_games``; a set of ``num_games * max_turns`` positions cannot fill up. Close the session before
+        the row set."""
+        if not self._h:
+            raise RuntimeError("session is closed")
+        if self._unbounded:
+            raise ValueError("attach_rows needs a finite num_games: a row set has a fixed capacity")
+        from .shards import _attach
+
+        _attach(rowset, self)
+        self._rows = rowset  # (kept alive as long as the session may append to it)
+
     def run_to_end(self) -> SelfPlayStats:
         if self._unbounded:
             raise ValueError("a session with an endless supply of games (num_games=UNBOUNDED) has no end: use step(n)")

@@ -1,0 +1,328 @@
+"""Training shards from self-play records, built on the MI355X.
+
+``prepare_training_set_with_split`` / ``prepare_training_set`` follow the reference's sharding step
+(alpharat/data/sharding.py:73-385): games are split into train and val, the positions of each split are shuffled, and
+``shard_NNNN.npz`` files with the eight ``BatchKey`` arrays (alpharat/nn/training/keys.py:52-62) are written beside a
+``manifest.json``. Where the reference builds every row in a Python loop (``FlatObservationBuilder.build`` and
+``build_targets`` once per position), the rows here come from ``ar_rows_build``: the games sit in a device-resident
+``RowSet`` -- appended on the device by a session the set is attached to, or uploaded from records and bundles -- and the
+shuffle is the gather index of the kernel that writes the rows.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import uuid
+import weakref
+from dataclasses import dataclass
+from datetime import datetime, timezone
+from pathlib import Path
+from typing import Callable, Sequence
+
+import numpy as np
+
+from . import _lib
+
+KEYS = ("observation", "policy_p1", "policy_p2", "value_p1", "value_p2", "action_p1", "action_p2", "cheese_outcomes")
+BUILDER_VERSION = "flat_v2"  # alpharat/nn/builders/flat.py:117-120
+
+# the 26 arrays of a bundle (crates/alpharat-sampling/src/recording.rs:23-162): per game, then per position
+_BUNDLE_GAME = ("maze", "initial_cheese", "cheese_outcomes", "max_turns", "result", "final_p1_score", "final_p2_score")
+_BUNDLE_POS = ("p1_pos", "p2_pos", "p1_score", "p2_score", "p1_mud", "p2_mud", "cheese_mask", "turn", "value_p1", "value_p2",
+               "visit_counts_p1", "visit_counts_p2", "prior_p1", "prior_p2", "policy_p1", "policy_p2", "action_p1",
+               "action_p2")
+_U8 = ("p1_pos", "p2_pos", "p1_mud", "p2_mud", "cheese_mask", "action_p1", "action_p2")
+_F32 = ("p1_score", "p2_score", "value_p1", "value_p2", "visit_counts_p1", "visit_counts_p2", "prior_p1", "prior_p2",
+        "policy_p1", "policy_p2")
+
+
+def read_bundle(path) -> list[dict]:
+    """The games of one ``bundle_<uuid>.npz`` in file order, as record dicts (the keys of ``sampling.record_to_dict``;
+    a bundle carries no game index: ``game_index`` is absent)."""
+    with np.load(path) as z:
+        if "game_lengths" not in z.files:  # the reference's single-game files (sharding.py:435-436) are not read here
+            raise ValueError(f"{path} is not a bundle (no game_lengths array): only bundle_<uuid>.npz files are read")
+        a = {k: z[k] for k in z.files}
+    lengths = a["game_lengths"]
+    h, w = a["maze"].shape[1:3]
+    ends = np.cumsum(lengths)
+    games = []
+    for i in range(len(lengths)):
+        lo, hi = int(ends[i] - lengths[i]), int(ends[i])
+        g = dict(width=int(w), height=int(h), n=hi - lo)
+        for k in _BUNDLE_GAME:
+            g[k] = a[k][i]
+        for k in _BUNDLE_POS:
+            g[k] = a[k][lo:hi]
+        g["max_turns"], g["result"] = int(g["max_turns"]), int(g["result"])
+        g["cheese_mask"] = g["cheese_mask"].reshape(hi - lo, h * w)
+        games.append(g)
+    return games
+
+
+def read_bundle_dirs(dirs: Sequence) -> list[dict]:
+    """Every game of the bundles under the given batch directories (``<dir>/games/*.npz`` as the reference lays batches
+    out, sharding.py:423-428, else ``<dir>/*.npz``), directories in the order given, files by name."""
+    games: list[dict] = []
+    for d in dirs:
+        d = Path(d)
+        src = d / "games" if (d / "games").is_dir() else d
+        for f in sorted(src.glob("*.npz")):
+            games.extend(read_bundle(f))
+    return games
+
+
+def _view_of(game: dict, keep: list) -> _lib.ArGameRecordView:
+    v = _lib.ArGameRecordView()
+    v.width, v.height, v.max_turns = int(game["width"]), int(game["height"]), int(game["max_turns"])
+    v.game_index = int(game.get("game_index", 0))
+    v.n_positions = len(np.asarray(game["turn"]))
+    v.final_p1_score, v.final_p2_score = float(game["final_p1_score"]), float(game["final_p2_score"])
+    v.result = int(game.get("result", 0))
+
+    def ptr(key, dt, ct):
+        a = np.array(game[key], dtype=dt, order="C", copy=True)
+        keep.append(a)
+        return a.ctypes.data_as(C.POINTER(ct))
+
+    v.maze = ptr("maze", np.int8, C.c_int8)
+    v.initial_cheese = ptr("initial_cheese", np.uint8, C.c_uint8)
+    v.cheese_outcomes = ptr("cheese_outcomes", np.uint8, C.c_uint8)
+    for k in _U8:
+        setattr(v, k, ptr(k, np.uint8, C.c_uint8))
+    v.turn = ptr("turn", np.uint16, C.c_uint16)
+    for k in _F32:
+        setattr(v, k, ptr(k, np.float32, C.c_float))
+    return v
+
+
+class RowSet:
+    """ctypes mirror of ``ArRowSet`` (include/alpharat_hip.h): finished games kept on the device until their training rows
+    are built. ``capacity_positions`` is fixed here and allocated once; an append that does not fit raises ``MemoryError``
+    and changes nothing. For a session, size it ``num_games * max_turns``: an upper bound, so an attached run never fills it.
+    """
+
+    def __init__(self, width: int, height: int, capacity_positions: int, device_index: int = 0) -> None:
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        self._session = None
+        _lib.check(_lib.load().ar_rows_open(self.width, self.height, int(capacity_positions), int(device_index),
+                                            C.byref(self._h)))
+
+    def _handle(self):
+        if not self._h:
+            raise RuntimeError("row set is closed")
+        return self._h
+
+    def add_games(self, games: Sequence[dict]) -> None:
+        """Host records (sink dicts, or ``read_bundle`` games) to the tail of the set, in the order given."""
+        if not games:
+            return
+        keep: list = []
+        views = (_lib.ArGameRecordView * len(games))(*[_view_of(g, keep) for g in games])
+        _lib.check(_lib.load().ar_rows_add_games(self._handle(), views, len(games)))
+
+    def count(self) -> tuple[int, int]:
+        g, p = C.c_uint32(0), C.c_uint64(0)
+        _lib.check(_lib.load().ar_rows_count(self._handle(), C.byref(g), C.byref(p)))
+        return int(g.value), int(p.value)
+
+    def games(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(game_index, first_row, n_rows) of every stored game, in append order."""
+        n = self.count()[0]
+        gi, fr, nr = np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+        _lib.check(_lib.load().ar_rows_games(self._handle(), gi.ctypes.data, fr.ctypes.data, nr.ctypes.data))
+        return gi, fr, nr
+
+    def build(self, rows) -> dict:
+        """Output row i from stored position ``rows[i]``: the eight arrays of a shard, ``len(rows)`` rows each."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        n, w, h = len(rows), self.width, self.height
+        out = dict(observation=np.empty((n, w * h * 7 + 6), np.float32), policy_p1=np.empty((n, 5), np.float32),
+                   policy_p2=np.empty((n, 5), np.float32), value_p1=np.empty(n, np.float32), value_p2=np.empty(n, np.float32),
+                   action_p1=np.empty(n, np.int8), action_p2=np.empty(n, np.int8), cheese_outcomes=np.empty((n, h, w), np.int8))
+        ptrs = _lib.ArTrainRows(*[out[k].ctypes.data for k in KEYS])
+        _lib.check(_lib.load().ar_rows_build(self._handle(), rows.ctypes.data, n, C.byref(ptrs)))
+        return out
+
+    def build_kernel_ms(self) -> float:
+        """Time inside the kernels of the last ``build`` (HIP events)."""
+        ms = C.c_double(0.0)
+        _lib.check(_lib.load().ar_rows_build_time(self._handle(), C.byref(ms)))
+        return float(ms.value)
+
+    def clear(self) -> None:
+        _lib.check(_lib.load().ar_rows_clear(self._handle()))
+
+    def close(self) -> None:
+        if not self._h:
+            return
+        s = self._session() if self._session is not None else None
+        if s is not None and s._h:
+            raise RuntimeError("close the session this row set is attached to first")
+        h, self._h = self._h, C.c_void_p()
+        _lib.load().ar_rows_close(h)
+
+    def __enter__(self) -> "RowSet":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def _attach(rowset: RowSet, session) -> None:
+    """``SelfPlaySession.attach_rows``: every game the session drains is appended to ``rowset`` on the device."""
+    _lib.check(_lib.load().ar_rows_attach(rowset._handle(), session._h))
+    rowset._session = weakref.ref(session)
+
+
+@dataclass(frozen=True)
+class ShardingResult:  # sharding.py:63-70
+    shard_id: str
+    shard_dir: str
+    total_positions: int
+    train_positions: int
+    val_positions: int
+
+
+RowBuilder = Callable[[np.ndarray], dict]
+
+
+def _listing(games_or_bundle_dirs, rowset, row_builder):
+    """(lengths per game in listing order, row builder over positions numbered through that listing, width, height,
+    source batches, a row set to close afterwards or None)."""
+    src = list(games_or_bundle_dirs) if games_or_bundle_dirs is not None else []
+    own = None
+    batches: list[str] = []
+    if src:
+        if not isinstance(src[0], dict):
+            batches = [f"{Path(d).parent.name}/{Path(d).name}" for d in src]  # experiments/paths.py:134-143
+            src = read_bundle_dirs(src)
+            if not src:
+                raise ValueError("No games found in batch directories")  # sharding.py:438-439
+        lengths = np.array([len(np.asarray(g["turn"])) for g in src], np.int64)
+        w, h = int(src[0]["width"]), int(src[0]["height"])
+        for g in src:
+            if (int(g["width"]), int(g["height"])) != (w, h):  # sharding.py:560-564
+                raise ValueError(f"Dimension mismatch: expected ({w}, {h}), got ({g['width']}, {g['height']})")
+        if row_builder is not None:
+            return lengths, row_builder, w, h, batches, None
+        if rowset is None:
+            rowset = own = RowSet(w, h, max(int(lengths.sum()), 1))
+        try:
+            first = rowset.count()[1]
+            rowset.add_games(src)
+        except BaseException:
+            if own is not None:
+                own.close()
+            raise
+        stored = first + np.arange(int(lengths.sum()), dtype=np.uint64)  # appended in the order given, games of no position skipped
+    elif rowset is not None:
+        gi, fr, nr = rowset.games()
+        order = np.argsort(gi, kind="stable")  # an attached run appends games as they finish: list them by game index
+        lengths = nr[order].astype(np.int64)
+        w, h = rowset.width, rowset.height
+        stored = (np.concatenate([fr[g] + np.arange(nr[g], dtype=np.uint64) for g in order]) if len(order)
+                  else np.zeros(0, np.uint64))
+        if row_builder is not None:
+            return lengths, row_builder, w, h, batches, None
+    else:
+        raise ValueError("batch_dirs cannot be empty")  # sharding.py:121-122, 233-234
+    return lengths, (lambda index: rowset.build(stored[np.asarray(index, np.int64)])), w, h, batches, own
+
+
+def _write_split(out_dir: Path, members, lengths, offsets, row_builder, positions_per_shard, seed, compress, set_id, batches,
+                 w, h) -> int:
+    """sharding.py:303-385 _process_game_refs_to_shards: the split's positions, shuffled, in chunks of positions_per_shard."""
+    pos = (np.concatenate([offsets[g] + np.arange(lengths[g], dtype=np.int64) for g in members]) if len(members)
+           else np.zeros(0, np.int64))
+    total = len(pos)
+    order = pos[np.random.default_rng(seed).permutation(total)]  # :345-346
+    save = np.savez_compressed if compress else np.savez
+    count = 0
+    for start in range(0, total, positions_per_shard):  # :799-819
+        rows = row_builder(order[start:start + positions_per_shard])
+        save(out_dir / f"shard_{count:04d}.npz", **{k: rows[k] for k in KEYS})
+        count += 1
+    manifest = dict(training_set_id=set_id, created_at=datetime.now(timezone.utc).isoformat(), builder_version=BUILDER_VERSION,
+                    source_batches=batches, total_positions=total, shard_count=count, positions_per_shard=positions_per_shard,
+                    width=w, height=h)  # sharding.py:46-60 TrainingSetManifest
+    (out_dir / "manifest.json").write_text(json.dumps(manifest, indent=2))
+    return total
+
+
+def prepare_training_set_with_split(games_or_bundle_dirs, output_dir, *, val_ratio: float = 0.1,
+                                    positions_per_shard: int = 10000, seed: int | None = None,
+                                    rowset: RowSet | None = None, compress: bool = False,
+                                    row_builder: RowBuilder | None = None) -> ShardingResult:
+    """sharding.py:191-300 with the rows built on the device.
+
+    ``games_or_bundle_dirs``: record dicts (``on_game`` / ``read_bundle``) or batch directories holding bundles, taken in
+    the order given and uploaded to ``rowset`` (a set of their size is opened when none is given); or ``None`` with an
+    attached ``rowset``, whose games are taken in increasing ``game_index``. Games are permuted with
+    ``default_rng(seed).permutation`` and the first ``int(total * val_ratio)`` form ``val/``, the rest ``train/``; the
+    positions of a split are permuted with ``default_rng(seed)`` (train) and ``default_rng(seed + 1)`` (val) and built
+    ``positions_per_shard`` at a time. Shards are written stored (``np.savez``); ``compress=True`` gives the reference's
+    ``savez_compressed`` -- ``np.load`` reads both alike. ``row_builder(index) -> the eight arrays`` replaces the device as
+    the source of rows (index numbers the positions through the listed games); it exists so that the file layout can be
+    checked without a device.
+    """
+    if not 0.0 <= val_ratio < 1.0:
+        raise ValueError(f"val_ratio must be in [0.0, 1.0), got {val_ratio}")
+    if positions_per_shard <= 0:
+        raise ValueError("positions_per_shard must be positive")
+    lengths, build, w, h, batches, own = _listing(games_or_bundle_dirs, rowset, row_builder)
+    try:
+        total_games = len(lengths)
+        if total_games == 0:
+            raise ValueError("No games found in batch directories")
+        idx = np.random.default_rng(seed).permutation(total_games)  # :244-246
+        n_val = int(total_games * val_ratio)                        # :248
+        val, train = idx[:n_val], idx[n_val:]
+        # (sharding.py:252-253 raises "No games left for training" here; with val_ratio < 1 and at least one game,
+        # int(total * val_ratio) < total, so that cannot happen: the range check above is what refuses such a ratio)
+        offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+        set_id = str(uuid.uuid4())
+        set_dir = Path(output_dir) / set_id
+        set_dir.mkdir(parents=True, exist_ok=False)
+        (set_dir / "train").mkdir()
+        n_train = _write_split(set_dir / "train", train, lengths, offsets, build, positions_per_shard, seed, compress,
+                               f"{set_id}_train", batches, w, h)
+        n_valp = 0
+        if len(val):  # :278-292
+            (set_dir / "val").mkdir()
+            n_valp = _write_split(set_dir / "val", val, lengths, offsets, build, positions_per_shard,
+                                  seed + 1 if seed is not None else None, compress, f"{set_id}_val", batches, w, h)
+        return ShardingResult(set_id, str(set_dir), n_train + n_valp, n_train, n_valp)
+    finally:
+        if own is not None:
+            own.close()
+
+
+def prepare_training_set(games_or_bundle_dirs, output_dir, *, positions_per_shard: int = 10000, seed: int | None = None,
+                         rowset: RowSet | None = None, compress: bool = False,
+                         row_builder: RowBuilder | None = None) -> Path:
+    """sharding.py:73-188: the same procedure without the split -- every position shuffled with ``default_rng(seed)``,
+    shards and manifest directly under ``output_dir/<training_set_id>``. Returns that directory."""
+    if positions_per_shard <= 0:
+        raise ValueError("positions_per_shard must be positive")
+    lengths, build, w, h, batches, own = _listing(games_or_bundle_dirs, rowset, row_builder)
+    try:
+        if int(lengths.sum()) == 0:
+            raise ValueError("No positions found in batch directories")  # :139-140
+        offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+        set_id = str(uuid.uuid4())
+        set_dir = Path(output_dir) / set_id
+        set_dir.mkdir(parents=True, exist_ok=False)
+        _write_split(set_dir, np.arange(len(lengths)), lengths, offsets, build, positions_per_shard, seed, compress, set_id,
+                     batches, w, h)
+        return set_dir
+    finally:
+        if own is not None:
+            own.close()

@@ -346,6 +346,42 @@ int ar_match_run(const ArMatchParams* params, ArMatchSink sink, void* sink_user,
 /* Bundle writer on its own (recording.rs:23-162 write_bundle): used by the known-answer test. */
 int ar_write_bundle(const ArGameRecordView* games, uint32_t n, const char* path);
 
+/* ---- training rows (alpharat/data/sharding.py:513-595 _process_games_to_arrays: FlatObservationBuilder.build,
+ * nn/builders/flat.py:142-197, and build_targets, nn/targets.py:19-70, once per position) -----------------------------
+ * A row set keeps finished games on the device: their position records as the engine leaves them, a header per game and
+ * the maze bytes; no observations. Its capacity in positions is fixed at open and allocated once; an append that does not
+ * fit returns AR_E_NOMEM and changes nothing. Games come from host records (ar_rows_add_games) or, without visiting the
+ * host, from a session the set is attached to. ar_rows_build writes output row i from stored position rows[i]: the
+ * caller's order (a shuffle) is the gather index. The eight arrays are the BatchKey arrays of a shard
+ * (nn/training/keys.py:52-62), n rows each, in host memory owned by the caller.
+ * One caller at a time; an attached set outlives its session's last step and is closed after the session. */
+typedef struct ArRowSet ArRowSet;
+typedef struct ArTrainRows {
+    float* observation;      /* [n][h*w*7 + 6]  as ar_encode                                                */
+    float* policy_p1;        /* [n][5]                                                                      */
+    float* policy_p2;        /* [n][5]                                                                      */
+    float* value_p1;         /* [n]  final score - score at the position                                    */
+    float* value_p2;         /* [n]                                                                         */
+    int8_t* action_p1;       /* [n]                                                                         */
+    int8_t* action_p2;       /* [n]                                                                         */
+    int8_t* cheese_outcomes; /* [n][h][w]  the game's outcome where the position still has the cheese, else -1 */
+} ArTrainRows;
+int ar_rows_open(uint8_t width, uint8_t height, uint64_t capacity_positions, int device, ArRowSet** out);
+/* host records, from bundles or a sink; the cheese outcomes are the view's. A game of another board size: AR_E_INVALID. */
+int ar_rows_add_games(ArRowSet* set, const ArGameRecordView* games, uint32_t n);
+/* before the session's first step: every game the session drains is appended on the device, cheese outcomes included.
+ * A session that has stepped, a second attach, another board size or device: AR_E_INVALID. */
+int ar_rows_attach(ArRowSet* set, ArSelfPlaySession* session);
+int ar_rows_count(const ArRowSet* set, uint32_t* games, uint64_t* positions);
+/* one entry per stored game, in append order (arrays of ar_rows_count's `games` entries; any may be NULL) */
+int ar_rows_games(const ArRowSet* set, uint32_t* game_index, uint64_t* first_row, uint32_t* n_rows);
+/* rows[n]: stored positions, each below ar_rows_count's `positions` (else AR_E_INVALID); n == 0 succeeds */
+int ar_rows_build(ArRowSet* set, const uint64_t* rows, uint64_t n, const ArTrainRows* out);
+/* time inside the kernels of the last ar_rows_build (HIP events), for measurements */
+int ar_rows_build_time(const ArRowSet* set, double* kernel_ms);
+int ar_rows_clear(ArRowSet* set);
+void ar_rows_close(ArRowSet* set);
+
 #ifdef __cplusplus
 }
 #endif
