@@ -32,6 +32,7 @@
 #include "dev_gather8.h"
 #include "dev_gatherw.h"
 #include "dev_backup16.h"
+#include "dev_advance.h"
 #include "dev_match.h"
 #include "dev_agents.h"
 #include "dev_rows.h"
@@ -180,6 +181,7 @@ __device__ inline void slot_at_pages(Slot<NW>& s, const Bases& B, uint32_t slot,
     s.pool_blk = n;
 }
 // the arena a slot leaves behind: pages go to the return list of their zone, host-grown arenas are flagged
+// (in `s`, the slot as it will be written back; so is the error of a full return list)
 template <int NW>
 __device__ inline void leave_arena(const Slot<NW>& old, Slot<NW>& s, const Bases& B) {
     if (old.pool_blk) {
@@ -187,7 +189,8 @@ __device__ inline void leave_arena(const Slot<NW>& old, Slot<NW>& s, const Bases
         const uint32_t first = (uint32_t)(((unsigned long long)old.stats_off - (unsigned long long)zone * B.pool.zone_bytes) / B.pool.page_bytes);
         const uint32_t at = atomicAdd(&B.pool.ret_n[zone], 1u);
         if (at < B.pool.ret_cap) B.pool.ret[(size_t)zone * B.pool.ret_cap + at] = (unsigned long long)first | ((unsigned long long)old.pool_blk << 32);
-        // (the list holds a run per slot of the zone and then some: more cannot be left between two merges)
+        else s.error = 12;  // (the list holds a run per slot of the zone and then some: more cannot be left between two
+                            // merges. A run that found it full would stay taken for good: the host's scan reports it)
     } else if (old.cap != 0) {
         s.release_grown = 1;
     }
@@ -253,6 +256,7 @@ __global__ void k_init_games(Slot<NW>* slots, const GameInit<NW>* init, uint32_t
     if (s.pool_blk) {
         Slot<NW> unused = s;
         leave_arena(s, unused, B);
+        if (unused.error) s.error = unused.error;
     }
     s.cap = 0;
     s.pool_blk = 0;
@@ -740,50 +744,58 @@ __global__ void __launch_bounds__(64) k_finish(Slot<NW>* slots, uint32_t n_slots
     slots[i] = s;
 }
 
-// Tree reuse (tree.rs:283-302): one wavefront per game re-roots the tree by the sliding compaction
-// described in dev_search.h (advance_tree_scalar is the one-lane statement of the same passes).
-// Pass 1 decides keep/drop and new ids 64 nodes at a time (parents inside the same 64 are resolved
-// by lane shuffles, the running count by ballot + popcount); pass 2 moves kept nodes.
-// The compaction is also where a game changes arena: once the kept tree is counted, the slot picks
-// the smallest arena (its first arena or an overflow-pool class) that holds the kept tree plus one
-// full search, and pass 2 writes there. So a tree never runs out of room in the middle of a search,
-// and a tree that shrank gives its block back. A slot that stalled anyway (pool empty at the time)
-// is retried here on every launch: its nodes are copied unchanged into a bigger block.
+// Tree reuse (tree.rs:283-302): a workgroup per game that has to move re-roots the tree by the sliding compaction of
+// dev_advance.h (advance_tree_scalar in dev_search.h is the one-lane statement of the same passes).
+// The compaction is also where a game changes arena: once the kept tree is counted, the slot picks the run of pages
+// that holds the kept tree plus one full search, and the move writes there. So a tree never runs out of room in the
+// middle of a search, and a tree that shrank gives pages back. A slot that stalled anyway (pool empty at the time)
+// is retried here on every launch: its nodes are copied unchanged into a bigger run.
+// The slot header stays in memory: the block reads the few words it needs and its first thread writes the few that change.
 template <int NW>
-__global__ void __launch_bounds__(64) k_advance(Slot<NW>* slots, uint32_t n_slots, Bases B, SearchCfg cfg,
-                                                uint32_t first_slot, uint32_t phase, uint32_t ready_status) {
-    const uint32_t slot = first_slot + blockIdx.x;
-    if (slot >= n_slots) return;
-    const uint32_t status = slots[slot].status;
-    if (status != tag_status(SLOT_ADVANCE, phase) && status != tag_status(SLOT_STALL, phase)) return;
-    const uint32_t lane = threadIdx.x;
-    Slot<NW> s = slots[slot];
-    const Mem<NW> m = resolve_mem<NW>(s, B.arena, B.scratch, slot, B.L, B.maze);
+__device__ inline void adv_arena_fields(const Slot<NW>& from, Slot<NW>& to) {
+    to.stats_off = from.stats_off;
+    to.fwd_off = from.fwd_off;
+    to.cap = from.cap;
+    to.pool_blk = from.pool_blk;
+    to.release_grown = from.release_grown;
+    to.error = from.error;
+}
+template <int NW>
+__device__ inline void advance_slot(Slot<NW>* slots, uint32_t slot, const Bases& B, const SearchCfg& cfg, uint32_t phase,
+                                    uint32_t ready_status, uint32_t fast_nodes, AdvLds& L) {
+    const uint32_t tid = threadIdx.x;
+    Slot<NW>& G = slots[slot];
+    Slot<NW> s;  // the arena the slot has now (only the fields the arena helpers read and write)
+    adv_arena_fields(G, s);
+    const uint32_t status = G.status, hi = G.hi, keep_root = G.pending_root, need = G.need_nodes;
+    __syncthreads();  // (the first thread rewrites these words at the end: every thread has read them)
+    NodeStats* stats = (NodeStats*)(B.arena + s.stats_off);
+    uint32_t* fwd = (uint32_t*)(B.arena + s.fwd_off);
 
     if (status == tag_status(SLOT_STALL, phase)) {
-        const uint32_t want = pool_pages_for(B.pool, s.need_nodes > s.cap + 1 ? s.need_nodes : s.cap + 1);
-        uint32_t idx = NIL;
-        if (lane == 0 && want) idx = pool_claim(B.pool, slot, want);
-        idx = (uint32_t)__shfl((int)idx, 0, 64);
+        const uint32_t want = pool_pages_for(B.pool, need > s.cap + 1 ? need : s.cap + 1);
+        if (tid == 0) L.pick = want ? pool_claim(B.pool, slot, want) : NIL;
+        __syncthreads();
+        const uint32_t idx = L.pick;
         if (idx == NIL) return;  // nothing free: the host sees the stall and decides
-        Slot<NW> d = s;
+        Slot<NW> d;
+        adv_arena_fields(s, d);
         slot_at_pages(d, B, slot, idx, want);
-        const Mem<NW> md = resolve_mem<NW>(d, B.arena, B.scratch, slot, B.L, B.maze);
-        const uint4* ss = (const uint4*)m.stats;
-        uint4* ds = (uint4*)md.stats;
-        for (uint32_t w = lane; w < s.hi * (uint32_t)(sizeof(NodeStats) / 16); w += 64) ds[w] = ss[w];
-        if (lane == 0) {
+        const uint4* ss = (const uint4*)stats;
+        uint4* ds = (uint4*)(B.arena + d.stats_off);
+        for (uint32_t w = tid; w < hi * (uint32_t)NODE_GROUPS; w += ADV_THREADS) ds[w] = ss[w];
+        if (tid == 0) {
             leave_arena(s, d, B);
-            d.status = ready_status;
-            slots[slot] = d;
+            adv_arena_fields(d, G);
+            G.status = ready_status;
         }
         return;
     }
 
-    const uint32_t keep_root = s.pending_root;
     if (keep_root == NIL) {  // fresh root: the pages a fresh tree wants (the run it is in, if that is as many)
-        if (lane == 0) {
-            Slot<NW> d = s;
+        if (tid == 0) {
+            Slot<NW> d;
+            adv_arena_fields(s, d);
             const uint32_t want = B.pool.fresh_pages;
             bool ok = s.cap != 0;
             if (s.pool_blk != want) {  // (a bigger run, none, or an arena from the host)
@@ -795,96 +807,75 @@ __global__ void __launch_bounds__(64) k_advance(Slot<NW>* slots, uint32_t n_slot
                 }
             }
             if (ok) {  // (an arena too small for a whole search stalls at its first gather and grows, like any other)
-                make_root(d, resolve_mem<NW>(d, B.arena, B.scratch, slot, B.L, B.maze));
-                d.status = ready_status;
-                slots[slot] = d;
+                adv_arena_fields(d, G);
+                make_root(G, resolve_mem<NW>(G, B.arena, B.scratch, slot, B.L, B.maze));
+                G.status = ready_status;
             }  // else: no arena yet; the slot stays as it is and the next launch of this parity tries again
         }
         return;
     }
-    const uint32_t hi = s.hi;
-    uint32_t cnt = 0;
-    const uint32_t first = keep_root & ~63u;
-    for (uint32_t base = 0; base < first; base += 64) {  // everything before the kept root is dropped
-        const uint32_t i = base + lane;
-        if (i < hi) __hip_atomic_store(&m.fwd[i], NIL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    for (uint32_t base = first; base < hi; base += 64) {
-        const uint32_t i = base + lane;
-        // 0 unknown, 1 keep, 2 drop
-        uint32_t st = 2, p = NIL;
-        if (i < hi) {
-            if (i == keep_root) st = 1;
-            else if (i > keep_root) {
-                p = m.stats[i].h1.parent;
-                if (p == NIL) st = 2;
-                else if (p < base)
-                    st = __hip_atomic_load(&m.fwd[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != NIL ? 1u : 2u;
-                else st = 0;
+
+    Slot<NW> d;
+    adv_arena_fields(s, d);
+    bool moved = false;
+    const uint32_t cnt = advance_compact(stats, fwd, hi, keep_root, fast_nodes, L, [&](uint32_t kept) -> NodeStats* {
+        // destination: the run that holds the kept tree plus one search (0 pages: beyond a run; the tree stays)
+        const uint32_t want = pool_pages_for(B.pool, arena_need(kept, cfg));
+        if (want != 0 && want != s.pool_blk) {  // (pool_blk 0: an arena from the host)
+            if (tid == 0) L.pick = pool_claim(B.pool, slot, want);
+            __syncthreads();
+            const uint32_t idx = L.pick;
+            if (idx != NIL) {
+                slot_at_pages(d, B, slot, idx, want);
+                moved = true;
             }
         }
-        // parents inside this group of 64: propagate along the id order (parent lane < child lane)
-        for (int round = 0; round < 64; ++round) {
-            const uint32_t src = (st == 0) ? (p - base) : lane;
-            const uint32_t pst = (uint32_t)__shfl((int)st, (int)src, 64);
-            if (st == 0 && pst != 0) st = pst;
-            if (!__any(st == 0)) break;
-        }
-        const bool keep = st == 1;
-        const unsigned long long bal = __ballot(keep);
-        const uint32_t before = (uint32_t)__popcll(bal & ((1ULL << lane) - 1ULL));
-        if (i < hi)
-            __hip_atomic_store(&m.fwd[i], keep ? cnt + before : NIL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        cnt += (uint32_t)__popcll(bal);
-        // the next group's lanes read this group's new ids: the stores must have left the wavefront
-        // (one wavefront on one CU: workgroup scope is enough, and an agent-scope fence would write
-        // back the XCD's whole L2 -- 550 times per step)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-    // destination arena: the smallest that holds the kept tree plus one search
-    const uint32_t want = pool_pages_for(B.pool, arena_need(cnt, cfg));  // (0: beyond a run; the tree stays where it is)
-    Slot<NW> d = s;
-    bool moved = false;
-    if (want != 0 && want != s.pool_blk) {  // (pool_blk 0: an arena from the host)
-        uint32_t idx = NIL;
-        if (lane == 0) idx = pool_claim(B.pool, slot, want);
-        idx = (uint32_t)__shfl((int)idx, 0, 64);
-        if (idx != NIL) {
-            slot_at_pages(d, B, slot, idx, want);
-            moved = true;
-        }
-    }
-    const Mem<NW> md = resolve_mem<NW>(d, B.arena, B.scratch, slot, B.L, B.maze);
-
-    for (uint32_t base = first; base < hi; base += 64) {
-        const uint32_t i = base + lane;
-        uint32_t ni = NIL;
-        if (i < hi) ni = __hip_atomic_load(&m.fwd[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        NodeStats nd;
-        if (ni != NIL) {
-            nd = m.stats[i];
-            nd.h1.parent = i == keep_root ? NIL
-                                          : __hip_atomic_load(&m.fwd[nd.h1.parent], __ATOMIC_RELAXED,
-                                                              __HIP_MEMORY_SCOPE_WORKGROUP);
-            for (int c = 0; c < 25; ++c)
-                if (nd.c[c] != NIL)
-                    nd.c[c] = __hip_atomic_load(&m.fwd[nd.c[c]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        __syncthreads();  // every lane has read its node before any lane overwrites a source
-        if (ni != NIL) md.stats[ni] = nd;
-        __syncthreads();
-    }
-    if (lane == 0) {
+        return (NodeStats*)(B.arena + d.stats_off);
+    });
+    if (tid == 0) {
         if (moved) leave_arena(s, d, B);
-        d.root = 0;
-        d.hi = cnt;
-        d.node_count = cnt;
-        d.status = ready_status;
-        slots[slot] = d;
+        adv_arena_fields(d, G);
+        G.root = 0;
+        G.hi = cnt;
+        G.node_count = cnt;
+        G.status = ready_status;
+    }
+}
+
+// Which slots: k_advance_scan lists the slots of [first_slot, n_slots) that wait for this phase's tree reuse, and k_advance
+// runs a fixed grid over the list, a block taking entries blockIdx, blockIdx + gridDim, ... Games move in bursts (a
+// session's games start in step, and so do the games that refill the slots of one host visit), in neighbouring slots:
+// a block per range of slots serialises a burst (measured: as slow as one wavefront per game), a block per slot is
+// 131072 blocks of eight wavefronts. `count` is this launch's counter and `count_next` the next launch's, which is
+// cleared here: the launches of one stream alternate between two counters, so no launch needs a memset of its own.
+enum { ADV_BLOCKS = 2048 };
+template <int NW>
+__global__ void __launch_bounds__(256) k_advance_scan(const Slot<NW>* slots, uint32_t n_slots, uint32_t first_slot, uint32_t phase,
+                                                      uint32_t* list, uint32_t* count, uint32_t* count_next) {
+    const uint32_t slot = first_slot + blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
+    bool work = false;
+    if (slot < n_slots) {
+        const uint32_t status = slots[slot].status;
+        work = status == tag_status(SLOT_ADVANCE, phase) || status == tag_status(SLOT_STALL, phase);
+    }
+    const unsigned long long bal = __ballot(work);
+    if (bal != 0ULL) {
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(count, (uint32_t)__popcll(bal));
+        base = (uint32_t)__shfl((int)base, 0, 64);
+        if (work) list[base + (uint32_t)__popcll(bal & ((1ULL << lane) - 1ULL))] = slot;  // (at most one entry per slot of the range)
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count_next = 0;
+}
+template <int NW>
+__global__ void __launch_bounds__(ADV_THREADS) k_advance(Slot<NW>* slots, Bases B, SearchCfg cfg, uint32_t phase, uint32_t ready_status,
+                                                         const uint32_t* list, const uint32_t* count, uint32_t fast_nodes) {
+    __shared__ AdvLds L;
+    const uint32_t n_todo = *count;
+    for (uint32_t t = blockIdx.x; t < n_todo; t += gridDim.x) {
+        const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[t]);
+        __syncthreads();  // (the tables of the tree before are free)
+        advance_slot(slots, slot, B, cfg, phase, ready_status, fast_nodes, L);
     }
 }
 
@@ -988,6 +979,7 @@ __global__ void k_pack_done(Slot<NW>* slots, const uint32_t* done_list, uint32_t
         // what the zone has free); an arena from the host is flagged for release
         Slot<NW> unused = s;
         leave_arena(s, unused, B);
+        if (unused.error) s.error = unused.error;
         if (unused.release_grown) s.release_grown = 1;
         s.cap = 0;
         s.pool_blk = 0;
@@ -1093,6 +1085,7 @@ __global__ void k_apply_grow(Slot<NW>* slots, const GrowReq* req, uint32_t n, Ba
     if (s.pool_blk) {
         Slot<NW> unused = s;
         leave_arena(s, unused, B);
+        if (unused.error) s.error = unused.error;
     }
     s.pool_blk = 0;
     s.cap = req[i].cap;
@@ -1304,6 +1297,7 @@ __global__ void k_match_release(Slot<NW>* slots, const uint32_t* done_list, uint
     Slot<NW>& s = slots[done_list[d]];
     Slot<NW> unused = s;
     leave_arena(s, unused, B);
+    if (unused.error) s.error = unused.error;
     if (unused.release_grown) s.release_grown = 1;
     s.cap = 0;
     s.pool_blk = 0;
@@ -1801,6 +1795,22 @@ enum class GatherKernel { Lane, Octet2, Octet3, Wide };
 // 7x7 / 1897 sims at 65536 games: 1180 M vs 1251 M): few games want k_gather8's wavefront count, many the fused kernel
 static bool default_uniform_queue(uint32_t resident_games) { return resident_games <= 16384u; }
 
+// ar_debug_advance: the compaction of dev_advance.h on trees the caller made up, one block per tree; a tree either stays
+// on its records or moves to the same place of a second buffer
+struct DbgAdvTree {
+    uint32_t first, hi, keep_root, moves;
+};
+__global__ void __launch_bounds__(ADV_THREADS) k_dbg_advance(NodeStats* recs, NodeStats* other, uint32_t* fwd, const DbgAdvTree* trees,
+                                                             uint32_t n, uint32_t fast_nodes, uint32_t* counts) {
+    __shared__ AdvLds L;
+    if (blockIdx.x >= n) return;
+    const DbgAdvTree t = trees[blockIdx.x];
+    NodeStats* src = recs + t.first;
+    NodeStats* dst = t.moves ? other + t.first : src;
+    const uint32_t cnt = advance_compact(src, fwd + t.first, t.hi, t.keep_root, fast_nodes, L, [&](uint32_t) { return dst; });
+    if (threadIdx.x == 0) counts[blockIdx.x] = cnt;
+}
+
 #if defined(AR_STATS)
 static void* g_dbg_slots;
 static uint32_t g_dbg_S, g_dbg_nw;
@@ -1990,10 +2000,15 @@ struct Engine {
             if (const char* e = getenv("AR_GW_PASSES")) gatherw_passes = atoi(e) > 0 ? (uint32_t)atoi(e) : 0xFFFFFFFFu;  // 0: no limit
         }
         cap0 = arena_nodes ? (uint32_t)align_up(arena_nodes, 64) : initial_arena_nodes(cfg);  // (arenas are whole 256-byte units)
+        if (const char* e = getenv("AR_ADV_NODES"))  // test knob, like AR_ARENA_NODES: small trees reach the slow path
+            if (atoi(e) >= 0) adv_fast_nodes = (uint32_t)atoi(e) < (uint32_t)ADV_MAX_NODES ? (uint32_t)atoi(e) : (uint32_t)ADV_MAX_NODES;
         slot_grown.assign(S, nullptr);
         slot_grown_cap.assign(S, 0u);
         HIP_TRY(slots.alloc(S));
         HIP_TRY(hipMemsetAsync(slots.p, 0, sizeof(Slot<NW>) * S, stream));
+        HIP_TRY(adv_list.alloc(S));
+        HIP_TRY(adv_count.alloc(2 * ADV_CTXS));
+        HIP_TRY(hipMemsetAsync(adv_count.p, 0, sizeof(uint32_t) * 2 * ADV_CTXS, stream));
 #if defined(AR_STATS)
         g_dbg_slots = slots.p;
         g_dbg_S = S;
@@ -2265,25 +2280,40 @@ struct Engine {
                 const uint32_t z0 = g.first / POOL_ZONE_SLOTS, z1 = (g.end + POOL_ZONE_SLOTS - 1) / POOL_ZONE_SLOTS;
                 hipLaunchKernelGGL(k_pool_merge, dim3(z1 - z0), dim3(64), 0, g.stream, pool, z0, z1 - z0);
             }
-            hipLaunchKernelGGL(k_advance<NW>, dim3(n), dim3(64), 0, g.stream, slots.p, g.end, bases(), cfg, g.first, 0u,
-                               (uint32_t)SLOT_ACTIVE);
+            launch_k_advance(g.stream, g.first, g.end, 0u, (uint32_t)SLOT_ACTIVE, gi);
         }
         g.step += 1;
         return AR_OK;
     }
 
+    // tree reuse of slots [first, end) on `st`: every launch site goes through here
+    uint32_t adv_fast_nodes = ADV_MAX_NODES;  // (AR_ADV_NODES, a test knob: trees above it take the compaction's slow path)
+    // `ctx`: which sequence of launches this one belongs to (a group's, or ADV_CTX_ALL for the launches over all slots):
+    // the launches of a sequence are in stream order and alternate between the sequence's two counters
+    enum { ADV_CTX_ALL = 64, ADV_CTXS = 65 };
+    DevBuf<uint32_t> adv_list, adv_count;  // [S] slots that wait, grouped as the slots are; [ADV_CTXS][2]
+    uint64_t adv_seq[ADV_CTXS] = {};
+    void launch_k_advance(hipStream_t st, uint32_t first, uint32_t end, uint32_t phase, uint32_t ready, uint32_t ctx) {
+        const uint32_t n = end - first;
+        uint32_t* cnt = adv_count.p + 2 * ctx + (uint32_t)(adv_seq[ctx] & 1);
+        uint32_t* cnt_next = adv_count.p + 2 * ctx + (uint32_t)((adv_seq[ctx] + 1) & 1);
+        adv_seq[ctx] += 1;
+        hipLaunchKernelGGL(k_advance_scan<NW>, dim3((n + 255) / 256), dim3(256), 0, st, slots.p, end, first, phase, adv_list.p + first,
+                           cnt, cnt_next);
+        hipLaunchKernelGGL(k_advance<NW>, dim3(n < (uint32_t)ADV_BLOCKS ? n : (uint32_t)ADV_BLOCKS), dim3(ADV_THREADS), 0, st, slots.p,
+                           bases(), cfg, phase, ready, adv_list.p + first, cnt, adv_fast_nodes);
+    }
+
     // tree reuse of the group's previous step, on the side stream: after that step's backup and (when a gather has been
     // launched since) after that gather
     int launch_late_advance(Group& g) {
-        const uint32_t n = g.end - g.first;
         HIP_TRY(hipStreamWaitEvent(g.adv_stream, g.backed_up, 0));
         HIP_TRY(hipStreamWaitEvent(g.adv_stream, g.gathered, 0));
         if (merge_per_group && pool.bits) {
             const uint32_t z0 = g.first / POOL_ZONE_SLOTS, z1 = (g.end + POOL_ZONE_SLOTS - 1) / POOL_ZONE_SLOTS;
             hipLaunchKernelGGL(k_pool_merge, dim3(z1 - z0), dim3(64), 0, g.adv_stream, pool, z0, z1 - z0);
         }
-        hipLaunchKernelGGL(k_advance<NW>, dim3(n), dim3(64), 0, g.adv_stream, slots.p, g.end, bases(), cfg, g.first, g.adv_phase,
-                           (uint32_t)SLOT_READY_A + g.adv_phase);
+        launch_k_advance(g.adv_stream, g.first, g.end, g.adv_phase, (uint32_t)SLOT_READY_A + g.adv_phase, (uint32_t)(&g - groups.data()));
         HIP_TRY(hipEventRecord(g.adv_ev[g.adv_phase], g.adv_stream));
         g.adv_pending = false;
         return AR_OK;
@@ -2300,7 +2330,7 @@ struct Engine {
     }
     void launch_advance() {
         if (pool.bits) hipLaunchKernelGGL(k_pool_merge, dim3(pool.zones), dim3(64), 0, stream, pool, 0u, pool.zones);
-        hipLaunchKernelGGL(k_advance<NW>, dim3(S), dim3(64), 0, stream, slots.p, S, bases(), cfg, 0u, 0u, (uint32_t)SLOT_ACTIVE);
+        launch_k_advance(stream, 0u, S, 0u, (uint32_t)SLOT_ACTIVE, (uint32_t)ADV_CTX_ALL);
     }
     void launch_cancel() { hipLaunchKernelGGL(k_cancel<NW>, dim3(grid(S)), dim3(64), 0, stream, slots.p, S, bases()); }
 
@@ -4051,6 +4081,42 @@ int ar_generate_cheese(uint8_t width, uint8_t height, uint8_t p1_cell, uint8_t p
     return AR_OK;
 }
 
+// Test entry (not in the public header): re-roots `n` made-up trees in one launch with the routine k_advance uses.
+// records: all trees' node records back to back, tree t being nodes [first[t], first[t] + hi[t]); keep_root[t] is the
+// node to keep; moves[t] != 0: the kept tree is written to a second buffer (which starts out as bytes of 0xEE), else in
+// place. fast_nodes: the fast path's limit as AR_ADV_NODES sets it (0xFFFFFFFF: the default). Out: both buffers
+// (in_place_out, moved_out: as many records as came in) and the kept count per tree.
+int ar_debug_advance(const void* records, uint64_t n_records, const uint32_t* first, const uint32_t* hi, const uint32_t* keep_root,
+                     const uint32_t* moves, uint32_t n, uint32_t fast_nodes, void* in_place_out, void* moved_out, uint32_t* counts_out) {
+    if (!records || !first || !hi || !keep_root || !moves || !in_place_out || !moved_out || !counts_out || n == 0 || n_records == 0)
+        return fail(AR_E_INVALID, "ar_debug_advance: null argument");
+    std::vector<DbgAdvTree> trees(n);
+    for (uint32_t t = 0; t < n; ++t) {
+        if (hi[t] == 0 || keep_root[t] >= hi[t] || (uint64_t)first[t] + hi[t] > n_records) return fail(AR_E_INVALID, "ar_debug_advance: bad tree");
+        trees[t] = DbgAdvTree{first[t], hi[t], keep_root[t], moves[t]};
+    }
+    const size_t bytes = (size_t)n_records * sizeof(NodeStats);
+    DevBuf<NodeStats> a, b;
+    DevBuf<uint32_t> fwd, cnt;
+    DevBuf<DbgAdvTree> tr;
+    HIP_TRY(a.alloc(n_records));
+    HIP_TRY(b.alloc(n_records));
+    HIP_TRY(fwd.alloc(n_records));
+    HIP_TRY(cnt.alloc(n));
+    HIP_TRY(tr.alloc(n));
+    HIP_TRY(hipMemcpy(a.p, records, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b.p, 0xEE, bytes));
+    HIP_TRY(hipMemcpy(tr.p, trees.data(), sizeof(DbgAdvTree) * n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_dbg_advance, dim3(n), dim3(ADV_THREADS), 0, 0, a.p, b.p, fwd.p, tr.p, n,
+                       fast_nodes < (uint32_t)ADV_MAX_NODES ? fast_nodes : (uint32_t)ADV_MAX_NODES, cnt.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(in_place_out, a.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(moved_out, b.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts_out, cnt.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    return AR_OK;
+}
+
 #if defined(AR_STATS)
 // sizes of the resident trees: [0..64) games by live-tree top (hi) / 512, [64..128) by arena capacity / 512,
 // [128] sum of hi, [129] sum of cap, [130] games
@@ -4064,6 +4130,13 @@ int ar_debug_tree_hist(unsigned long long* out131) {
     else hipLaunchKernelGGL(k_dbg_tree_hist<4>, dim3((g_dbg_S + 255) / 256), dim3(256), 0, 0, (const Slot<4>*)g_dbg_slots, g_dbg_S, d);
     HIP_TRY(hipMemcpy(out131, d, 131 * 8, hipMemcpyDeviceToHost));
     hipFree(d);
+    return AR_OK;
+}
+int ar_debug_advance_clk(unsigned long long* out32) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out32, HIP_SYMBOL(ar::g_adv_clk), sizeof(unsigned long long) * 32));
+    unsigned long long z[32] = {0};
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ar::g_adv_clk), z, sizeof z));
     return AR_OK;
 }
 int ar_debug_round_stats(unsigned long long* out32) {
