@@ -218,6 +218,8 @@ EXPORTS = {
     "ar_rows_games": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ar_rows_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ArTrainRows)]),
     "ar_rows_build_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "ar_rows_order_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "ar_rows_build_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ArTrainRows), C.c_void_p]),
     "ar_rows_clear": (C.c_int, [C.c_void_p]),
     "ar_rows_close": (None, [C.c_void_p]),
 }

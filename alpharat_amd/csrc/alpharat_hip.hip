@@ -1050,6 +1050,27 @@ k_rows_build(const PosRec<NW>* recs, const uint32_t* pos_game, const RowGame* ga
     rows_build_row<NW>(threadIdx.x & 63u, recs[src], g, mazes + (size_t)gi * hw * 4u, outcomes + (size_t)gi * hw, out, r);
 }
 
+// Output row row0 + i of a batch from stored position order_rows[first + row0 + i], seen by P2 where order_swap[...] is set
+// (dev_rows.h rows_build_row_as): an epoch's shuffle and its player-swap mask sit on the device as the set's order, and a
+// batch is a window of it, written once into the caller's tensors. The shape of k_rows_build: one wavefront per row, four
+// rows per block, global loads and stores only, no LDS. The wavefront's number in the block is made a scalar, so the row's
+// index, its flag and its game are read once per wavefront and the flag selects without divergence.
+template <int NW>
+__global__ void __launch_bounds__(ROWS_PER_BLOCK * ROWS_LANES)
+k_rows_batch(const PosRec<NW>* recs, const uint32_t* pos_game, const RowGame* games, const uint8_t* mazes,
+             const uint8_t* outcomes, const uint64_t* order_rows, const uint8_t* order_swap, uint64_t first, uint64_t row0,
+             uint32_t n, RowOut out) {
+    const uint32_t i = blockIdx.x * ROWS_PER_BLOCK + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (i >= n) return;
+    const uint64_t r = row0 + i;
+    const uint64_t src = order_rows[first + r];
+    const bool swap = order_swap[first + r] != 0;
+    const uint32_t gi = pos_game[src];
+    const RowGame& g = games[gi];
+    const size_t hw = (size_t)g.width * g.height;
+    rows_build_row_as<NW>(threadIdx.x & 63u, recs[src], g, mazes + (size_t)gi * hw * 4u, outcomes + (size_t)gi * hw, out, r, swap);
+}
+
 // arena growth: what a stalled slot reports, and its new home once the host has copied the nodes
 struct StallInfo {
     uint32_t slot, cap, hi, need;
@@ -2675,6 +2696,15 @@ struct RowStore {
     double build_kernel_ms = 0.0;
     hipEvent_t ev_append = nullptr;  // behind the last k_rows_append of an attached session, on its stream
     bool has_append = false;
+    // ar_rows_build_device: the order (stored position and perspective of every row of an epoch), replaced as a whole by
+    // ar_rows_order_set; ev_batch sits behind the last k_rows_batch, on the caller's stream
+    DevBuf<uint64_t> ord_rows;
+    DevBuf<uint8_t> ord_swap;
+    uint64_t ord_cap = 0, ord_n = 0;
+    bool has_order = false;
+    hipEvent_t ev_batch = nullptr;
+    bool has_batch = false;
+    hipError_t wait_batches() const { return has_batch ? hipEventSynchronize(ev_batch) : hipSuccess; }
     // uploads and builds run on the null stream: they wait for the attached session's last append, nothing else
     hipError_t wait_appends() const { return has_append ? hipEventSynchronize(ev_append) : hipSuccess; }
 
@@ -2683,6 +2713,7 @@ struct RowStore {
         if (ev0) hipEventDestroy(ev0);
         if (ev1) hipEventDestroy(ev1);
         if (ev_append) hipEventDestroy(ev_append);
+        if (ev_batch) hipEventDestroy(ev_batch);
     }
     int open(uint8_t w, uint8_t h, uint64_t cap, int dev) {
         device = dev;
@@ -2700,6 +2731,7 @@ struct RowStore {
         HIP_TRY(hipEventCreate(&ev0));
         HIP_TRY(hipEventCreate(&ev1));
         HIP_TRY(hipEventCreateWithFlags(&ev_append, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ev_batch, hipEventDisableTiming));
         return AR_OK;
     }
     bool fits(uint64_t positions, uint64_t n_games) const {
@@ -2912,6 +2944,100 @@ int rows_build(RowStore& R, const uint64_t* rows, uint64_t n, const ArTrainRows&
     HIP_TRY(hipMemcpy(o.action_p1, out.action_p1, n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(o.action_p2, out.action_p2, n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(o.cheese_outcomes, out.cheese_outcomes, n * hw, hipMemcpyDeviceToHost));
+    return AR_OK;
+}
+
+// ar_rows_order_set: the order is checked on the host, then replaces the old one on the device. Nothing may still read the
+// old one: the appends of an attached session and the last stream a batch was launched on are waited for first.
+int rows_order_set(RowStore& R, const uint64_t* rows, const uint8_t* swap, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (rows[i] >= R.n_pos)
+            return fail(AR_E_INVALID, "order entry " + std::to_string(i) + " asks for position " + std::to_string(rows[i]) +
+                                          ", the set holds " + std::to_string(R.n_pos));
+    HIP_TRY(hipSetDevice(R.device));
+    HIP_TRY(R.wait_appends());
+    HIP_TRY(R.wait_batches());
+    if (n > R.ord_cap) {
+        DevBuf<uint64_t> nr;
+        DevBuf<uint8_t> ns;
+        if (nr.alloc(n) != hipSuccess || ns.alloc(n) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(AR_E_NOMEM, "not enough device memory for an order of " + std::to_string(n) + " rows");
+        }
+        std::swap(R.ord_rows.p, nr.p);  // (the old buffers are freed with nr and ns)
+        std::swap(R.ord_swap.p, ns.p);
+        R.ord_cap = n;
+    }
+    R.has_order = false;
+    if (n) {
+        HIP_TRY(hipMemcpy(R.ord_rows.p, rows, n * 8, hipMemcpyHostToDevice));
+        if (swap)
+            HIP_TRY(hipMemcpy(R.ord_swap.p, swap, n, hipMemcpyHostToDevice));
+        else
+            HIP_TRY(hipMemset(R.ord_swap.p, 0, n));
+        HIP_TRY(hipStreamSynchronize(nullptr));  // the batches run on other streams: the order is complete before any is launched
+    }
+    R.ord_n = n;
+    R.has_order = true;
+    return AR_OK;
+}
+
+// an output array of ar_rows_build_device: device memory of the set's device
+int rows_check_device_ptr(const RowStore& R, const void* p, size_t align, const char* what) {
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof a);
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(AR_E_INVALID, std::string(what) + " is not device memory");
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != R.device)
+        return fail(AR_E_INVALID, std::string(what) + " is not device memory of device " + std::to_string(R.device));
+    if ((uintptr_t)p % align) return fail(AR_E_INVALID, std::string(what) + " is not aligned to " + std::to_string(align) + " bytes");
+    return AR_OK;
+}
+
+// ar_rows_build_device: rows first .. first + n of the order into the caller's device arrays, on the caller's stream. It
+// only launches: no synchronisation, no copy, no allocation.
+template <int NW>
+int rows_build_device(RowStore& R, uint64_t first, uint64_t n, const ArTrainRows& o, hipStream_t stream) {
+    if (!R.has_order) return fail(AR_E_INVALID, "the row set has no order: ar_rows_order_set comes first");
+    if (first > R.ord_n || n > R.ord_n - first)
+        return fail(AR_E_INVALID, "rows " + std::to_string(first) + " + " + std::to_string(n) + " go beyond the order of " +
+                                      std::to_string(R.ord_n));
+    if (n == 0) return AR_OK;
+    const struct { const void* p; size_t align; const char* what; } arrays[8] = {
+        {o.observation, 4, "observation"}, {o.policy_p1, 4, "policy_p1"}, {o.policy_p2, 4, "policy_p2"},
+        {o.value_p1, 4, "value_p1"},       {o.value_p2, 4, "value_p2"},   {o.action_p1, 1, "action_p1"},
+        {o.action_p2, 1, "action_p2"},     {o.cheese_outcomes, 1, "cheese_outcomes"}};
+    for (const auto& a : arrays)
+        if (int rc = rows_check_device_ptr(R, a.p, a.align, a.what)) return rc;
+    int before = 0;
+    HIP_TRY(hipGetDevice(&before));  // the caller's framework keeps its own current device
+    if (before != R.device) HIP_TRY(hipSetDevice(R.device));
+    RowOut out;
+    out.observation = o.observation;
+    out.policy_p1 = o.policy_p1;
+    out.policy_p2 = o.policy_p2;
+    out.value_p1 = o.value_p1;
+    out.value_p2 = o.value_p2;
+    out.action_p1 = o.action_p1;
+    out.action_p2 = o.action_p2;
+    out.cheese_outcomes = o.cheese_outcomes;
+    hipError_t err = hipSuccess;
+    for (uint64_t row0 = 0; row0 < n && err == hipSuccess; row0 += ROWS_PER_LAUNCH) {
+        const uint32_t cnt = (uint32_t)(n - row0 < (uint64_t)ROWS_PER_LAUNCH ? n - row0 : (uint64_t)ROWS_PER_LAUNCH);
+        hipLaunchKernelGGL(k_rows_batch<NW>, dim3((cnt + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(ROWS_PER_BLOCK * ROWS_LANES), 0,
+                           stream, (const PosRec<NW>*)R.recs.p, (const uint32_t*)R.pos_game.p, (const RowGame*)R.games.p,
+                           (const uint8_t*)R.mazes.p, (const uint8_t*)R.outcomes.p, (const uint64_t*)R.ord_rows.p,
+                           (const uint8_t*)R.ord_swap.p, first, row0, cnt, out);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) {
+        err = hipEventRecord(R.ev_batch, stream);
+        R.has_batch = true;
+    }
+    if (before != R.device) (void)hipSetDevice(before);
+    HIP_TRY(err);
     return AR_OK;
 }
 
@@ -4340,10 +4466,31 @@ int ar_rows_build_time(const ArRowSet* s, double* kernel_ms) {
     return AR_OK;
 }
 
+int ar_rows_order_set(ArRowSet* s, const uint64_t* rows, const uint8_t* swap, uint64_t n) {
+    if (!s || !s->impl || (!rows && n)) return fail(AR_E_INVALID, "null argument");
+    return rows_order_set(*s->impl, rows, swap, n);
+}
+
+int ar_rows_build_device(ArRowSet* s, uint64_t first, uint64_t n, const ArTrainRows* out, void* stream) {
+    if (!s || !s->impl) return fail(AR_E_INVALID, "null argument");
+    if (n && (!out || !out->observation || !out->policy_p1 || !out->policy_p2 || !out->value_p1 || !out->value_p2 ||
+              !out->action_p1 || !out->action_p2 || !out->cheese_outcomes))
+        return fail(AR_E_INVALID, "null argument");
+    static const ArTrainRows none = {};
+    return s->impl->nw == 1 ? rows_build_device<1>(*s->impl, first, n, out ? *out : none, (hipStream_t)stream)
+                            : rows_build_device<4>(*s->impl, first, n, out ? *out : none, (hipStream_t)stream);
+}
+
 int ar_rows_clear(ArRowSet* s) {
     if (!s || !s->impl) return fail(AR_E_INVALID, "null argument");
+    if (s->impl->has_batch) {  // the positions may be overwritten next: no batch may still read them
+        HIP_TRY(hipSetDevice(s->impl->device));
+        HIP_TRY(s->impl->wait_batches());
+    }
     s->impl->h_games.clear();
     s->impl->n_pos = 0;
+    s->impl->has_order = false;
+    s->impl->ord_n = 0;
     return AR_OK;
 }
 

@@ -96,6 +96,38 @@ def _view_of(game: dict, keep: list) -> _lib.ArGameRecordView:
     return v
 
 
+def row_shapes(width: int, height: int) -> dict:
+    """The shape of one row of each of the eight arrays."""
+    return dict(observation=(width * height * 7 + 6,), policy_p1=(5,), policy_p2=(5,), value_p1=(), value_p2=(),
+                action_p1=(), action_p2=(), cheese_outcomes=(height, width))
+
+
+def check_out_tensors(out: dict, n: int, width: int, height: int, device) -> None:
+    """``RowSet.build_into``'s conditions on its output tensors (``ValueError``); no device and no library is needed."""
+    import torch
+
+    shapes = row_shapes(width, height)
+    for k in KEYS:
+        if k not in out:
+            raise ValueError(f"out has no {k!r}")
+        t, want = out[k], (torch.int8 if k in ("action_p1", "action_p2", "cheese_outcomes") else torch.float32)
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{k} is not a torch tensor")
+        if t.dtype != want:
+            raise ValueError(f"{k} has dtype {t.dtype}, not {want}")
+        if not t.is_contiguous():
+            raise ValueError(f"{k} is not contiguous")
+        row = tuple(t.shape[1:])
+        if t.dim() < 1 or not (row == shapes[k] or (shapes[k] == () and row == (1,))):
+            raise ValueError(f"{k} has shape {tuple(t.shape)}, not (rows, {', '.join(map(str, shapes[k]))})")
+        if t.shape[0] < n:
+            raise ValueError(f"{k} has {t.shape[0]} rows, {n} are asked for")
+    for k in KEYS:
+        t = out[k]
+        if t.device != device:
+            raise ValueError(f"{k} is on {t.device}, the row set on {device}")
+
+
 class RowSet:
     """ctypes mirror of ``ArRowSet`` (include/alpharat_hip.h): finished games kept on the device until their training rows
     are built. ``capacity_positions`` is fixed here and allocated once; an append that does not fit raises ``MemoryError``
@@ -103,9 +135,10 @@ class RowSet:
     """
 
     def __init__(self, width: int, height: int, capacity_positions: int, device_index: int = 0) -> None:
-        self.width, self.height = int(width), int(height)
+        self.width, self.height, self.device_index = int(width), int(height), int(device_index)
         self._h = C.c_void_p()
         self._session = None
+        self._order_token = None  # set by the RowDataset whose epoch the order belongs to
         _lib.check(_lib.load().ar_rows_open(self.width, self.height, int(capacity_positions), int(device_index),
                                             C.byref(self._h)))
 
@@ -151,7 +184,41 @@ class RowSet:
         _lib.check(_lib.load().ar_rows_build_time(self._handle(), C.byref(ms)))
         return float(ms.value)
 
+    def set_order(self, rows, swap=None) -> None:
+        """The order ``build_into`` takes its windows from, kept on the device and replaced as a whole: row i is stored
+        position ``rows[i]``, seen by P2 where ``swap[i]`` is set (``None``: nowhere). A position beyond the set raises
+        ``ValueError`` and the old order stays. Waits for the batches still being written from the old order."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        if rows.ndim != 1:
+            raise ValueError("rows must be one-dimensional")
+        if swap is not None:
+            swap = np.ascontiguousarray(swap, dtype=np.uint8)
+            if swap.shape != rows.shape:
+                raise ValueError(f"swap has shape {swap.shape}, rows {rows.shape}")
+        self._order_token = None
+        _lib.check(_lib.load().ar_rows_order_set(self._handle(), rows.ctypes.data, swap.ctypes.data if swap is not None else None,
+                                                 len(rows)))
+
+    def build_into(self, first: int, n: int, out: dict, stream=None) -> None:
+        """Rows ``first .. first + n`` of the order into the caller's torch tensors ``out`` (the eight ``KEYS``), on
+        ``stream`` (``None``: ``torch.cuda.current_stream()`` of the set's device). Only launches: the tensors are ready
+        behind that stream, as after any torch operation on it. Every tensor is on the set's device, contiguous, float32
+        (int8 for the actions and cheese outcomes) and has at least ``n`` rows of its row shape (values and actions ``()``
+        or ``(1,)``, cheese outcomes ``(h, w)``), else ``ValueError`` before the library is touched."""
+        import torch
+
+        first, n = int(first), int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        check_out_tensors(out, n, self.width, self.height, torch.device("cuda", self.device_index))
+        handle = self._handle()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device_index)
+        ptrs = _lib.ArTrainRows(*[out[k].data_ptr() for k in KEYS])
+        _lib.check(_lib.load().ar_rows_build_device(handle, first, n, C.byref(ptrs), C.c_void_p(stream.cuda_stream)))
+
     def clear(self) -> None:
+        """Forgets the games, and the order with them."""
         _lib.check(_lib.load().ar_rows_clear(self._handle()))
 
     def close(self) -> None:

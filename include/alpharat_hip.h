@@ -379,6 +379,21 @@ int ar_rows_games(const ArRowSet* set, uint32_t* game_index, uint64_t* first_row
 int ar_rows_build(ArRowSet* set, const uint64_t* rows, uint64_t n, const ArTrainRows* out);
 /* time inside the kernels of the last ar_rows_build (HIP events), for measurements */
 int ar_rows_build_time(const ArRowSet* set, double* kernel_ms);
+/* ---- batches for a trainer, without the host copy (the reference's GPUDataset, nn/gpu_dataset.py, and its per-batch
+ * PlayerSwapStrategy, nn/augmentation.py:86-184) ------------------------------------------------------------------------
+ * The set keeps one order on the device: for every row of an epoch its stored position and whether the row is seen by P2
+ * (swap[i] != 0: the planes, scalars, policies, actions and values of the two players exchanged, cheese outcome 0 <-> 3,
+ * score difference negated). ar_rows_order_set checks every position (one beyond the set: AR_E_INVALID, the old order
+ * stays), waits for the set's pending appends and for the last stream a batch was launched on, and replaces the order as
+ * a whole; swap == NULL swaps no row. */
+int ar_rows_order_set(ArRowSet* set, const uint64_t* rows, const uint8_t* swap, uint64_t n);
+/* Rows first .. first + n of the order into `out_device`, whose eight arrays are the caller's device memory on the set's
+ * device (n rows each, the float arrays 4-byte aligned), launched on `stream` (a hipStream_t; NULL: the null stream). It
+ * only launches: no synchronisation, no copy, no allocation; the caller orders its reads behind `stream`. AR_E_INVALID
+ * before any launch: no order set, first + n beyond the order, an array that is not device memory of the set's device
+ * (hipPointerGetAttributes) or a misaligned float array. n == 0 succeeds and launches nothing. */
+int ar_rows_build_device(ArRowSet* set, uint64_t first, uint64_t n, const ArTrainRows* out_device, void* stream);
+/* forgets the games and drops the order */
 int ar_rows_clear(ArRowSet* set);
 void ar_rows_close(ArRowSet* set);
 
