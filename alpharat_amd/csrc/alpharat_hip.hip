@@ -760,6 +760,11 @@ __device__ inline void adv_arena_fields(const Slot<NW>& from, Slot<NW>& to) {
     to.release_grown = from.release_grown;
     to.error = from.error;
 }
+// the block reads the same words in every lane: in scalar registers they cost the move none of its vector registers
+__device__ inline uint32_t adv_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+__device__ inline long long adv_uniform(long long x) {
+    return (long long)(((unsigned long long)adv_uniform((uint32_t)((unsigned long long)x >> 32)) << 32) | adv_uniform((uint32_t)x));
+}
 template <int NW>
 __device__ inline void advance_slot(Slot<NW>* slots, uint32_t slot, const Bases& B, const SearchCfg& cfg, uint32_t phase,
                                     uint32_t ready_status, uint32_t fast_nodes, AdvLds& L) {
@@ -767,7 +772,14 @@ __device__ inline void advance_slot(Slot<NW>* slots, uint32_t slot, const Bases&
     Slot<NW>& G = slots[slot];
     Slot<NW> s;  // the arena the slot has now (only the fields the arena helpers read and write)
     adv_arena_fields(G, s);
-    const uint32_t status = G.status, hi = G.hi, keep_root = G.pending_root, need = G.need_nodes;
+    s.stats_off = adv_uniform(s.stats_off);
+    s.fwd_off = adv_uniform(s.fwd_off);
+    s.cap = adv_uniform(s.cap);
+    s.pool_blk = adv_uniform(s.pool_blk);
+    s.release_grown = adv_uniform(s.release_grown);
+    s.error = adv_uniform(s.error);
+    const uint32_t status = adv_uniform(G.status), hi = adv_uniform(G.hi), keep_root = adv_uniform(G.pending_root),
+                   need = adv_uniform(G.need_nodes);
     __syncthreads();  // (the first thread rewrites these words at the end: every thread has read them)
     NodeStats* stats = (NodeStats*)(B.arena + s.stats_off);
     uint32_t* fwd = (uint32_t*)(B.arena + s.fwd_off);
@@ -776,7 +788,7 @@ __device__ inline void advance_slot(Slot<NW>* slots, uint32_t slot, const Bases&
         const uint32_t want = pool_pages_for(B.pool, need > s.cap + 1 ? need : s.cap + 1);
         if (tid == 0) L.pick = want ? pool_claim(B.pool, slot, want) : NIL;
         __syncthreads();
-        const uint32_t idx = L.pick;
+        const uint32_t idx = adv_uniform(L.pick);
         if (idx == NIL) return;  // nothing free: the host sees the stall and decides
         Slot<NW> d;
         adv_arena_fields(s, d);
@@ -824,7 +836,7 @@ __device__ inline void advance_slot(Slot<NW>* slots, uint32_t slot, const Bases&
         if (want != 0 && want != s.pool_blk) {  // (pool_blk 0: an arena from the host)
             if (tid == 0) L.pick = pool_claim(B.pool, slot, want);
             __syncthreads();
-            const uint32_t idx = L.pick;
+            const uint32_t idx = adv_uniform(L.pick);
             if (idx != NIL) {
                 slot_at_pages(d, B, slot, idx, want);
                 moved = true;
@@ -842,40 +854,65 @@ __device__ inline void advance_slot(Slot<NW>* slots, uint32_t slot, const Bases&
     }
 }
 
-// Which slots: k_advance_scan lists the slots of [first_slot, n_slots) that wait for this phase's tree reuse, and k_advance
-// runs a fixed grid over the list, a block taking entries blockIdx, blockIdx + gridDim, ... Games move in bursts (a
-// session's games start in step, and so do the games that refill the slots of one host visit), in neighbouring slots:
-// a block per range of slots serialises a burst (measured: as slow as one wavefront per game), a block per slot is
-// 131072 blocks of eight wavefronts. `count` is this launch's counter and `count_next` the next launch's, which is
-// cleared here: the launches of one stream alternate between two counters, so no launch needs a memset of its own.
-enum { ADV_BLOCKS = 2048 };
+// Which slots: k_advance_scan lists the slots of [first_slot, n_slots) that wait for this phase's tree reuse, by the size
+// of the job (a launch lasts as long as its largest trees, so those start first), and k_advance's blocks take the entries
+// through a ticket, largest class first: a block's first ticket is its number, every later one comes from the counter.
+// Games move in bursts (a session's games start in step, and so do the games that refill the slots of one host visit),
+// in neighbouring slots: a block per range of slots serialises a burst (measured: as slow as one wavefront per game), a
+// block per slot is 131072 blocks of eight wavefronts. `count` holds this launch's ADV_COUNTERS words (entries per
+// class, then the ticket) and `count_next` the next launch's, which are cleared here: the launches of one stream
+// alternate between two sets, so no launch needs a memset of its own. Class c's list is list + c * list_stride.
+// ADV_BLOCKS: the grid. 256 (a block per CU, a tree at a time beside the CU's evaluator workgroups) gave the shortest batch
+// step on the bench workload, ahead of 512 and 2048 (profiles/r08_advance_ab.txt).
+enum { ADV_BLOCKS = 256, ADV_CLASSES = 4, ADV_TICKET = ADV_CLASSES, ADV_COUNTERS = 8 };
+// nodes to look at: hi - pending_root of a re-root, hi of a stalled slot's copy, 0 for a fresh root. The bounds are an
+// inference, not a histogram by nodes: tools/advance_stats.py sorts trees by time, and its two means (3175 nodes in 173 us
+// for all trees, 7819 nodes in 550 us for those above 300 us, profiles/r08_advance_premise.txt) put about 15 nodes in a
+// microsecond, so 8192 / 4096 / 1024 nodes stand for about 550 / 300 / 70 us of the parent's kernel. The order of the
+// classes is what matters, not where exactly they part.
+__device__ inline uint32_t adv_size_class(uint32_t nodes) { return nodes >= 8192u ? 0u : nodes >= 4096u ? 1u : nodes >= 1024u ? 2u : 3u; }
 template <int NW>
 __global__ void __launch_bounds__(256) k_advance_scan(const Slot<NW>* slots, uint32_t n_slots, uint32_t first_slot, uint32_t phase,
-                                                      uint32_t* list, uint32_t* count, uint32_t* count_next) {
+                                                      uint32_t* list, uint32_t list_stride, uint32_t* count, uint32_t* count_next) {
     const uint32_t slot = first_slot + blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
-    bool work = false;
+    uint32_t cls = ADV_CLASSES;  // (no work)
     if (slot < n_slots) {
-        const uint32_t status = slots[slot].status;
-        work = status == tag_status(SLOT_ADVANCE, phase) || status == tag_status(SLOT_STALL, phase);
+        const Slot<NW>& G = slots[slot];
+        const uint32_t status = G.status;
+        if (status == tag_status(SLOT_ADVANCE, phase)) cls = adv_size_class(G.pending_root == NIL ? 0u : G.hi - G.pending_root);
+        else if (status == tag_status(SLOT_STALL, phase)) cls = adv_size_class(G.hi);
     }
-    const unsigned long long bal = __ballot(work);
-    if (bal != 0ULL) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(count, (uint32_t)__popcll(bal));
-        base = (uint32_t)__shfl((int)base, 0, 64);
-        if (work) list[base + (uint32_t)__popcll(bal & ((1ULL << lane) - 1ULL))] = slot;  // (at most one entry per slot of the range)
+    if (__ballot(cls != (uint32_t)ADV_CLASSES) != 0ULL) {
+        for (uint32_t c = 0; c < (uint32_t)ADV_CLASSES; ++c) {
+            const unsigned long long bal = __ballot(cls == c);
+            if (bal == 0ULL) continue;
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(count + c, (uint32_t)__popcll(bal));
+            base = (uint32_t)__shfl((int)base, 0, 64);
+            // (at most one entry per slot of the range, so a class's list never holds more than list_stride)
+            if (cls == c) list[(size_t)c * list_stride + base + (uint32_t)__popcll(bal & ((1ULL << lane) - 1ULL))] = slot;
+        }
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *count_next = 0;
+    if (blockIdx.x == 0 && threadIdx.x < (uint32_t)ADV_COUNTERS) count_next[threadIdx.x] = 0;
 }
 template <int NW>
 __global__ void __launch_bounds__(ADV_THREADS) k_advance(Slot<NW>* slots, Bases B, SearchCfg cfg, uint32_t phase, uint32_t ready_status,
-                                                         const uint32_t* list, const uint32_t* count, uint32_t fast_nodes) {
+                                                         const uint32_t* list, uint32_t list_stride, uint32_t* count, uint32_t fast_nodes) {
     __shared__ AdvLds L;
-    const uint32_t n_todo = *count;
-    for (uint32_t t = blockIdx.x; t < n_todo; t += gridDim.x) {
-        const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[t]);
-        __syncthreads();  // (the tables of the tree before are free)
+    for (uint32_t t = blockIdx.x;;) {
+        uint32_t c = 0, at = t;  // entry `at` of class c: the classes one after the other (the counts are read again per
+        for (; c < (uint32_t)ADV_CLASSES; ++c) {  // ticket: a few scalar loads, and no registers held across a tree)
+            const uint32_t n = count[c];
+            if (at < n) break;
+            at -= n;
+        }
+        if (c == (uint32_t)ADV_CLASSES) break;
+        const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[(size_t)c * list_stride + at]);
+        __syncthreads();  // (the tables of the tree before are free, and every thread has read its ticket)
         advance_slot(slots, slot, B, cfg, phase, ready_status, fast_nodes, L);
+        if (threadIdx.x == 0) L.ticket = gridDim.x + atomicAdd(count + ADV_TICKET, 1u);
+        __syncthreads();
+        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.ticket);
     }
 }
 
@@ -2023,13 +2060,15 @@ struct Engine {
         cap0 = arena_nodes ? (uint32_t)align_up(arena_nodes, 64) : initial_arena_nodes(cfg);  // (arenas are whole 256-byte units)
         if (const char* e = getenv("AR_ADV_NODES"))  // test knob, like AR_ARENA_NODES: small trees reach the slow path
             if (atoi(e) >= 0) adv_fast_nodes = (uint32_t)atoi(e) < (uint32_t)ADV_MAX_NODES ? (uint32_t)atoi(e) : (uint32_t)ADV_MAX_NODES;
+        if (const char* e = getenv("AR_ADV_BLOCKS"))  // test knob: a smaller k_advance grid, so that a block takes several entries
+            if (atoi(e) > 0) adv_blocks = (uint32_t)atoi(e) < (uint32_t)ADV_BLOCKS ? (uint32_t)atoi(e) : (uint32_t)ADV_BLOCKS;
         slot_grown.assign(S, nullptr);
         slot_grown_cap.assign(S, 0u);
         HIP_TRY(slots.alloc(S));
         HIP_TRY(hipMemsetAsync(slots.p, 0, sizeof(Slot<NW>) * S, stream));
-        HIP_TRY(adv_list.alloc(S));
-        HIP_TRY(adv_count.alloc(2 * ADV_CTXS));
-        HIP_TRY(hipMemsetAsync(adv_count.p, 0, sizeof(uint32_t) * 2 * ADV_CTXS, stream));
+        HIP_TRY(adv_list.alloc((size_t)ADV_CLASSES * S));
+        HIP_TRY(adv_count.alloc(2 * ADV_CTXS * ADV_COUNTERS));
+        HIP_TRY(hipMemsetAsync(adv_count.p, 0, sizeof(uint32_t) * 2 * ADV_CTXS * ADV_COUNTERS, stream));
 #if defined(AR_STATS)
         g_dbg_slots = slots.p;
         g_dbg_S = S;
@@ -2312,17 +2351,18 @@ struct Engine {
     // `ctx`: which sequence of launches this one belongs to (a group's, or ADV_CTX_ALL for the launches over all slots):
     // the launches of a sequence are in stream order and alternate between the sequence's two counters
     enum { ADV_CTX_ALL = 64, ADV_CTXS = 65 };
-    DevBuf<uint32_t> adv_list, adv_count;  // [S] slots that wait, grouped as the slots are; [ADV_CTXS][2]
+    DevBuf<uint32_t> adv_list, adv_count;  // [ADV_CLASSES][S] slots that wait, grouped as the slots are; [ADV_CTXS][2][ADV_COUNTERS]
     uint64_t adv_seq[ADV_CTXS] = {};
+    uint32_t adv_blocks = ADV_BLOCKS;  // (AR_ADV_BLOCKS, a test knob: a smaller grid, so that a block takes several entries)
     void launch_k_advance(hipStream_t st, uint32_t first, uint32_t end, uint32_t phase, uint32_t ready, uint32_t ctx) {
         const uint32_t n = end - first;
-        uint32_t* cnt = adv_count.p + 2 * ctx + (uint32_t)(adv_seq[ctx] & 1);
-        uint32_t* cnt_next = adv_count.p + 2 * ctx + (uint32_t)((adv_seq[ctx] + 1) & 1);
+        uint32_t* cnt = adv_count.p + (2 * ctx + (uint32_t)(adv_seq[ctx] & 1)) * ADV_COUNTERS;
+        uint32_t* cnt_next = adv_count.p + (2 * ctx + (uint32_t)((adv_seq[ctx] + 1) & 1)) * ADV_COUNTERS;
         adv_seq[ctx] += 1;
         hipLaunchKernelGGL(k_advance_scan<NW>, dim3((n + 255) / 256), dim3(256), 0, st, slots.p, end, first, phase, adv_list.p + first,
-                           cnt, cnt_next);
-        hipLaunchKernelGGL(k_advance<NW>, dim3(n < (uint32_t)ADV_BLOCKS ? n : (uint32_t)ADV_BLOCKS), dim3(ADV_THREADS), 0, st, slots.p,
-                           bases(), cfg, phase, ready, adv_list.p + first, cnt, adv_fast_nodes);
+                           S, cnt, cnt_next);
+        hipLaunchKernelGGL(k_advance<NW>, dim3(n < adv_blocks ? n : adv_blocks), dim3(ADV_THREADS), 0, st, slots.p,
+                           bases(), cfg, phase, ready, adv_list.p + first, S, cnt, adv_fast_nodes);
     }
 
     // tree reuse of the group's previous step, on the side stream: after that step's backup and (when a gather has been

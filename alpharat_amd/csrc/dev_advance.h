@@ -16,7 +16,10 @@
 //   3. the caller picks the destination once the count is known (the same records, or a run of another size).
 //   4. move, by 16-byte group: unit u is group u % 20 of kept node u / 20, so twenty consecutive lanes read one
 //      contiguous record and the stores to dst + 16 u are contiguous across the whole block. The units that hold ids
-//      (adv_id_words) are mapped through the table on the way.
+//      (adv_id_words) are mapped through the table on the way. The move goes in chunks of ADV_CHUNK_NODES whole kept nodes:
+//      the source node of each is looked up once per chunk, into a 16-bit list in LDS (two lists of a chunk: 204 bytes,
+//      not the 2 bytes per node of a list of the whole tree), and the loads of the next chunks are in flight while a
+//      chunk waits, passes its barrier and is stored (adv_move_lds).
 // The slow path (any hi) keeps new ids in the arena's fwd[] in global memory: the recurrence as one wavefront ran it
 // before, then a move by 25 old nodes per step over all threads.
 #pragma once
@@ -30,7 +33,10 @@ enum {
     ADV_THREADS = 512,
     ADV_TILE = 2048,             // parents in LDS at a time
     ADV_MAX_NODES = 32768,       // hi - keep_root of the fast path: bitmap + counts cover this many ids
-    ADV_UNITS = 4,               // units per thread in flight in the move (a chunk: 2048 units, 32 KB)
+    ADV_UNITS = 2,               // units per thread and chunk of the move
+    ADV_CHUNK_NODES = ADV_THREADS * ADV_UNITS / NODE_GROUPS,  // a chunk: 51 whole kept nodes (1020 units, 16 KB)
+    ADV_CHUNK_UNITS = ADV_CHUNK_NODES * NODE_GROUPS,
+    ADV_DEPTH = 3,               // chunks in flight: the loads of chunk c + ADV_DEPTH - 1 are issued before chunk c's barrier
     ADV_PARENT_GROUP = 11,       // h1: {scale, r1, r2, parent}
     ADV_SLOW_NODES = ADV_THREADS / NODE_GROUPS,  // old nodes per step of the slow path's move
 };
@@ -59,7 +65,8 @@ AR_HD uint32_t adv_new_id(const unsigned long long* bits, const uint16_t* before
 // w with before[w] <= k (before[w + 1] = before[w] + the word's bits > k), then the (k - before[w])-th set bit of it.
 // words: 64-id words the tree has. from_word: a word at or below the one that holds it (a thread's units go up through
 // the kept nodes, 1/20 of a chunk at a time, so the word of its last unit is a few words short at most: a few steps
-// forward, and a binary search over the rest only when those were not enough).
+// forward, and a binary search over the rest only when those were not enough). The move no longer searches (adv_fill_list
+// below); this stays as the statement of what a list entry is, and tests/hostsim_advance runs it.
 AR_HD uint32_t adv_src_node(const unsigned long long* bits, const uint16_t* before, uint32_t words, uint32_t k, uint32_t from_word) {
     uint32_t lo = from_word, hi = words - 1;
     for (int step = 0; step < 4 && lo < hi && (uint32_t)before[lo + 1] <= k; ++step) ++lo;
@@ -86,6 +93,59 @@ AR_HD uint32_t adv_src_node(const unsigned long long* bits, const uint16_t* befo
     }
     return lo * 64u + pos;
 }
+// The source list of a chunk, src[n0 + k] = old id (relative to keep_root) for the chunk's kept nodes k = 0 .. nodes - 1,
+// without a search: where the id `rel` goes in it (ADV_NOT_LISTED: dropped, or a node of another chunk).
+static const uint32_t ADV_NOT_LISTED = 0xFFFFFFFFu;
+AR_HD uint32_t adv_list_slot(const unsigned long long* bits, const uint16_t* before, uint32_t rel, uint32_t n0, uint32_t nodes) {
+    if (!((bits[rel >> 6] >> (rel & 63u)) & 1ULL)) return ADV_NOT_LISTED;
+    const uint32_t k = adv_new_id(bits, before, rel) - n0;  // (below n0: wraps to a large number)
+    return k < nodes ? k : ADV_NOT_LISTED;
+}
+// Thread `tid` of `threads` (a multiple of 64) fills its part of the list: the threads take one id each of a window of
+// `threads` ids that starts at word from_word, and the window moves up until the words below it hold the whole chunk.
+// from_word: a word at or below the one that holds kept node n0 (the word of the last node of the chunk before).
+// cnt: the tree's kept count; nothing is written for n0 >= cnt. No two threads write the same entry, and a thread needs
+// nothing another one writes: one barrier after the call publishes the list.
+AR_HD void adv_fill_list(const unsigned long long* bits, const uint16_t* before, uint32_t words, uint32_t cnt, uint32_t n0,
+                         uint32_t from_word, uint32_t tid, uint32_t threads, uint16_t* list) {
+    if (n0 >= cnt) return;
+    const uint32_t nodes = cnt - n0 < (uint32_t)ADV_CHUNK_NODES ? cnt - n0 : (uint32_t)ADV_CHUNK_NODES;
+    for (uint32_t w0 = from_word; w0 < words; w0 += threads / 64u) {
+        const uint32_t rel = w0 * 64u + tid;
+        if ((rel >> 6) < words) {
+            const uint32_t k = adv_list_slot(bits, before, rel, n0, nodes);
+            if (k != ADV_NOT_LISTED) list[k] = (uint16_t)rel;
+        }
+        const uint32_t next = w0 + threads / 64u;
+        if (next < words && (uint32_t)before[next] >= n0 + nodes) break;  // (the words from `next` on hold later nodes only)
+    }
+}
+// The k-th unit of thread `tid` in chunk c of a tree of `units` units. Local unit j (< ADV_CHUNK_UNITS) is group j % 20 of
+// the chunk's kept node j / 20 and unit c * ADV_CHUNK_UNITS + j of the tree. Every thread has ADV_UNITS units in every
+// chunk, on no condition (adv_move_lds says why): the few threads whose k-th local unit would lie past the chunk's last
+// repeat that last unit (the same load, the same store of the same bytes), and a unit past the tree's last loads the kept
+// root's first group and is not stored.
+struct AdvUnit {
+    uint32_t j, u;  // local unit (clamped), the tree's unit
+    bool in_tree;   // u < units
+};
+AR_HD AdvUnit adv_chunk_unit(uint32_t c, uint32_t k, uint32_t tid, uint32_t units) {
+    AdvUnit x;
+    x.j = k * ADV_THREADS + tid;
+    if (x.j >= (uint32_t)ADV_CHUNK_UNITS) x.j = ADV_CHUNK_UNITS - 1u;
+    x.u = c * ADV_CHUNK_UNITS + x.j;
+    x.in_tree = x.u < units;
+    return x;
+}
+// where the unit is loaded from, in 16-byte groups from the kept root's record on; entry: the chunk's source list entry of
+// the unit's node (anything, if the unit is past the tree)
+AR_HD uint32_t adv_unit_source(const AdvUnit& x, uint32_t entry) { return x.in_tree ? entry * NODE_GROUPS + adv_unit_group(x.j) : 0u; }
+// whole: the chunk is one of the cnt / ADV_CHUNK_NODES whole ones (every unit of it is in the tree)
+AR_HD bool adv_unit_stored(const AdvUnit& x, bool whole) { return whole || x.in_tree; }
+// the register buffer a chunk's units wait in
+AR_HD uint32_t adv_chunk_buffer(uint32_t c) { return c % ADV_DEPTH; }
+static_assert(ADV_DEPTH >= 2, "the rest of a tree is loaded ADV_DEPTH - 1 steps ahead like any chunk: something must be ahead");
+
 // one unit on its way from the source to the destination: w = the four words of group g of a kept node
 // (is_root: of the kept root, whose parent becomes NIL); new_id maps an old id of a kept node
 template <class NewId>
@@ -104,8 +164,10 @@ struct AdvLds {
     unsigned long long bits[ADV_MAX_NODES / 64];  // keep flags by id relative to keep_root
     uint16_t before[ADV_MAX_NODES / 64];          // kept nodes in the words below
     uint16_t par[ADV_TILE];                       // parents of the tile, relative to keep_root (ADV_NONE: dropped for sure)
+    uint16_t list[2][ADV_CHUNK_NODES];            // source lists of the move: chunk c's in list[c & 1]
     uint32_t cnt;
     uint32_t pick;                                // the caller's word (which destination was picked)
+    uint32_t ticket;                              // the caller's word (which entry of the launch's list comes next)
 };
 static const uint32_t ADV_NONE = 0xFFFFu;
 
@@ -173,52 +235,86 @@ __device__ inline uint32_t adv_mark_lds(const NodeStats* src, uint32_t hi, uint3
     return L.cnt;
 }
 
-// step 4. In place, units go in increasing order in chunks, and every load of a chunk has RETURNED before any store of
-// the chunk is issued (registers filled, then a barrier). No other ordering is needed: src[n] >= n, so the source of
-// unit u lies at or above dst + 16 u. A chunk's stores therefore land at or below its own sources, which it has read
-// already, and below the sources of every later chunk, which lie above everything written so far -- a thread that is
-// still storing chunk c cannot hurt a thread that already loads chunk c + 1. A tree that moves to other records needs no
-// barrier at all.
-__device__ inline void adv_move_lds(const NodeStats* src, NodeStats* dst, uint32_t hi, uint32_t cnt, uint32_t keep_root,
-                                    bool in_place, const AdvLds& L) {
-    const uint4* s4 = (const uint4*)src;
+// step 4. A chunk is ADV_CHUNK_NODES whole kept nodes, so a thread's units are the same groups of the same nodes of every
+// chunk. The chunk's source list (adv_fill_list) is in LDS before its loads are issued: one lookup per kept node, and a
+// unit's lanes read their node's entry. In place, units go in increasing order in chunks, and every load of a chunk has
+// RETURNED before any store of the chunk is issued (registers filled, then a barrier). No other ordering is needed:
+// src[n] >= n, so the source of unit u lies at or above dst + 16 u. A chunk's stores therefore land at or below its own
+// sources, which it has read already, and below the sources of every later chunk, which lie above everything written so
+// far -- so the loads of the next ADV_DEPTH - 1 chunks are issued BEFORE this chunk's wait, barrier and stores and stay
+// in flight across them. A tree that moves to other records waits for no load at the barrier, which is then only what
+// publishes the next list. Step c: loads of chunk c + ADV_DEPTH - 1, list of chunk c + ADV_DEPTH (into the buffer whose
+// readers all passed the barrier before), wait for chunk c, barrier, ids mapped, stores of chunk c.
+// Forced inline: as a called function its record pointers are generic, and flat loads also count on the counter that the
+// waits for LDS reads use (profiles/r08_resource_usage.txt).
+__device__ __forceinline__ void adv_move_lds(const NodeStats* src, NodeStats* dst, uint32_t hi, uint32_t cnt, uint32_t keep_root,
+                                             bool in_place, AdvLds& L) {
+    const uint4* s4 = (const uint4*)(src + keep_root);  // (a uniform base and 32-bit offsets: ids relative to keep_root)
     uint4* d4 = (uint4*)dst;
     const uint32_t tid = threadIdx.x, units = cnt * NODE_GROUPS, words = (hi - keep_root + 63u) / 64u;
-    uint32_t at_word[ADV_UNITS];  // the word in which the k-th unit of the chunk before found its node
-#pragma unroll
-    for (uint32_t k = 0; k < ADV_UNITS; ++k) at_word[k] = 0;
-    for (uint32_t c0 = 0; c0 < units; c0 += ADV_THREADS * ADV_UNITS) {
-        uint4 v[ADV_UNITS];
+    const uint32_t full = cnt / ADV_CHUNK_NODES;  // whole chunks; the rest, if any, is chunk `full`
+    auto fill = [&](uint32_t c) {
+        const uint32_t from_word = c == 0 ? 0u : (uint32_t)L.list[(c - 1u) & 1u][ADV_CHUNK_NODES - 1] >> 6;
+        adv_fill_list(L.bits, L.before, words, cnt, c * ADV_CHUNK_NODES, from_word, tid, ADV_THREADS, L.list[c & 1u]);
+    };
+    // Every thread issues ADV_UNITS loads per chunk, and ADV_UNITS stores per whole chunk, on no condition (adv_chunk_unit):
+    // the compiler then knows how many are outstanding and waits for a chunk with a counted vmcnt that leaves the later
+    // ones in flight (behind a branch it would have to wait for all).
+    auto load = [&](uint32_t c, uint4* v) {
 #pragma unroll
         for (uint32_t k = 0; k < ADV_UNITS; ++k) {
-            const uint32_t u = c0 + k * ADV_THREADS + tid;
-            v[k] = make_uint4(0, 0, 0, 0);
-            if (u < units) {
-                const uint32_t rel = adv_src_node(L.bits, L.before, words, adv_unit_node(u), at_word[k]);
-                at_word[k] = rel >> 6;
-                v[k] = s4[(size_t)(keep_root + rel) * NODE_GROUPS + adv_unit_group(u)];
-            }
+            const AdvUnit x = adv_chunk_unit(c, k, tid, units);
+            v[k] = s4[adv_unit_source(x, L.list[c & 1u][adv_unit_node(x.j)])];
         }
+    };
+    auto store = [&](uint32_t c, uint4* v, bool whole) {
 #pragma unroll
         for (uint32_t k = 0; k < ADV_UNITS; ++k) {
-            const uint32_t u = c0 + k * ADV_THREADS + tid;
-            if (u < units && adv_id_words(adv_unit_group(u)) != 0) {
+            const AdvUnit x = adv_chunk_unit(c, k, tid, units);
+            if (adv_id_words(adv_unit_group(x.j)) != 0) {
                 uint32_t w[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
-                adv_remap_unit(w, adv_unit_group(u), u < NODE_GROUPS,
+                adv_remap_unit(w, adv_unit_group(x.j), x.u < NODE_GROUPS,
                                [&](uint32_t old) { return adv_new_id(L.bits, L.before, old - keep_root); });
                 v[k] = make_uint4(w[0], w[1], w[2], w[3]);
             }
+            if (adv_unit_stored(x, whole)) (d4 + (size_t)c * ADV_CHUNK_UNITS)[x.j] = v[k];
         }
+    };
+    auto arrived = [&](uint4* v) {
         if (in_place) {
 #pragma unroll
             for (uint32_t k = 0; k < ADV_UNITS; ++k) adv_arrived(v[k]);
-            __syncthreads();
         }
+    };
+    uint4 v[ADV_DEPTH][ADV_UNITS];
+    fill(0);
+    __syncthreads();
 #pragma unroll
-        for (uint32_t k = 0; k < ADV_UNITS; ++k) {
-            const uint32_t u = c0 + k * ADV_THREADS + tid;
-            if (u < units) d4[u] = v[k];
+    for (uint32_t s = 1; s < ADV_DEPTH; ++s) {
+        load(s - 1, v[s - 1]);
+        fill(s);
+        __syncthreads();
+    }
+    for (uint32_t c0 = 0; c0 < full; c0 += ADV_DEPTH) {
+#pragma unroll
+        for (uint32_t s = 0; s < ADV_DEPTH; ++s) {
+            const uint32_t c = c0 + s;  // (adv_chunk_buffer(c) = s: c0 is a multiple of ADV_DEPTH)
+            if (c >= full) break;
+            load(c + ADV_DEPTH - 1, v[(s + ADV_DEPTH - 1) % ADV_DEPTH]);
+            fill(c + ADV_DEPTH);
+            arrived(v[s]);
+            __syncthreads();
+            store(c, v[s], true);
         }
+    }
+    if (cnt % ADV_CHUNK_NODES != 0) {  // the rest: its loads were issued ADV_DEPTH - 1 steps ago, like any chunk's
+#pragma unroll
+        for (uint32_t s = 0; s < ADV_DEPTH; ++s)
+            if (adv_chunk_buffer(full) == s) {
+                arrived(v[s]);
+                __syncthreads();
+                store(full, v[s], false);
+            }
     }
 }
 
@@ -313,7 +409,8 @@ __device__ inline uint32_t advance_compact(const NodeStats* src, uint32_t* fwd, 
     const uint32_t n = hi - keep_root;
     const bool fast = n <= fast_nodes && n <= (uint32_t)ADV_MAX_NODES;
     ADV_STAT(const unsigned long long c0 = wall_clock64();)
-    const uint32_t cnt = fast ? adv_mark_lds(src, hi, keep_root, L) : adv_mark_fwd(src, fwd, hi, keep_root, L);
+    const uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane(  // (the same in every lane: a scalar register)
+        (int)(fast ? adv_mark_lds(src, hi, keep_root, L) : adv_mark_fwd(src, fwd, hi, keep_root, L)));
     ADV_STAT(const unsigned long long c1 = wall_clock64();)
     NodeStats* dst = pick_dst(cnt);
     ADV_STAT(const unsigned long long c2 = wall_clock64();)
