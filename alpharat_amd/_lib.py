@@ -183,6 +183,16 @@ class ArTrainRows(C.Structure):
                                           "action_p2", "cheese_outcomes")]
 
 
+class ArValSums(C.Structure):
+    _fields_ = [("n", C.c_uint64)] + [(k, C.c_double * 2) for k in ("ce", "sq_err", "ent_pred", "ent_target")] + [
+        (k, C.c_uint64 * 2) for k in ("top1", "top2")] + [
+        (k, C.c_double * 2) for k in ("sum_pred", "sum_target", "sum_pred2", "sum_target2", "sum_pred_target")]
+
+
+class ArValRows(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("logits_p1", "logits_p2", "value_p1", "value_p2")]
+
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -222,6 +232,8 @@ EXPORTS = {
     "ar_rows_build_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ArTrainRows), C.c_void_p]),
     "ar_rows_clear": (C.c_int, [C.c_void_p]),
     "ar_rows_close": (None, [C.c_void_p]),
+    "ar_rows_validate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(ArValSums),
+                                   C.POINTER(ArValRows)]),
 }
 
 _lib = None

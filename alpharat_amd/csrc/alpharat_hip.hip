@@ -36,6 +36,7 @@
 #include "dev_match.h"
 #include "dev_agents.h"
 #include "dev_rows.h"
+#include "dev_validate.h"
 #include "zig_norm_tables.inc"
 
 using namespace ar;
@@ -1106,6 +1107,91 @@ k_rows_batch(const PosRec<NW>* recs, const uint32_t* pos_game, const RowGame* ga
     const RowGame& g = games[gi];
     const size_t hw = (size_t)g.width * g.height;
     rows_build_row_as<NW>(threadIdx.x & 63u, recs[src], g, mazes + (size_t)gi * hw * 4u, outcomes + (size_t)gi * hw, out, r, swap);
+}
+
+// ---- validation over stored rows (dev_validate.h) ------------------------------------------------------------------
+// Evaluator requests from stored records, one lane per row: the position of row rows[i], and the number of its stored game
+// as the index of its Board (one Board per stored game, maze_off = game * hw * 4: the set's mazes are the maze pool).
+enum { VAL_BLOCK = 256, VAL_WAVES = VAL_BLOCK / 64, VAL_N_TERMS = VAL_N_DOUBLE + VAL_N_COUNT };
+template <int NW>
+__global__ void __launch_bounds__(VAL_BLOCK)
+k_val_requests(const PosRec<NW>* recs, const uint32_t* pos_game, const uint64_t* rows, uint32_t n, LeafReq<NW>* req) {
+    const uint32_t i = blockIdx.x * VAL_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t src = rows[i];
+    LeafReq<NW> q;
+    q.st = recs[src].st;
+    q.slot = pos_game[src];
+    q.pad = 0;
+    req[i] = q;
+}
+
+// The terms of row i (val_row_terms) from its record, its game, the evaluator's ten logits and two values, summed over the
+// block: in double over the wavefront with __shfl_down (a fixed tree), then over the block's wavefronts through LDS in
+// wavefront order. One partial vector per block, written with plain stores: no atomics, so the same request gives the same
+// bytes. A lane beyond n adds zeros and takes part in every shuffle.
+template <int NW>
+__global__ void __launch_bounds__(VAL_BLOCK)
+k_val_terms(const PosRec<NW>* recs, const uint32_t* pos_game, const RowGame* games, const uint64_t* rows, uint32_t n,
+            const float* logits, const EvalOut* ev, ValAcc* partial) {
+    __shared__ double s_d[VAL_WAVES][VAL_N_DOUBLE];
+    __shared__ uint32_t s_c[VAL_WAVES][VAL_N_COUNT];
+    const uint32_t i = blockIdx.x * VAL_BLOCK + threadIdx.x;
+    ValAcc acc;
+#pragma unroll
+    for (int j = 0; j < VAL_N_DOUBLE; ++j) acc.d[j] = 0.0;
+#pragma unroll
+    for (int j = 0; j < VAL_N_COUNT; ++j) acc.c[j] = 0;
+    if (i < n) {
+        const uint64_t src = rows[i];
+        float l[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) l[k] = logits[(size_t)i * 10 + k];
+        const EvalOut& o = ev[i];
+        val_accumulate(acc, val_row_terms<NW>(recs[src], games[pos_game[src]], l, o.v1, o.v2));
+    }
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < VAL_N_DOUBLE; ++j) {
+        double v = acc.d[j];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) s_d[wave][j] = v;
+    }
+#pragma unroll
+    for (int j = 0; j < VAL_N_COUNT; ++j) {
+        uint32_t c = (uint32_t)acc.c[j];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_down((int)c, off, 64);
+        if (lane == 0) s_c[wave][j] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x < VAL_N_DOUBLE) {
+        double v = s_d[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < VAL_WAVES; ++w) v += s_d[w][threadIdx.x];
+        partial[blockIdx.x].d[threadIdx.x] = v;
+    } else if (threadIdx.x < VAL_N_TERMS) {
+        const uint32_t j = threadIdx.x - VAL_N_DOUBLE;
+        uint64_t c = 0;
+#pragma unroll
+        for (int w = 0; w < VAL_WAVES; ++w) c += s_c[w][j];
+        partial[blockIdx.x].c[j] = c;
+    }
+}
+
+// One block adds the partial vectors of a chunk to the running total, in index order: thread j owns term j.
+__global__ void __launch_bounds__(64) k_val_sum(const ValAcc* partial, uint32_t n_partial, ValAcc* total) {
+    const uint32_t j = threadIdx.x;
+    if (j < VAL_N_DOUBLE) {
+        double v = total->d[j];
+        for (uint32_t b = 0; b < n_partial; ++b) v += partial[b].d[j];
+        total->d[j] = v;
+    } else if (j < VAL_N_TERMS) {
+        uint64_t c = total->c[j - VAL_N_DOUBLE];
+        for (uint32_t b = 0; b < n_partial; ++b) c += partial[b].c[j - VAL_N_DOUBLE];
+        total->c[j - VAL_N_DOUBLE] = c;
+    }
 }
 
 // arena growth: what a stalled slot reports, and its new home once the host has copied the nodes
@@ -2714,6 +2800,7 @@ int parse_device(const char* device, int device_index, int& out) {
 // and the game of every position. Everything is allocated once at open for `capacity` positions (a game has at least one
 // position, so `capacity` games at most); an append that does not fit is refused and changes nothing. The observations are
 // not stored: k_rows_build writes them when rows are asked for. Not thread-safe: one caller at a time, as a session.
+static std::atomic<uint64_t> g_rows_stamp{1};  // a value per state of a set's mazes that an evaluator may be bound to
 struct RowStore {
     int device = 0, nw = 1;
     uint8_t width = 0, height = 0;
@@ -2745,6 +2832,17 @@ struct RowStore {
     hipEvent_t ev_batch = nullptr;
     bool has_batch = false;
     hipError_t wait_batches() const { return has_batch ? hipEventSynchronize(ev_batch) : hipSuccess; }
+    // ar_rows_validate: one Board per stored game (the evaluator's `boards`; games only ever append, so the first
+    // val_boards_n entries stay right until a clear), and the workspace of one chunk, grown to the largest chunk asked for
+    uint64_t stamp = 0;  // changes when the games are forgotten: the same pool and count may then hold other mazes
+    DevBuf<Board> val_boards;
+    size_t val_boards_n = 0;
+    DevBuf<uint64_t> val_rows;
+    DevBuf<uint8_t> val_req;
+    DevBuf<EvalOut> val_out;
+    DevBuf<float> val_logits;
+    DevBuf<ValAcc> val_partial, val_total;
+    uint32_t val_chunk = 0;
     // uploads and builds run on the null stream: they wait for the attached session's last append, nothing else
     hipError_t wait_appends() const { return has_append ? hipEventSynchronize(ev_append) : hipSuccess; }
 
@@ -2762,6 +2860,7 @@ struct RowStore {
         hw = (uint32_t)w * h;
         nw = hw <= 64 ? 1 : 4;
         capacity = cap;
+        stamp = g_rows_stamp++;
         HIP_TRY(hipSetDevice(device));
         if (recs.alloc(cap * rec_bytes()) != hipSuccess || pos_game.alloc(cap) != hipSuccess || games.alloc(cap) != hipSuccess ||
             mazes.alloc(cap * hw * 4) != hipSuccess || outcomes.alloc(cap * hw) != hipSuccess) {
@@ -3078,6 +3177,137 @@ int rows_build_device(RowStore& R, uint64_t first, uint64_t n, const ArTrainRows
     }
     if (before != R.device) (void)hipSetDevice(before);
     HIP_TRY(err);
+    return AR_OK;
+}
+
+// free and allocate again (DevBuf::alloc on its own would leak the old block)
+template <typename T>
+static hipError_t regrow(DevBuf<T>& b, size_t count) {
+    if (b.p) {
+        const hipError_t e = hipFree(b.p);
+        b.p = nullptr;
+        b.n = 0;
+        if (e != hipSuccess) return e;
+    }
+    return b.alloc(count);
+}
+
+// ar_rows_validate: the request in chunks of `chunk` rows -- requests from the stored records (k_val_requests), the
+// evaluator with its logits output (net_launch), the terms of every row summed per block (k_val_terms) and added to the
+// running total (k_val_sum) -- all on the null stream; blocks until the sums are on the host. No observation, no target
+// array and, without `ro`, no per-row output leaves the device.
+enum { VAL_DEFAULT_CHUNK = 65536 };
+template <int NW>
+int rows_validate(RowStore& R, ArNet* net, const uint64_t* rows, uint64_t n, uint32_t chunk, ArValSums& sums, const ArValRows* ro) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (rows[i] >= R.n_pos)
+            return fail(AR_E_INVALID, "row " + std::to_string(i) + " asks for position " + std::to_string(rows[i]) +
+                                          ", the set holds " + std::to_string(R.n_pos));
+    if (net->dev.width != R.width || net->dev.height != R.height)
+        return fail(AR_E_INVALID, "the network was built for a " + std::to_string(net->dev.width) + "x" +
+                                      std::to_string(net->dev.height) + " board, the row set holds " + std::to_string(R.width) +
+                                      "x" + std::to_string(R.height) + " games");
+    if (net->device != R.device)
+        return fail(AR_E_INVALID, "the network is on device " + std::to_string(net->device) + ", the row set on device " +
+                                      std::to_string(R.device));
+    const size_t n_games = R.h_games.size();
+    if ((uint64_t)n_games * R.hw * 4u > 0xFFFFFFFFull)  // Board::maze_off is 32 bits wide
+        return fail(AR_E_INVALID, "the row set holds more games than an evaluator's maze pool can address");
+    if (n == 0) return AR_OK;
+    if (chunk == 0) chunk = VAL_DEFAULT_CHUNK;
+    if ((uint64_t)chunk > n) chunk = (uint32_t)n;
+    HIP_TRY(hipSetDevice(R.device));
+    HIP_TRY(R.wait_appends());
+    HIP_TRY(R.wait_batches());
+    const uint32_t max_blocks = (chunk + VAL_BLOCK - 1) / VAL_BLOCK;
+    if (chunk > R.val_chunk) {
+        R.val_chunk = 0;
+        if (regrow(R.val_rows, chunk) != hipSuccess || regrow(R.val_req, (size_t)chunk * sizeof(LeafReq<NW>)) != hipSuccess ||
+            regrow(R.val_out, chunk) != hipSuccess || regrow(R.val_logits, (size_t)chunk * 10) != hipSuccess ||
+            regrow(R.val_partial, max_blocks) != hipSuccess || (!R.val_total.p && R.val_total.alloc(1) != hipSuccess)) {
+            (void)hipGetLastError();
+            return fail(AR_E_NOMEM, "not enough device memory to validate " + std::to_string(chunk) + " rows at a time");
+        }
+        R.val_chunk = chunk;
+    }
+    // the boards of the games appended since the last call
+    if (n_games > R.val_boards.n || !R.val_boards.p) {
+        if (regrow(R.val_boards, n_games + n_games / 2 + 64) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(AR_E_NOMEM, "not enough device memory for the boards of " + std::to_string(n_games) + " games");
+        }
+        R.val_boards_n = 0;
+    }
+    if (R.val_boards_n < n_games) {
+        std::vector<Board> boards(n_games - R.val_boards_n);
+        for (size_t g = R.val_boards_n; g < n_games; ++g) {
+            Board& b = boards[g - R.val_boards_n];
+            b.width = R.h_games[g].width;
+            b.height = R.h_games[g].height;
+            b.max_turns = R.h_games[g].max_turns;
+            b.total_cheese = 0;  // (the evaluators read the size, max_turns and maze_off)
+            b.maze_off = (uint32_t)(g * R.hw * 4u);
+        }
+        HIP_TRY(hipMemcpy(R.val_boards.p + R.val_boards_n, boards.data(), boards.size() * sizeof(Board), hipMemcpyHostToDevice));
+        R.val_boards_n = n_games;
+    }
+    if (net->bound_pool != R.mazes.p || net->bound_mazes != (int)n_games || net->bound_stamp != R.stamp) {
+        if (int rc = net_bind_mazes(net, R.mazes.p, (int)n_games, nullptr)) return rc;
+        net->bound_stamp = R.stamp;
+    }
+    HIP_TRY(hipMemsetAsync(R.val_total.p, 0, sizeof(ValAcc), nullptr));
+    std::vector<EvalOut> h_out;
+    std::vector<float> h_logits;
+    if (ro) {
+        h_out.resize(chunk);
+        h_logits.resize((size_t)chunk * 10);
+    }
+    const PosRec<NW>* recs = (const PosRec<NW>*)R.recs.p;
+    LeafReq<NW>* req = (LeafReq<NW>*)R.val_req.p;
+    for (uint64_t row0 = 0; row0 < n; row0 += chunk) {
+        const uint32_t cnt = (uint32_t)(n - row0 < (uint64_t)chunk ? n - row0 : (uint64_t)chunk);
+        const uint32_t blocks = (cnt + VAL_BLOCK - 1) / VAL_BLOCK;
+        HIP_TRY(hipMemcpy(R.val_rows.p, rows + row0, (size_t)cnt * 8, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_val_requests<NW>, dim3(blocks), dim3(VAL_BLOCK), 0, nullptr, recs, (const uint32_t*)R.pos_game.p,
+                           (const uint64_t*)R.val_rows.p, cnt, req);
+        HIP_TRY(hipGetLastError());
+        if (int rc = net_launch<NW>(net, req, nullptr, cnt, (const char*)R.val_boards.p, sizeof(Board), R.val_out.p,
+                                    R.val_logits.p, nullptr))
+            return rc;
+        hipLaunchKernelGGL(k_val_terms<NW>, dim3(blocks), dim3(VAL_BLOCK), 0, nullptr, recs, (const uint32_t*)R.pos_game.p,
+                           (const RowGame*)R.games.p, (const uint64_t*)R.val_rows.p, cnt, (const float*)R.val_logits.p,
+                           (const EvalOut*)R.val_out.p, R.val_partial.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_val_sum, dim3(1), dim3(64), 0, nullptr, (const ValAcc*)R.val_partial.p, blocks, R.val_total.p);
+        HIP_TRY(hipGetLastError());
+        if (ro) {
+            HIP_TRY(hipMemcpy(h_out.data(), R.val_out.p, sizeof(EvalOut) * cnt, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(h_logits.data(), R.val_logits.p, (size_t)cnt * 40, hipMemcpyDeviceToHost));
+            for (uint32_t i = 0; i < cnt; ++i) {
+                if (ro->logits_p1) memcpy(ro->logits_p1 + (row0 + i) * 5, &h_logits[(size_t)i * 10], 20);
+                if (ro->logits_p2) memcpy(ro->logits_p2 + (row0 + i) * 5, &h_logits[(size_t)i * 10 + 5], 20);
+                if (ro->value_p1) ro->value_p1[row0 + i] = h_out[i].v1;
+                if (ro->value_p2) ro->value_p2[row0 + i] = h_out[i].v2;
+            }
+        }
+    }
+    ValAcc total;
+    HIP_TRY(hipMemcpy(&total, R.val_total.p, sizeof total, hipMemcpyDeviceToHost));  // (waits for the null stream)
+    sums.n = n;
+    for (int p = 0; p < 2; ++p) {
+        const double* d = total.d + VAL_D_PER_PLAYER * p;
+        sums.ce[p] = d[0];
+        sums.sq_err[p] = d[1];
+        sums.ent_pred[p] = d[2];
+        sums.ent_target[p] = d[3];
+        sums.sum_pred[p] = d[4];
+        sums.sum_target[p] = d[5];
+        sums.sum_pred2[p] = d[6];
+        sums.sum_target2[p] = d[7];
+        sums.sum_pred_target[p] = d[8];
+        sums.top1[p] = total.c[p];
+        sums.top2[p] = total.c[2 + p];
+    }
     return AR_OK;
 }
 
@@ -4529,12 +4759,25 @@ int ar_rows_clear(ArRowSet* s) {
     }
     s->impl->h_games.clear();
     s->impl->n_pos = 0;
+    s->impl->val_boards_n = 0;
+    s->impl->stamp = g_rows_stamp++;
     s->impl->has_order = false;
     s->impl->ord_n = 0;
     return AR_OK;
 }
 
 void ar_rows_close(ArRowSet* s) { delete s; }
+
+int ar_rows_validate(ArRowSet* s, ArNet* net, const uint64_t* rows, uint64_t n, uint32_t chunk_rows, ArValSums* sums,
+                     const ArValRows* rows_out) {
+    if (!s || !s->impl || !net || !sums || (!rows && n)) return fail(AR_E_INVALID, "null argument");
+    ArValSums out;
+    memset(&out, 0, sizeof out);
+    const int rc = s->impl->nw == 1 ? rows_validate<1>(*s->impl, net, rows, n, chunk_rows, out, rows_out)
+                                    : rows_validate<4>(*s->impl, net, rows, n, chunk_rows, out, rows_out);
+    if (rc == AR_OK) *sums = out;
+    return rc;
+}
 
 // ---- matches: tournament.py:329-373 / eval/game.py:47-87 / searcher_agent.py:40-56 on the device --------------
 int ar_match_run(const ArMatchParams* p, ArMatchSink sink, void* sink_user, ArMatchStats* out) {

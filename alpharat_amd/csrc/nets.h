@@ -1110,6 +1110,7 @@ struct ArNet {
     float* cmaze = nullptr;
     const uint8_t* bound_pool = nullptr;
     int bound_mazes = 0;
+    uint64_t bound_stamp = 0;  // non-zero: the pool is a row set's mazes in that state (ar_rows_validate); else 0
     size_t smem = 0;
     // ar_net_evaluate's own buffers (requests, boards, mazes, outputs, logits) and the maze bytes they hold
     struct Scratch {
@@ -1439,6 +1440,7 @@ static int net_build(const arnet::Blob& b, ArNet* net) {
 // (always recomputed: a pool at the same address with the same count may hold other mazes -- an engine that
 // died and a new one whose allocation landed on the same block; the kernel is tiny)
 static int net_bind_mazes(ArNet* net, const uint8_t* d_maze_pool, int n_mazes, hipStream_t stream) {
+    net->bound_stamp = 0;
     if (arnet::is_cnn(net->dev.arch)) {  // the CNN reads the maze planes itself
         net->bound_pool = d_maze_pool;
         net->bound_mazes = n_mazes;

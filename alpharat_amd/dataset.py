@@ -101,6 +101,11 @@ class RowDataset:
         train, val = split_games(gi, val_ratio, seed)
         return RowDataset(self.rowset, self.games[train]), RowDataset(self.rowset, self.games[val])
 
+    def validate(self, net, chunk_rows: int = 0, return_rows: bool = False):
+        """``net`` over this dataset's ``positions``: ``val.validate(net).metrics()`` is the reference's validation pass
+        over the val half of a split (``alpharat_amd.validate``). Needs no order and disturbs none."""
+        return self.rowset.validate(net, self._positions, chunk_rows, return_rows)
+
     def epoch_iter(self, batch_size: int, *, epoch: int = 0, seed: int = 0, augment: bool = True, p_swap: float = 0.5,
                    shuffle: bool = True, drop_last: bool = True) -> Iterator[dict]:
         """One epoch as dicts of device tensors in ``GPUDataset``'s shapes: observation ``(N, h*w*7+6)`` and policies

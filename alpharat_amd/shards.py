@@ -217,6 +217,13 @@ class RowSet:
         ptrs = _lib.ArTrainRows(*[out[k].data_ptr() for k in KEYS])
         _lib.check(_lib.load().ar_rows_build_device(handle, first, n, C.byref(ptrs), C.c_void_p(stream.cuda_stream)))
 
+    def validate(self, net, rows, chunk_rows: int = 0, return_rows: bool = False):
+        """``net`` over the stored positions ``rows``: the sums of the reference's validation pass
+        (``alpharat_amd.validate.validate``)."""
+        from .validate import validate
+
+        return validate(self, net, rows, chunk_rows, return_rows)
+
     def clear(self) -> None:
         """Forgets the games, and the order with them."""
         _lib.check(_lib.load().ar_rows_clear(self._handle()))

@@ -397,6 +397,43 @@ int ar_rows_build_device(ArRowSet* set, uint64_t first, uint64_t n, const ArTrai
 int ar_rows_clear(ArRowSet* set);
 void ar_rows_close(ArRowSet* set);
 
+/* ---- validation of a checkpoint over stored positions (the validation pass of alpharat/nn/training/loop.py:306-361:
+ * eval-mode forward, the loss of architectures/<arch>/loss.py, the detailed metrics of nn/metrics.py) --------------------
+ * The request is walked in chunks: evaluator requests are written from the stored records, the evaluator runs with its
+ * logits output, and one reduction sums the terms of every row; no observation and no target array is built. The sums
+ * are additive over rows (two results over disjoint rows add to the result over their union) and are formed in double
+ * from f32 terms without atomics: the same request gives the same bytes. For player p, with logits l, predicted value v
+ * (softplus, as ar_net_evaluate), target policy t and target value y = final score - score at the position:
+ *   ce          -sum_k t_k log_softmax(l)_k                      (F.cross_entropy with soft targets)
+ *   sq_err      (v - y)^2                                        (F.mse_loss)
+ *   ent_pred    -sum_k softmax(l)_k log_softmax(l)_k             (metrics.py:34-46)
+ *   ent_target  -sum_k t_k log(max(t_k, 1e-8))                   (metrics.py:49-62)
+ *   top1, top2  rank < 1, rank < 2, where a is the first index of the largest t_k and
+ *               rank = #{k : l_k > l_a} + #{k < a : l_k == l_a}  (metrics.py:15-31; torch.topk leaves the order among
+ *               equal logits open: taking the lower index first is this library's rule)
+ *   sum_pred, sum_target, sum_pred2, sum_target2, sum_pred_target   v, y, v^2, y^2, v y (metrics.py:65-116) */
+typedef struct ArValSums {
+    uint64_t n;
+    double ce[2], sq_err[2], ent_pred[2], ent_target[2];
+    uint64_t top1[2], top2[2];
+    double sum_pred[2], sum_target[2], sum_pred2[2], sum_target2[2], sum_pred_target[2];
+} ArValSums;
+/* per-row outputs in request order, host memory of n rows each; any array may be NULL */
+typedef struct ArValRows {
+    float* logits_p1; /* [n][5] */
+    float* logits_p2; /* [n][5] */
+    float* value_p1;  /* [n]    */
+    float* value_p2;  /* [n]    */
+} ArValRows;
+/* rows[n]: stored positions as for ar_rows_build, in any order, repeats allowed. chunk_rows: rows per evaluator launch,
+ * 0 = 65536 (a workspace of about 10 MB, kept in the set and grown to the largest chunk asked for). Blocks until the sums
+ * are on the host; waits for the set's pending appends and batches first. n == 0 succeeds with zero sums. AR_E_INVALID,
+ * with the set, the net and *sums untouched: a null set, net or sums; rows == NULL with n > 0; a row beyond the set's
+ * positions; a net built for another board size; a net on another device. The net's maze constants are bound to the
+ * set's mazes when they are not already; ar_net_evaluate binds its own again by itself. rows_out may be NULL. */
+int ar_rows_validate(ArRowSet* set, ArNet* net, const uint64_t* rows, uint64_t n, uint32_t chunk_rows, ArValSums* sums,
+                     const ArValRows* rows_out);
+
 #ifdef __cplusplus
 }
 #endif
