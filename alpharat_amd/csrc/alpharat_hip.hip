@@ -499,7 +499,7 @@ k_gatherw(Slot<NW>* slots, uint32_t n_slots, SearchCfg cfg, Bases B, uint32_t fi
     typedef GwShared<NW, G, R> Sh;
     __shared__ Sh sh;
     const uint32_t ring_mask = Sh::RING - 1;
-    __shared__ GwOutcomeTable otab;
+    __shared__ OutcomeTable otab;
     extern __shared__ uint32_t lds_maze[];  // the shared maze (B.maze_stage bytes), if the run has one
     const uint32_t L = threadIdx.x;
     GwMem<NW> m;
@@ -516,7 +516,7 @@ k_gatherw(Slot<NW>* slots, uint32_t n_slots, SearchCfg cfg, Bases B, uint32_t fi
     m.leaf_off = (uint32_t)B.L.leaf_off;
     m.spill_off = (uint32_t)B.L.levels_off;
     m.coll_cap = B.L.coll_cap;
-    if (L < 17) gw_outcome_entry(L, otab.omap[L], otab.n[L]);
+    if (L < 17) outcome_entry(L, otab.omap[L], otab.n[L]);
     if (L == 0) sh.tail = G;
     for (uint32_t c = L; c < (uint32_t)G; c += 64) {
         sh.game[c].slot = NIL;

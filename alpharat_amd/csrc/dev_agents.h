@@ -60,7 +60,7 @@ AR_HD uint32_t agent_sample(Rng& r, const float* policy, float temperature) {
         uint32_t best = 0;
         float top = policy[0];
         for (uint32_t i = 1; i < 5u; ++i) {
-            const float v = pick5(policy, i);
+            const float v = sel5f(policy, i);
             if (v > top) {
                 top = v;
                 best = i;

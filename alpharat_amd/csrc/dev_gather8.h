@@ -48,37 +48,9 @@ struct alignas(16) LevelO {
     State<NW> saved;
 };
 
-// node.rs:251-283 compute_outcomes for the 17 effective-action maps a cell can have (each of the four moves open or
-// blocked; or stuck in mud: everything is STAY), tabulated once per block: a new node's two maps are two LDS reads
-// instead of two runs of pack_outcomes (~50 instructions each, executed by the whole wavefront whenever ANY of its
-// eight games creates a node, i.e. in most rounds)
-struct OutcomeTable {
-    uint32_t omap[17];
-    uint32_t n[17];
-};
 __device__ inline void outcome_table_fill(OutcomeTable& t) {  // lanes 0..16 of the block
     const uint32_t k = threadIdx.x;
-    if (k < 17) {
-        uint32_t eff = 4u << 12;
-        if (k == 16) {
-            eff = 4u | (4u << 3) | (4u << 6) | (4u << 9) | (4u << 12);
-        } else {
-            eff |= (k & 1u) ? 4u : 0u;            // bit d set: direction d is blocked -> STAY
-            eff |= ((k & 2u) ? 4u : 1u) << 3;
-            eff |= ((k & 4u) ? 4u : 2u) << 6;
-            eff |= ((k & 8u) ? 4u : 3u) << 9;
-        }
-        uint32_t om, nn;
-        pack_outcomes(eff, om, nn);
-        t.omap[k] = om;
-        t.n[k] = nn;
-    }
-}
-// the table key of a player at `cell` with mud timer `mud` (same case split as eff_actions, dev_engine.h)
-__device__ inline uint32_t outcome_key(const uint8_t* cost, uint8_t cell, uint8_t mud) {
-    if (mud > 0) return 16u;
-    const uint32_t c = cell_costs(cost, cell);
-    return ((c & 0xffu) ? 0u : 1u) | (((c >> 8) & 0xffu) ? 0u : 2u) | (((c >> 16) & 0xffu) ? 0u : 4u) | (((c >> 24) & 0xffu) ? 0u : 8u);
+    if (k < 17) outcome_entry(k, t.omap[k], t.n[k]);
 }
 
 // what an octet touches rarely lives in LDS (coherent inside the wavefront, no registers): the game's random
@@ -130,59 +102,16 @@ struct Oct {
 
 __device__ inline uint32_t sel4(const uint32_t* a, uint32_t c) { return c == 0 ? a[0] : c == 1 ? a[1] : c == 2 ? a[2] : a[3]; }
 
-// search.rs:500-532 on five scores that every lane holds: best and second-best in outcome order, then the tie
-// pass. The random stream is only fetched (from LDS) when some outcome ties with the best one -- exactly the
-// cases in which the reference draws.
+// best_of5 on five scores that every lane holds. The random stream is only fetched (from LDS) when some outcome ties
+// with the best one -- exactly the cases in which the reference draws.
 template <int NW>
-__device__ inline void best_of5(const float* s, uint32_t n, OctShared<NW>& sh, uint32_t& best_out, float& second_out) {
-    const float NEG_INF = -__builtin_inff();
-    uint32_t best = 0;
-    float best_score = NEG_INF, second = NEG_INF;
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i) {
-        if (i < n) {
-            const float sc = s[i];
-            if (sc > best_score) {
-                second = best_score;
-                best_score = sc;
-                best = i;
-            } else if (sc > second) {
-                second = sc;
-            }
-        }
-    }
-    bool any_tie = false;
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i) any_tie = any_tie || (i < n && i != best && fabsf(s[i] - best_score) < 1e-12f);
-    if (any_tie) {
-        Rng rng = sh.rng;
-        uint32_t ties = 1;
-#pragma unroll
-        for (uint32_t i = 0; i < 5; ++i) {
-            if (i < n && i != best && fabsf(s[i] - best_score) < 1e-12f) {
-                ties += 1;
-                if (rng_below(rng, ties) == 0) best = i;
-            }
-        }
-        // every lane stores the (identical) new state: each thread then reads back what it wrote itself, so the
-        // compiler cannot keep a stale copy in registers for the lanes that would otherwise only read
-        sh.rng = rng;
-    }
-    best_out = best;
-    second_out = second;
-}
-// this lane's outcome as the best one: search.rs:534-553
-__device__ inline uint32_t vtc_of(float util, float num, uint32_t ns, float second) {
-    const float NEG_INF = -__builtin_inff();
-    if (second <= NEG_INF) return 0xFFFFFFFFu;
-    if (util >= second) return 0xFFFFFFFFu;
-    const float denom = second - util;
-    if (denom <= 0.0f) return 0xFFFFFFFFu;
-    const float n1 = (float)ns + 1.0f;
-    float vtc = num / denom - n1 + 1.0f;
-    if (!(vtc > 1.0f)) vtc = 1.0f;
-    const uint32_t k = vtc >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)vtc;
-    return k > 1 ? k : 1;
+__device__ inline void oct_best_of5(const float* s, uint32_t n, OctShared<NW>& sh, uint32_t& best_out, float& second_out) {
+    Rng rng = sh.rng;  // (best_of5 reads it on a tie only, and the compiler sinks these loads into that branch)
+    bool wait = false, drew = false;
+    best_of5(s, n, true, rng, wait, drew, best_out, second_out);
+    // every lane stores the (identical) new state: each thread then reads back what it wrote itself, so the
+    // compiler cannot keep a stale copy in registers for the lanes that would otherwise only read
+    if (drew) sh.rng = rng;
 }
 
 // One round of an octet's gather: the same decisions in the same order as gather_round (dev_search.h).
@@ -354,30 +283,17 @@ __device__ inline void gather8_round(Oct<NW>& o, OctShared<NW>& sh, const Outcom
                     mass2 += oct_getf<3>(c2);
                     mass1 += oct_getf<4>(c1);
                     mass2 += oct_getf<4>(c2);
-                    const float fpu1 = a.v1 - cfg.fpu_reduction * b.scale * sqrtf(mass1);
-                    const float fpu2 = a.v2 - cfg.fpu_reduction * b.scale * sqrtf(mass2);
-                    const float sqrt_total = sqrtf((float)(cv > 1 ? cv : 1));
+                    const float fpu1 = fpu_of(a.v1, b.scale, mass1, cfg), fpu2 = fpu_of(a.v2, b.scale, mass2, cfg);
+                    const float sqrt_total = sqrt_total_of(cv);
                     o.forced = 0;
 #pragma unroll
                     for (int pl = 0; pl < 2; ++pl) {
                         const Edge& e = pl == 0 ? E1 : E2;
-                        const uint32_t n = pl == 0 ? n1 : n2;
-                        const bool live = ol < n;
-                        const float q = e.visits > 0 ? e.q : (pl == 0 ? fpu1 : fpu2);
-                        o.util[pl] = q / b.scale;
-                        o.num[pl] = cfg.c_puct * e.prior * sqrt_total;
-                        o.ns[pl] = live ? e.visits + e.nif : 0;
+                        if (outcome_terms(e, ol < (pl == 0 ? n1 : n2), pl == 0 ? fpu1 : fpu2, b.scale, sqrt_total, cv, cfg,
+                                          from_pick, o.util[pl], o.num[pl], o.ns[pl], o.sc[pl]))
+                            o.forced |= 1u << pl;
                         o.nif0[pl] = e.nif;
                         o.add[pl] = 0;
-                        float sc = o.util[pl] + o.num[pl] / (1.0f + (float)o.ns[pl]);
-                        if (live && from_pick && cfg.force_k > 0.0f && e.prior > 0.0f) {
-                            const float threshold = sqrtf(cfg.force_k * e.prior * (float)cv);
-                            if ((float)e.visits < threshold) {
-                                sc = 1e20f;
-                                o.forced |= 1u << pl;
-                            }
-                        }
-                        o.sc[pl] = sc;
                     }
                     o.n1 = n1;
                     o.n2 = n2;
@@ -441,7 +357,7 @@ __device__ inline void gather8_round(Oct<NW>& o, OctShared<NW>& sh, const Outcom
                 s1[2] = oct_getf<2>(o.sc[0]);
                 s1[3] = oct_getf<3>(o.sc[0]);
                 s1[4] = oct_getf<4>(o.sc[0]);
-                best_of5(s1, o.n1, sh, b1, sec1);
+                oct_best_of5(s1, o.n1, sh, b1, sec1);
                 c1 = oct_pick(vtc_of(o.util[0], o.num[0], o.ns[0], sec1), b1);
             }
             if (o.n2 > 1) {
@@ -451,7 +367,7 @@ __device__ inline void gather8_round(Oct<NW>& o, OctShared<NW>& sh, const Outcom
                 s2[2] = oct_getf<2>(o.sc[1]);
                 s2[3] = oct_getf<3>(o.sc[1]);
                 s2[4] = oct_getf<4>(o.sc[1]);
-                best_of5(s2, o.n2, sh, b2, sec2);
+                oct_best_of5(s2, o.n2, sh, b2, sec2);
                 c2 = oct_pick(vtc_of(o.util[1], o.num[1], o.ns[1], sec2), b2);
             }
             uint32_t k = o.alloc_left;
@@ -469,14 +385,13 @@ __device__ inline void gather8_round(Oct<NW>& o, OctShared<NW>& sh, const Outcom
             }
             o.mask |= 1u << flat;
 #pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {  // half_take: the chosen outcome's started count and score
-                const uint32_t b = pl == 0 ? b1 : b2;
+            for (int pl = 0; pl < 2; ++pl) {  // the chosen outcome's started count and score
                 const uint32_t nsb = o.ns[pl] + k;
-                const float sc = o.util[pl] + o.num[pl] / (1.0f + (float)nsb);
-                const bool hit = ol == b;
+                const bool hit = ol == (pl == 0 ? b1 : b2);
+                const float sc = score_after_take(o.sc[pl], o.util[pl], o.num[pl], nsb, hit, (o.forced >> pl) & 1u);
                 o.ns[pl] = hit ? nsb : o.ns[pl];
                 o.add[pl] += hit ? k : 0u;
-                o.sc[pl] = (hit && !((o.forced >> pl) & 1u)) ? sc : o.sc[pl];
+                o.sc[pl] = sc;
             }
             o.alloc_left -= k;
         }

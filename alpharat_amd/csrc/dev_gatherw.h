@@ -70,30 +70,8 @@ struct alignas(16) GwU4 {
     uint32_t x, y, z, w;
 };
 
-// node.rs:251-283 compute_outcomes for the 17 effective-action maps a cell can have, tabulated once per block
-// (device); the CPU harness computes them directly
-struct GwOutcomeTable {
-    uint32_t omap[17];
-    uint32_t n[17];
-};
-AR_HD void gw_outcome_entry(uint32_t k, uint32_t& omap, uint32_t& n) {
-    uint32_t eff = 4u << 12;
-    if (k == 16) {
-        eff = 4u | (4u << 3) | (4u << 6) | (4u << 9) | (4u << 12);
-    } else {
-        eff |= (k & 1u) ? 4u : 0u;  // bit d set: direction d is blocked -> STAY
-        eff |= ((k & 2u) ? 4u : 1u) << 3;
-        eff |= ((k & 4u) ? 4u : 2u) << 6;
-        eff |= ((k & 8u) ? 4u : 3u) << 9;
-    }
-    pack_outcomes(eff, omap, n);
-}
-AR_HD uint32_t gw_outcome_key(const uint8_t* cost, uint8_t cell, uint8_t mud) {
-    if (mud > 0) return 16u;
-    const uint32_t c = cell_costs(cost, cell);
-    return ((c & 0xffu) ? 0u : 1u) | (((c >> 8) & 0xffu) ? 0u : 2u) | (((c >> 16) & 0xffu) ? 0u : 4u) |
-           (((c >> 24) & 0xffu) ? 0u : 8u);
-}
+// (the name the CPU harness under tests/hostsim passes its null table by; the table itself is dev_search.h's)
+typedef OutcomeTable GwOutcomeTable;
 
 // the position of an entry as its children (or the entry itself, when it is run again) find it
 template <int NW>
@@ -174,132 +152,6 @@ struct GwLane {
     unsigned long long dbg_t[3];      // 100 MHz clock: record arrived, set-up done, allocation done
 #endif
 };
-
-// Element `i` of a small array that lives in registers, as an OR over masked elements: a chain of `i == 0 ? a[0] : ...`
-// selects is rewritten by the optimizer into one load through a selected pointer, which pins the whole lane state in
-// scratch memory; a select between an element and zero is not.
-AR_HD uint32_t gw_sel5u(const uint32_t* a, uint32_t i) {
-    uint32_t r = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 5; ++j) r |= (i == j) ? a[j] : 0u;
-    return r;
-}
-AR_HD float gw_sel5f(const float* a, uint32_t i) {
-    uint32_t r = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 5; ++j) r |= (i == j) ? f32_to_bits(a[j]) : 0u;
-    return bits_to_f32(r);
-}
-// ---- per-player allocation state (the lane kernel's HalfAlloc with the added-visits counters packed) ------------
-struct GwHalf {
-    float score[5], util[5], num[5];
-    uint32_t ns[5], nif0[5];
-    uint32_t add;     // 5 x 6 bits: visits added to outcome i in this allocation
-    uint32_t forced;  // bit i: forced-playout score (search.rs:493-498)
-    uint32_t n;
-};
-
-// search.rs:478-498 (same expressions as half_init, dev_search.h)
-AR_HD void gw_half_init(GwHalf& h, const Edge* e, uint32_t n, float node_value, float scale, uint32_t cv,
-                        const SearchCfg& cfg, bool is_root) {
-    h.n = n;
-    h.forced = 0;
-    h.add = 0;
-    float mass = 0.0f;
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i)
-        if (i < n && e[i].visits > 0) mass += e[i].prior;
-    const float fpu = node_value - cfg.fpu_reduction * scale * sqrtf(mass);
-    const float sqrt_total = sqrtf((float)(cv > 1 ? cv : 1));
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i) {
-        const bool live = i < n;
-        const float q = e[i].visits > 0 ? e[i].q : fpu;
-        h.util[i] = q / scale;
-        h.num[i] = cfg.c_puct * e[i].prior * sqrt_total;
-        h.ns[i] = live ? e[i].visits + e[i].nif : 0;
-        h.nif0[i] = e[i].nif;
-        h.score[i] = h.util[i] + h.num[i] / (1.0f + (float)h.ns[i]);
-    }
-    if (is_root && cfg.force_k > 0.0f) {
-#pragma unroll
-        for (uint32_t i = 0; i < 5; ++i) {
-            if (i < n && e[i].prior > 0.0f) {
-                const float threshold = sqrtf(cfg.force_k * e[i].prior * (float)cv);
-                if ((float)e[i].visits < threshold) {
-                    h.score[i] = 1e20f;
-                    h.forced |= 1u << i;
-                }
-            }
-        }
-    }
-}
-
-// search.rs:463-554 estimated_visits_to_change_best_half on the cached scores (half_best, dev_search.h). A tie pass
-// draws from the game's stream only when `may_draw`; otherwise `wait` is set and nothing has been consumed.
-AR_HD void gw_half_best(const GwHalf& h, bool may_draw, Rng& rng, bool& wait, bool& drew, uint32_t& best_out,
-                        uint32_t& vtc_out) {
-    const uint32_t n = h.n;
-    best_out = 0;
-    vtc_out = 0xFFFFFFFFu;
-    if (n <= 1) return;
-    const float NEG_INF = -__builtin_inff();
-    uint32_t best = 0;
-    float best_score = NEG_INF, second = NEG_INF;
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i) {
-        const float sc = h.score[i];
-        const bool in = i < n;
-        const bool gt = in && sc > best_score;
-        const bool gt2 = in && !gt && sc > second;
-        second = gt ? best_score : (gt2 ? sc : second);
-        best_score = gt ? sc : best_score;
-        best = gt ? i : best;
-    }
-    // (the first outcome the tie pass below would count: it is tested before any draw has moved `best`)
-    bool any_tie = false;
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i) any_tie = any_tie || (i < n && i != best && fabsf(h.score[i] - best_score) < 1e-12f);
-    if (any_tie) {
-        if (!may_draw) {
-            wait = true;
-            return;
-        }
-        drew = true;
-        uint32_t ties = 1;
-#pragma unroll
-        for (uint32_t i = 0; i < 5; ++i) {
-            if (i < n && i != best && fabsf(h.score[i] - best_score) < 1e-12f) {  // (`best` moves with the draws, as in the reference)
-                ties += 1;
-                if (rng_below(rng, ties) == 0) best = i;
-            }
-        }
-    }
-    best_out = best;
-    const float best_util = gw_sel5f(h.util, best);
-    if (second <= NEG_INF) return;
-    if (best_util >= second) return;
-    const float denom = second - best_util;
-    if (denom <= 0.0f) return;
-    const float n1 = (float)gw_sel5u(h.ns, best) + 1.0f;
-    float vtc = gw_sel5f(h.num, best) / denom - n1 + 1.0f;
-    if (!(vtc > 1.0f)) vtc = 1.0f;
-    const uint32_t k = vtc >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)vtc;
-    vtc_out = k > 1 ? k : 1;
-}
-
-AR_HD void gw_half_take(GwHalf& h, uint32_t b, uint32_t k) {
-    const uint32_t nsb = gw_sel5u(h.ns, b) + k;
-    const float sc = gw_sel5f(h.util, b) + gw_sel5f(h.num, b) / (1.0f + (float)nsb);
-    const bool keep_forced = (h.forced >> b) & 1u;
-    h.add += k << (6u * b);
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i) {
-        const bool hit = i == b;
-        h.ns[i] = hit ? nsb : h.ns[i];
-        h.score[i] = (hit && !keep_forced) ? sc : h.score[i];
-    }
-}
 
 // One game's addresses: the arena from the game's offset, the per-slot scratch from the layout
 template <int NW>
@@ -382,7 +234,7 @@ AR_HD void gw_fetch(GwLane<NW>& ln, uint32_t item, const GwGame<NW>* games, cons
 // ---- phase 2: look at the node (search.rs:591-636 root, :675-725 child, :742-817 build_gather_level) ---------------
 template <int NW>
 AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of the game*/, const GwMem<NW>& m,
-                    const SearchCfg& cfg, const GwOutcomeTable* otab) {
+                    const SearchCfg& cfg, const OutcomeTable* otab) {
     if (ln.free_ref != GW_SPILL) rec_owner[ln.free_ref] = 0;  // (every reader of it ran phase 1 of this pass)
     ln.is_final = ln.wait = ln.interior = false;
     ln.fin_node = NIL;
@@ -405,7 +257,7 @@ AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of 
         uint32_t om1, om2, n1, n2;
 #if defined(__HIP_DEVICE_COMPILE__)
         {
-            const uint32_t k1 = gw_outcome_key(cost, ln.pos.p1, ln.pos.m1), k2 = gw_outcome_key(cost, ln.pos.p2, ln.pos.m2);
+            const uint32_t k1 = outcome_key(cost, ln.pos.p1, ln.pos.m1), k2 = outcome_key(cost, ln.pos.p2, ln.pos.m2);
             om1 = otab->omap[k1];
             n1 = otab->n[k1];
             om2 = otab->omap[k2];
@@ -467,13 +319,14 @@ AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of 
         } else {
             // visited interior node: split its visits among the children (build_gather_level, search.rs:742-817)
             const uint32_t cv = a.visits > 0 ? a.visits - 1 : 0;
-            GwHalf h1, h2;
-            gw_half_init(h1, e1, meta_n(c.meta, 0), a.v1, b.scale, cv, cfg, ln.from_pick);
-            gw_half_init(h2, e2, meta_n(c.meta, 1), a.v2, b.scale, cv, cfg, ln.from_pick);
+            HalfAlloc h1, h2;
+            half_init(h1, e1, meta_n(c.meta, 0), a.v1, b.scale, cv, cfg, ln.from_pick);
+            half_init(h2, e2, meta_n(c.meta, 1), a.v2, b.scale, cv, cfg, ln.from_pick);
             // a draw is in depth-first order only when every earlier visit slot of the pick is final
             const uint32_t earlier = (1u << ln.t) - 1u;
             const bool may_draw = (G.final_mask & earlier) == earlier;
             uint32_t left = ln.k, mask = 0;
+            uint32_t add1 = 0, add2 = 0;  // 5 x 6 bits: visits added to outcome i of each player (a pick has GW_SLOTS visits)
             uint32_t v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0;
             bool wait = false;
 #if defined(AR_STATS) && defined(__HIP_DEVICE_COMPILE__)
@@ -483,9 +336,9 @@ AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of 
             bool drew = false;
             while (left > 0) {
                 uint32_t b1, b2, c1, c2;
-                gw_half_best(h1, may_draw, rng, wait, drew, b1, c1);
+                half_best(h1, may_draw, rng, wait, drew, b1, c1);
                 if (wait) break;
-                gw_half_best(h2, may_draw, rng, wait, drew, b2, c2);
+                half_best(h2, may_draw, rng, wait, drew, b2, c2);
                 if (wait) break;
                 uint32_t kk = left;
                 if (c1 < kk) kk = c1;
@@ -498,8 +351,10 @@ AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of 
                 v3 += b1 == 3 ? add : 0u;
                 v4 += b1 == 4 ? add : 0u;
                 mask |= 1u << (b1 * 5 + b2);
-                gw_half_take(h1, b1, kk);
-                gw_half_take(h2, b2, kk);
+                half_take(h1, b1, kk);
+                half_take(h2, b2, kk);
+                add1 += kk << (6u * b1);
+                add2 += kk << (6u * b2);
                 left -= kk;
 #if defined(AR_STATS) && defined(__HIP_DEVICE_COMPILE__)
                 ln.dbg_steps += 1;
@@ -518,7 +373,7 @@ AR_HD void gw_visit(GwLane<NW>& ln, GwGame<NW>& G, uint32_t* rec_owner /*[R] of 
             W.h0.nif = a.nif + ln.k;
 #pragma unroll
             for (uint32_t i = 0; i < 5; ++i) {
-                const uint32_t a1 = (h1.add >> (6u * i)) & 63u, a2 = (h2.add >> (6u * i)) & 63u;
+                const uint32_t a1 = (add1 >> (6u * i)) & 63u, a2 = (add2 >> (6u * i)) & 63u;
                 if (a1) W.e[0][i].nif = h1.nif0[i] + a1;
                 if (a2) W.e[1][i].nif = h2.nif0[i] + a2;
             }
@@ -611,7 +466,7 @@ AR_HD bool gw_publish(const GwLane<NW>& ln, GwGame<NW>& G, GwRec<NW>* rec /*[R] 
     while (mm) {
         const uint32_t idx = (uint32_t)lowest_bit(mm);
         mm &= mm - 1;
-        const uint32_t kj = (gw_sel5u(ln.vtp, idx / 5) >> (6u * (idx % 5))) & 63u;
+        const uint32_t kj = (sel5u(ln.vtp, idx / 5) >> (6u * (idx % 5))) & 63u;
         left -= 1;
         stub[slot] = gw_stub(true, false, idx, kj, ref, ln.t);
         stub_node[slot] = ln.kid[idx];  // (no lane writes this node's child table in the pass in which it publishes)

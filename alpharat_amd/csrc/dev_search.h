@@ -316,23 +316,155 @@ AR_HD uint32_t collisions_left(uint32_t node_count, const SearchCfg& c) {
 //                device-wide leaf queue (network evaluators) or the host reads them back (predict_fn)
 enum { EVAL_UNIFORM = 0, EVAL_STORE = 1 };
 
+// ---- node.rs:251-283 compute_outcomes for the 17 effective-action maps a cell can have (each of the four moves open or
+// blocked; or stuck in mud: everything is STAY), tabulated once per block by the kernels that create nodes with many
+// lanes: a new node's two maps are two LDS reads instead of two runs of pack_outcomes (~50 instructions each, executed by
+// the whole wavefront whenever any of its games creates a node, i.e. in most rounds)
+struct OutcomeTable {
+    uint32_t omap[17];
+    uint32_t n[17];
+};
+AR_HD void outcome_entry(uint32_t k, uint32_t& omap, uint32_t& n) {
+    uint32_t eff = 4u << 12;
+    if (k == 16) {
+        eff = 4u | (4u << 3) | (4u << 6) | (4u << 9) | (4u << 12);
+    } else {
+        eff |= (k & 1u) ? 4u : 0u;  // bit d set: direction d is blocked -> STAY
+        eff |= ((k & 2u) ? 4u : 1u) << 3;
+        eff |= ((k & 4u) ? 4u : 2u) << 6;
+        eff |= ((k & 8u) ? 4u : 3u) << 9;
+    }
+    pack_outcomes(eff, omap, n);
+}
+// the table key of a player at `cell` with mud timer `mud` (same case split as eff_actions, dev_engine.h)
+AR_HD uint32_t outcome_key(const uint8_t* cost, uint8_t cell, uint8_t mud) {
+    if (mud > 0) return 16u;
+    const uint32_t c = cell_costs(cost, cell);
+    return ((c & 0xffu) ? 0u : 1u) | (((c >> 8) & 0xffu) ? 0u : 2u) | (((c >> 16) & 0xffu) ? 0u : 4u) |
+           (((c >> 24) & 0xffu) ? 0u : 8u);
+}
+
+// ---- the allocation arithmetic of build_gather_level (search.rs:463-554, 775-798): every gather computes its scores,
+// thresholds and visit counts with the functions of this section, whoever holds which value ------------------------
+
+// Element `i` of a small array that lives in registers, as an OR over masked elements: a chain of `i == 0 ? a[0] : ...`
+// selects is rewritten by the optimizer into one load through a selected pointer, which pins the whole lane state in
+// scratch memory; a select between an element and zero is not.
+AR_HD uint32_t sel5u(const uint32_t* a, uint32_t i) {
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 5; ++j) r |= (i == j) ? a[j] : 0u;
+    return r;
+}
+AR_HD float sel5f(const float* a, uint32_t i) {
+    uint32_t r = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 5; ++j) r |= (i == j) ? f32_to_bits(a[j]) : 0u;
+    return bits_to_f32(r);
+}
+
+// search.rs:478-481: what an unvisited outcome counts as, from the prior mass of the visited ones (the caller sums the
+// mass in outcome order)
+AR_HD float fpu_of(float node_value, float scale, float mass, const SearchCfg& cfg) {
+    return node_value - cfg.fpu_reduction * scale * sqrtf(mass);
+}
+AR_HD float sqrt_total_of(uint32_t cv) { return sqrtf((float)(cv > 1 ? cv : 1)); }
+// search.rs:488-491: the score of an outcome with `ns` visits started
+AR_HD float puct_score(float util, float num, uint32_t ns) { return util + num / (1.0f + (float)ns); }
+
+// search.rs:478-498 for one outcome: q_norm, the exploration numerator c_puct*prior*sqrt_total, the started count and
+// the score. Returns true for a forced playout (search.rs:493-498), whose score then stays through the allocation.
+AR_HD bool outcome_terms(const Edge& e, bool live, float fpu, float scale, float sqrt_total, uint32_t cv,
+                         const SearchCfg& cfg, bool is_root, float& util, float& num, uint32_t& ns, float& score) {
+    const float q = e.visits > 0 ? e.q : fpu;
+    util = q / scale;
+    num = cfg.c_puct * e.prior * sqrt_total;
+    ns = live ? e.visits + e.nif : 0;
+    score = puct_score(util, num, ns);
+    if (live && is_root && cfg.force_k > 0.0f && e.prior > 0.0f) {
+        const float threshold = sqrtf(cfg.force_k * e.prior * (float)cv);
+        if ((float)e.visits < threshold) {
+            score = 1e20f;
+            return true;
+        }
+    }
+    return false;
+}
+
+// search.rs:775-798: an outcome's score after an allocation step. Only the started count of the chosen outcome (`hit`)
+// changes between two steps, so each step recomputes one score (same expression, same bits); a forced playout keeps its.
+AR_HD float score_after_take(float score, float util, float num, uint32_t ns, bool hit, bool forced) {
+    return (hit && !forced) ? puct_score(util, num, ns) : score;
+}
+
+// search.rs:500-532 on the five scores of a player: best and second-best in outcome order, then the tie pass, which
+// draws from the game's stream -- but only when `may_draw`; otherwise `wait` is set and nothing has been consumed (the
+// work-queue gather defers a draw until it is the game's next one in depth-first order). `drew`: the stream moved.
+AR_HD void best_of5(const float* s, uint32_t n, bool may_draw, Rng& rng, bool& wait, bool& drew, uint32_t& best_out,
+                    float& second_out) {
+    const float NEG_INF = -__builtin_inff();
+    uint32_t best = 0;
+    float best_score = NEG_INF, second = NEG_INF;
+#pragma unroll
+    for (uint32_t i = 0; i < 5; ++i) {
+        if (i < n) {
+            const float sc = s[i];
+            if (sc > best_score) {
+                second = best_score;
+                best_score = sc;
+                best = i;
+            } else if (sc > second) {
+                second = sc;
+            }
+        }
+    }
+    // (the first outcome the tie pass below would count: it is tested before any draw has moved `best`)
+    bool any_tie = false;
+#pragma unroll
+    for (uint32_t i = 0; i < 5; ++i) any_tie = any_tie || (i < n && i != best && fabsf(s[i] - best_score) < 1e-12f);
+    if (any_tie) {
+        if (!may_draw) {
+            wait = true;
+            return;
+        }
+        drew = true;
+        uint32_t ties = 1;
+#pragma unroll
+        for (uint32_t i = 0; i < 5; ++i) {
+            if (i < n && i != best && fabsf(s[i] - best_score) < 1e-12f) {  // (`best` moves with the draws, as in the reference)
+                ties += 1;
+                if (rng_below(rng, ties) == 0) best = i;
+            }
+        }
+    }
+    best_out = best;
+    second_out = second;
+}
+
+// search.rs:534-553: the visits after which the best outcome (its util, numerator and started count) stops being it
+AR_HD uint32_t vtc_of(float util, float num, uint32_t ns, float second) {
+    const float NEG_INF = -__builtin_inff();
+    if (second <= NEG_INF) return 0xFFFFFFFFu;
+    if (util >= second) return 0xFFFFFFFFu;
+    const float denom = second - util;
+    if (denom <= 0.0f) return 0xFFFFFFFFu;
+    const float n1 = (float)ns + 1.0f;
+    float vtc = num / denom - n1 + 1.0f;
+    if (!(vtc > 1.0f)) vtc = 1.0f;
+    const uint32_t k = vtc >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)vtc;
+    return k > 1 ? k : 1;
+}
+
 // ---- per-player allocation state of the node being expanded (registers) ----------------------
-// Only the started count of the chosen outcome changes between two allocation steps
-// (search.rs:775-798), so q_norm, the exploration numerator c_puct*prior*sqrt_total and the forced
-// flag are computed once per node; each step recomputes one score (same expression, same bits).
+// q_norm, the exploration numerator and the forced flag are computed once per node. The visits a step adds to an
+// outcome are counted by the caller, in the form its kernel can afford (an array in the lane kernel, whose batches go
+// to MAX_BATCH_SIZE; bit fields in the work-queue kernel).
 struct HalfAlloc {
     float score[5], util[5], num[5];
-    uint32_t ns[5], add[5], nif0[5];
+    uint32_t ns[5], nif0[5];
     uint32_t forced;  // bit i: forced-playout score (search.rs:493-498)
     uint32_t n;
 };
-
-AR_HD float pick5(const float* a, uint32_t i) {
-    return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : i == 3 ? a[3] : a[4];
-}
-AR_HD uint32_t pick5u(const uint32_t* a, uint32_t i) {
-    return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : i == 3 ? a[3] : a[4];
-}
 
 // node entry: search.rs:478-498 (fpu, sqrt_total, per-outcome score) from the loaded edges
 AR_HD void half_init(HalfAlloc& h, const Edge* e, uint32_t n, float node_value, float scale, uint32_t cv,
@@ -340,89 +472,43 @@ AR_HD void half_init(HalfAlloc& h, const Edge* e, uint32_t n, float node_value, 
     h.n = n;
     h.forced = 0;
     float mass = 0.0f;
+#pragma unroll
     for (uint32_t i = 0; i < 5; ++i)
         if (i < n && e[i].visits > 0) mass += e[i].prior;
-    const float fpu = node_value - cfg.fpu_reduction * scale * sqrtf(mass);
-    const float sqrt_total = sqrtf((float)(cv > 1 ? cv : 1));
+    const float fpu = fpu_of(node_value, scale, mass, cfg);
+    const float sqrt_total = sqrt_total_of(cv);
+#pragma unroll
     for (uint32_t i = 0; i < 5; ++i) {
-        const bool live = i < n;
-        const float q = e[i].visits > 0 ? e[i].q : fpu;
-        h.util[i] = q / scale;
-        h.num[i] = cfg.c_puct * e[i].prior * sqrt_total;
-        h.ns[i] = live ? e[i].visits + e[i].nif : 0;
+        if (outcome_terms(e[i], i < n, fpu, scale, sqrt_total, cv, cfg, is_root, h.util[i], h.num[i], h.ns[i], h.score[i]))
+            h.forced |= 1u << i;
         h.nif0[i] = e[i].nif;
-        h.add[i] = 0;
-        float sc = h.util[i] + h.num[i] / (1.0f + (float)h.ns[i]);
-        if (live && is_root && cfg.force_k > 0.0f && e[i].prior > 0.0f) {
-            const float threshold = sqrtf(cfg.force_k * e[i].prior * (float)cv);
-            if ((float)e[i].visits < threshold) {
-                sc = 1e20f;
-                h.forced |= 1u << i;
-            }
-        }
-        h.score[i] = sc;
     }
 }
 
-// search.rs:463-554 estimated_visits_to_change_best_half on the cached scores
-AR_HD void half_best(const HalfAlloc& h, Rng& rng, uint32_t& best_out, uint32_t& vtc_out) {
-    const uint32_t n = h.n;
-    if (n <= 1) {
-        best_out = 0;
-        vtc_out = 0xFFFFFFFFu;
-        return;
-    }
-    const float NEG_INF = -__builtin_inff();
-    uint32_t best = 0;
-    float best_score = NEG_INF, best_util = NEG_INF, second = NEG_INF;
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i) {
-        if (i < n) {
-            const float sc = h.score[i];
-            if (sc > best_score) {
-                second = best_score;
-                best_score = sc;
-                best = i;
-                best_util = h.util[i];
-            } else if (sc > second) {
-                second = sc;
-            }
-        }
-    }
-    uint32_t ties = 1;
-#pragma unroll
-    for (uint32_t i = 0; i < 5; ++i) {
-        if (i < n && i != best && fabsf(h.score[i] - best_score) < 1e-12f) {
-            ties += 1;
-            if (rng_below(rng, ties) == 0) {
-                best = i;
-                best_util = h.util[i];
-            }
-        }
-    }
-    best_out = best;
+// search.rs:463-554 estimated_visits_to_change_best_half on the cached scores (`may_draw`, `wait`, `drew`: best_of5)
+AR_HD void half_best(const HalfAlloc& h, bool may_draw, Rng& rng, bool& wait, bool& drew, uint32_t& best_out,
+                     uint32_t& vtc_out) {
+    best_out = 0;
     vtc_out = 0xFFFFFFFFu;
-    if (second <= NEG_INF) return;
-    if (best_util >= second) return;
-    const float denom = second - best_util;
-    if (denom <= 0.0f) return;
-    const float n1 = (float)pick5u(h.ns, best) + 1.0f;
-    float vtc = pick5(h.num, best) / denom - n1 + 1.0f;
-    if (!(vtc > 1.0f)) vtc = 1.0f;
-    const uint32_t k = vtc >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)vtc;
-    vtc_out = k > 1 ? k : 1;
+    if (h.n <= 1) return;
+    uint32_t best = 0;
+    float second = 0.0f;
+    best_of5(h.score, h.n, may_draw, rng, wait, drew, best, second);
+    if (wait) return;
+    best_out = best;
+    vtc_out = vtc_of(sel5f(h.util, best), sel5f(h.num, best), sel5u(h.ns, best), second);
 }
 
 AR_HD void half_take(HalfAlloc& h, uint32_t b, uint32_t k) {
-    // one division for the chosen outcome, then scatter with selects (no per-index divisions)
-    const uint32_t nsb = pick5u(h.ns, b) + k;
-    const float sc = pick5(h.util, b) + pick5(h.num, b) / (1.0f + (float)nsb);
-    const bool keep_forced = (h.forced >> b) & 1u;
+    // one division for the chosen outcome (the same operands for every i), then scatter with selects
+    const uint32_t nsb = sel5u(h.ns, b) + k;
+    const float util = sel5f(h.util, b), num = sel5f(h.num, b);
+    const bool forced = (h.forced >> b) & 1u;
+#pragma unroll
     for (uint32_t i = 0; i < 5; ++i) {
         const bool hit = i == b;
         h.ns[i] = hit ? nsb : h.ns[i];
-        h.add[i] += hit ? k : 0u;
-        h.score[i] = (hit && !keep_forced) ? sc : h.score[i];
+        h.score[i] = score_after_take(h.score[i], util, num, nsb, hit, forced);
     }
 }
 
@@ -571,6 +657,7 @@ struct GatherLane {
     State<NW> work;        // position at the current node
     uint32_t alloc_left;   // visits of the current node still to allocate (0: not in an allocation)
     HalfAlloc h1, h2;      // allocation state of the current node
+    uint32_t add1[5], add2[5];  // visits this allocation added to each outcome
     uint32_t kid[25];      // child table of the current node, loaded together with its record
 };
 
@@ -762,6 +849,7 @@ AR_HD void gather_round(GatherLane<NW>& g, Slot<NW>& s, const Mem<NW>& m, const 
                     const uint32_t cv = a.visits > 0 ? a.visits - 1 : 0;
                     half_init(g.h1, e1, meta_n(c.meta, 0), a.v1, b.scale, cv, cfg, from_pick);
                     half_init(g.h2, e2, meta_n(c.meta, 1), a.v2, b.scale, cv, cfg, from_pick);
+                    for (int i = 0; i < 5; ++i) g.add1[i] = g.add2[i] = 0;
                     g.node = rec;
                     g.omap0 = c.omap[0];
                     g.omap1 = c.omap[1];
@@ -781,8 +869,9 @@ AR_HD void gather_round(GatherLane<NW>& g, Slot<NW>& s, const Mem<NW>& m, const 
         for (uint32_t it = 0; it < cfg.alloc_per_round && g.alloc_left > 0; ++it) {  // search.rs:775-798, no memory traffic
             AR_COUNT(133);
             uint32_t b1, b2, c1, c2;
-            half_best(g.h1, s.rng, b1, c1);
-            half_best(g.h2, s.rng, b2, c2);
+            bool wait = false, drew = false;  // (a lane walks depth-first: it may always draw)
+            half_best(g.h1, true, s.rng, wait, drew, b1, c1);
+            half_best(g.h2, true, s.rng, wait, drew, b2, c2);
             uint32_t k = g.alloc_left;
             if (c1 < k) k = c1;
             if (c2 < k) k = c2;
@@ -792,13 +881,17 @@ AR_HD void gather_round(GatherLane<NW>& g, Slot<NW>& s, const Mem<NW>& m, const 
             g.mask |= 1u << flat;
             half_take(g.h1, b1, k);
             half_take(g.h2, b2, k);
+            for (uint32_t i = 0; i < 5; ++i) {
+                g.add1[i] += i == b1 ? k : 0u;
+                g.add2[i] += i == b2 ? k : 0u;
+            }
             g.alloc_left -= k;
         }
         if (g.alloc_left == 0) {
             NodeStats& W = m.stats[g.node];  // search.rs:800-814: write the virtual-loss deltas back
             for (uint32_t i = 0; i < 5; ++i) {
-                if (g.h1.add[i]) W.e[0][i].nif = g.h1.nif0[i] + g.h1.add[i];
-                if (g.h2.add[i]) W.e[1][i].nif = g.h2.nif0[i] + g.h2.add[i];
+                if (g.add1[i]) W.e[0][i].nif = g.h1.nif0[i] + g.add1[i];
+                if (g.add2[i]) W.e[1][i].nif = g.h2.nif0[i] + g.add2[i];
             }
         }
     }
@@ -1164,7 +1257,7 @@ AR_HD void extract_player(const Edge* e, uint32_t n, uint32_t omap, float node_v
     float mass = 0.0f;
     for (uint32_t i = 0; i < 5; ++i)
         if (i < n && e[i].visits > 0) mass += e[i].prior;
-    const float fpu = node_value - cfg.fpu_reduction * scale * sqrtf(mass);
+    const float fpu = fpu_of(node_value, scale, mass, cfg);
     float q[5], raw[5], qn[5], pruned[5];
     for (uint32_t i = 0; i < 5; ++i) {
         const bool live = i < n;
@@ -1185,7 +1278,7 @@ AR_HD void extract_player(const Edge* e, uint32_t n, uint32_t omap, float node_v
                 best_qn = qn[i];
                 best_prior = e[i].prior;
             }
-        const float sqrt_total = sqrtf((float)(cv > 1 ? cv : 1));
+        const float sqrt_total = sqrt_total_of(cv);
         const float puct_star = best_qn + cfg.c_puct * best_prior * sqrt_total / (1.0f + best_v);
 #pragma unroll
         for (uint32_t i = 0; i < 5; ++i) {
