@@ -193,6 +193,15 @@ class ArValRows(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("logits_p1", "logits_p2", "value_p1", "value_p2")]
 
 
+class ArOwnSums(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("cells", C.c_uint64), ("ce", C.c_double), ("batch_weighted", C.c_double),
+                ("batch_rows", C.c_uint64)]
+
+
+class ArOwnRows(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("ce", "cells", "value", "logits")]
+
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -234,6 +243,10 @@ EXPORTS = {
     "ar_rows_close": (None, [C.c_void_p]),
     "ar_rows_validate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(ArValSums),
                                    C.POINTER(ArValRows)]),
+    "ar_net_has_ownership": (C.c_int, [C.c_void_p]),
+    "ar_rows_validate_lv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                      C.POINTER(ArValSums), C.POINTER(ArOwnSums), C.POINTER(ArValRows),
+                                      C.POINTER(ArOwnRows)]),
 }
 
 _lib = None

@@ -1194,6 +1194,69 @@ __global__ void __launch_bounds__(64) k_val_sum(const ValAcc* partial, uint32_t 
     }
 }
 
+// The ownership terms of a chunk's rows (k_own_mfma) added to the running total by one block, without atomics. ce and
+// cells: thread t sums a contiguous segment of the rows in row order, thread 0 adds the 256 segment sums in order. With
+// `batch` > 0 the chunk (a multiple of `batch` rows, but for the request's last) is cut into consecutive batches: a thread
+// sums one batch's rows in row order and forms B_b * (ce_b / cells_b), 0 for a batch without an active cell
+// (losses/ownership.py:35-37); thread 0 adds the batches' terms in batch order.
+struct OwnAcc {
+    double ce, batch_weighted;
+    uint64_t cells;
+};
+enum { OWN_SUM_BLOCK = 256 };
+__global__ void __launch_bounds__(OWN_SUM_BLOCK)
+k_own_sum(const double* row_ce, const uint32_t* row_cells, uint32_t n, uint32_t batch, OwnAcc* total) {
+    __shared__ double s_ce[OWN_SUM_BLOCK];
+    __shared__ uint64_t s_cells[OWN_SUM_BLOCK];
+    const uint32_t t = threadIdx.x;
+    {
+        const uint64_t per = ((uint64_t)n + OWN_SUM_BLOCK - 1) / OWN_SUM_BLOCK;
+        const uint64_t lo = t * per, hi = lo + per < (uint64_t)n ? lo + per : (uint64_t)n;
+        double ce = 0.0;
+        uint64_t cells = 0;
+        for (uint64_t i = lo; i < hi; ++i) {
+            ce += row_ce[i];
+            cells += row_cells[i];
+        }
+        s_ce[t] = ce;
+        s_cells[t] = cells;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double ce = total->ce;
+        uint64_t cells = total->cells;
+        for (int j = 0; j < OWN_SUM_BLOCK; ++j) {
+            ce += s_ce[j];
+            cells += s_cells[j];
+        }
+        total->ce = ce;
+        total->cells = cells;
+    }
+    if (batch == 0) return;
+    const uint32_t n_batches = (uint32_t)(((uint64_t)n + batch - 1) / batch);
+    for (uint32_t b0 = 0; b0 < n_batches; b0 += OWN_SUM_BLOCK) {
+        __syncthreads();  // thread 0 is done with s_ce
+        double term = 0.0;
+        if (b0 + t < n_batches) {
+            const uint64_t lo = (uint64_t)(b0 + t) * batch, hi = lo + batch < (uint64_t)n ? lo + batch : (uint64_t)n;
+            double ce = 0.0;
+            uint64_t cells = 0;
+            for (uint64_t i = lo; i < hi; ++i) {
+                ce += row_ce[i];
+                cells += row_cells[i];
+            }
+            term = cells ? (double)(hi - lo) * (ce / (double)cells) : 0.0;
+        }
+        s_ce[t] = term;
+        __syncthreads();
+        if (t == 0) {
+            double v = total->batch_weighted;
+            for (uint32_t j = 0; j < OWN_SUM_BLOCK && b0 + j < n_batches; ++j) v += s_ce[j];
+            total->batch_weighted = v;
+        }
+    }
+}
+
 // arena growth: what a stalled slot reports, and its new home once the host has copied the nodes
 struct StallInfo {
     uint32_t slot, cap, hi, need;
@@ -2843,6 +2906,14 @@ struct RowStore {
     DevBuf<float> val_logits;
     DevBuf<ValAcc> val_partial, val_total;
     uint32_t val_chunk = 0;
+    // ar_rows_validate_lv: the trunk output of a chunk ([chunk][H]), its rows' ownership terms and, when the caller asks
+    // for them, the head's logits ([chunk][hw][4]); grown like the workspace above
+    DevBuf<float> own_feat, own_value, own_logits;
+    DevBuf<double> own_ce;
+    DevBuf<uint32_t> own_cells;
+    DevBuf<OwnAcc> own_total;
+    size_t own_feat_n = 0, own_logits_n = 0;
+    uint32_t own_chunk = 0;
     // uploads and builds run on the null stream: they wait for the attached session's last append, nothing else
     hipError_t wait_appends() const { return has_append ? hipEventSynchronize(ev_append) : hipSuccess; }
 
@@ -3196,9 +3267,14 @@ static hipError_t regrow(DevBuf<T>& b, size_t count) {
 // evaluator with its logits output (net_launch), the terms of every row summed per block (k_val_terms) and added to the
 // running total (k_val_sum) -- all on the null stream; blocks until the sums are on the host. No observation, no target
 // array and, without `ro`, no per-row output leaves the device.
+//
+// ar_rows_validate_lv (`own` set): the evaluator launch is the one that also stores its trunk output, and behind it run the
+// ownership head with its row terms (k_own_mfma) and their reduction (k_own_sum, batches of `loss_batch` rows); the
+// launches that ar_rows_validate makes are the same ones with the same arguments, so `sums` and `ro` get the same bytes.
 enum { VAL_DEFAULT_CHUNK = 65536 };
 template <int NW>
-int rows_validate(RowStore& R, ArNet* net, const uint64_t* rows, uint64_t n, uint32_t chunk, ArValSums& sums, const ArValRows* ro) {
+int rows_validate(RowStore& R, ArNet* net, const uint64_t* rows, uint64_t n, uint32_t chunk, ArValSums& sums, const ArValRows* ro,
+                  uint32_t loss_batch = 0, ArOwnSums* own = nullptr, const ArOwnRows* oro = nullptr) {
     for (uint64_t i = 0; i < n; ++i)
         if (rows[i] >= R.n_pos)
             return fail(AR_E_INVALID, "row " + std::to_string(i) + " asks for position " + std::to_string(rows[i]) +
@@ -3213,13 +3289,45 @@ int rows_validate(RowStore& R, ArNet* net, const uint64_t* rows, uint64_t n, uin
     const size_t n_games = R.h_games.size();
     if ((uint64_t)n_games * R.hw * 4u > 0xFFFFFFFFull)  // Board::maze_off is 32 bits wide
         return fail(AR_E_INVALID, "the row set holds more games than an evaluator's maze pool can address");
+    if (own) own->batch_rows = loss_batch;
     if (n == 0) return AR_OK;
     if (chunk == 0) chunk = VAL_DEFAULT_CHUNK;
+    if (own && loss_batch) {  // no batch straddles two chunks
+        uint64_t c = ((uint64_t)chunk + loss_batch - 1) / loss_batch * loss_batch;
+        if (c > n) c = n;
+        if (c > 0xFFFFFFFFull) return fail(AR_E_INVALID, "loss_batch_rows does not fit a chunk of the request");
+        chunk = (uint32_t)c;
+    }
     if ((uint64_t)chunk > n) chunk = (uint32_t)n;
     HIP_TRY(hipSetDevice(R.device));
     HIP_TRY(R.wait_appends());
     HIP_TRY(R.wait_batches());
     const uint32_t max_blocks = (chunk + VAL_BLOCK - 1) / VAL_BLOCK;
+    if (own) {
+        const size_t feat_n = (size_t)chunk * net->dev.H, logits_n = oro && oro->logits ? (size_t)chunk * R.hw * 4 : 0;
+        bool ok = true;
+        if (feat_n > R.own_feat_n) {
+            R.own_feat_n = 0;
+            ok = regrow(R.own_feat, feat_n) == hipSuccess;
+            if (ok) R.own_feat_n = feat_n;
+        }
+        if (ok && chunk > R.own_chunk) {
+            R.own_chunk = 0;
+            ok = regrow(R.own_ce, chunk) == hipSuccess && regrow(R.own_cells, chunk) == hipSuccess &&
+                 regrow(R.own_value, chunk) == hipSuccess && (R.own_total.p || R.own_total.alloc(1) == hipSuccess);
+            if (ok) R.own_chunk = chunk;
+        }
+        if (ok && logits_n > R.own_logits_n) {
+            R.own_logits_n = 0;
+            ok = regrow(R.own_logits, logits_n) == hipSuccess;
+            if (ok) R.own_logits_n = logits_n;
+        }
+        if (!ok) {
+            (void)hipGetLastError();
+            return fail(AR_E_NOMEM, "not enough device memory to validate " + std::to_string(chunk) +
+                                        " rows at a time with the ownership head");
+        }
+    }
     if (chunk > R.val_chunk) {
         R.val_chunk = 0;
         if (regrow(R.val_rows, chunk) != hipSuccess || regrow(R.val_req, (size_t)chunk * sizeof(LeafReq<NW>)) != hipSuccess ||
@@ -3256,12 +3364,14 @@ int rows_validate(RowStore& R, ArNet* net, const uint64_t* rows, uint64_t n, uin
         net->bound_stamp = R.stamp;
     }
     HIP_TRY(hipMemsetAsync(R.val_total.p, 0, sizeof(ValAcc), nullptr));
+    if (own) HIP_TRY(hipMemsetAsync(R.own_total.p, 0, sizeof(OwnAcc), nullptr));
     std::vector<EvalOut> h_out;
     std::vector<float> h_logits;
     if (ro) {
         h_out.resize(chunk);
         h_logits.resize((size_t)chunk * 10);
     }
+    float* own_logits = own && oro && oro->logits ? R.own_logits.p : nullptr;
     const PosRec<NW>* recs = (const PosRec<NW>*)R.recs.p;
     LeafReq<NW>* req = (LeafReq<NW>*)R.val_req.p;
     for (uint64_t row0 = 0; row0 < n; row0 += chunk) {
@@ -3272,8 +3382,23 @@ int rows_validate(RowStore& R, ArNet* net, const uint64_t* rows, uint64_t n, uin
                            (const uint64_t*)R.val_rows.p, cnt, req);
         HIP_TRY(hipGetLastError());
         if (int rc = net_launch<NW>(net, req, nullptr, cnt, (const char*)R.val_boards.p, sizeof(Board), R.val_out.p,
-                                    R.val_logits.p, nullptr))
+                                    R.val_logits.p, nullptr, own ? R.own_feat.p : nullptr))
             return rc;
+        if (own) {
+            if (int rc = net_launch_own<NW>(net, R.own_feat.p, req, R.outcomes.p, cnt, R.own_ce.p, R.own_cells.p, R.own_value.p,
+                                            own_logits, nullptr))
+                return rc;
+            hipLaunchKernelGGL(k_own_sum, dim3(1), dim3(OWN_SUM_BLOCK), 0, nullptr, (const double*)R.own_ce.p,
+                               (const uint32_t*)R.own_cells.p, cnt, loss_batch, R.own_total.p);
+            HIP_TRY(hipGetLastError());
+            if (oro) {
+                if (oro->ce) HIP_TRY(hipMemcpy(oro->ce + row0, R.own_ce.p, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+                if (oro->cells) HIP_TRY(hipMemcpy(oro->cells + row0, R.own_cells.p, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+                if (oro->value) HIP_TRY(hipMemcpy(oro->value + row0, R.own_value.p, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+                if (oro->logits)
+                    HIP_TRY(hipMemcpy(oro->logits + row0 * R.hw * 4, own_logits, (size_t)cnt * R.hw * 16, hipMemcpyDeviceToHost));
+            }
+        }
         hipLaunchKernelGGL(k_val_terms<NW>, dim3(blocks), dim3(VAL_BLOCK), 0, nullptr, recs, (const uint32_t*)R.pos_game.p,
                            (const RowGame*)R.games.p, (const uint64_t*)R.val_rows.p, cnt, (const float*)R.val_logits.p,
                            (const EvalOut*)R.val_out.p, R.val_partial.p);
@@ -3293,6 +3418,14 @@ int rows_validate(RowStore& R, ArNet* net, const uint64_t* rows, uint64_t n, uin
     }
     ValAcc total;
     HIP_TRY(hipMemcpy(&total, R.val_total.p, sizeof total, hipMemcpyDeviceToHost));  // (waits for the null stream)
+    if (own) {
+        OwnAcc ot;
+        HIP_TRY(hipMemcpy(&ot, R.own_total.p, sizeof ot, hipMemcpyDeviceToHost));
+        own->n = n;
+        own->cells = ot.cells;
+        own->ce = ot.ce;
+        own->batch_weighted = ot.batch_weighted;
+    }
     sums.n = n;
     for (int p = 0; p < 2; ++p) {
         const double* d = total.d + VAL_D_PER_PLAYER * p;
@@ -4779,6 +4912,26 @@ int ar_rows_validate(ArRowSet* s, ArNet* net, const uint64_t* rows, uint64_t n, 
     return rc;
 }
 
+int ar_rows_validate_lv(ArRowSet* s, ArNet* net, const uint64_t* rows, uint64_t n, uint32_t chunk_rows, uint32_t loss_batch_rows,
+                        ArValSums* sums, ArOwnSums* own, const ArValRows* rows_out, const ArOwnRows* own_out) {
+    if (!s || !s->impl || !net || !sums || !own || (!rows && n)) return fail(AR_E_INVALID, "null argument");
+    if (!net->has_own)
+        return fail(AR_E_INVALID, "the network has no ownership head (an mlp blob written with keep_ownership, hidden width a "
+                                  "multiple of 32 up to 256)");
+    ArValSums out;
+    ArOwnSums oout;
+    memset(&out, 0, sizeof out);
+    memset(&oout, 0, sizeof oout);
+    const int rc = s->impl->nw == 1
+                       ? rows_validate<1>(*s->impl, net, rows, n, chunk_rows, out, rows_out, loss_batch_rows, &oout, own_out)
+                       : rows_validate<4>(*s->impl, net, rows, n, chunk_rows, out, rows_out, loss_batch_rows, &oout, own_out);
+    if (rc == AR_OK) {
+        *sums = out;
+        *own = oout;
+    }
+    return rc;
+}
+
 // ---- matches: tournament.py:329-373 / eval/game.py:47-87 / searcher_agent.py:40-56 on the device --------------
 int ar_match_run(const ArMatchParams* p, ArMatchSink sink, void* sink_user, ArMatchStats* out) {
     if (!p || !out) return fail(AR_E_INVALID, "null argument");
@@ -4841,6 +4994,8 @@ int ar_net_load(const char* blob_path, int device, ArNet** out) {
 }
 
 void ar_net_free(ArNet* net) { delete net; }
+
+int ar_net_has_ownership(const ArNet* net) { return net && net->has_own ? 1 : 0; }
 
 }  // extern "C"
 

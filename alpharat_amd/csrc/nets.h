@@ -1100,12 +1100,15 @@ __global__ void k_encode(const ar::LeafReq<NW>* q, uint32_t n, const ar::Board* 
 }  // namespace arnet
 
 #include "nets_cnn.h"
+#include "nets_ownership.h"
 
 // ---- host object --------------------------------------------------------------------------------
 struct ArNet {
     int device = 0;
     arnet::NetDev dev;
     arnet::CnnDev cnn;
+    arnet::OwnDev own = {};  // LocalValueMLP's ownership head (an mlp blob that carries it, hidden width on the matrix cores)
+    bool has_own = false;
     std::vector<void*> allocs;
     float* cmaze = nullptr;
     const uint8_t* bound_pool = nullptr;
@@ -1256,6 +1259,37 @@ static int net_build(const arnet::Blob& b, ArNet* net) {
         d.n_head = 12;
         d.Kh = d.H;
         net->smem = mlp_smem_bytes(d.H);
+        // LocalValueMLP's ownership head (weights.py keep_ownership): all four tensors, or none
+        const char* own_names[4] = {"ownership_head.0.weight", "ownership_head.0.bias", "ownership_head.2.weight",
+                                    "ownership_head.2.bias"};
+        int present = 0;
+        for (const char* k : own_names) present += b.get(k) ? 1 : 0;
+        if (present) {
+            const uint32_t H = (uint32_t)d.H, N = 4u * (uint32_t)d.hw;
+            const std::vector<float>* w1 = b.get(own_names[0], {H, H}, err);
+            const std::vector<float>* b1 = w1 ? b.get(own_names[1], {H}, err) : nullptr;
+            const std::vector<float>* w2 = b1 ? b.get(own_names[2], {N, H}, err) : nullptr;
+            const std::vector<float>* b2 = w2 ? b.get(own_names[3], {N}, err) : nullptr;
+            if (!b2) return nets_fail(AR_E_BACKEND, err);
+            if (mlp_all_mfma(d.H)) {  // (other widths: the net loads as the plain blob does and reports no ownership head)
+                OwnDev& o = net->own;
+                o.H = d.H;
+                o.hw = d.hw;
+                o.Npad = (int)((N + 63u) & ~63u);
+                std::vector<float> w1t((size_t)H * H), w2t((size_t)H * o.Npad, 0.0f), b2p((size_t)o.Npad, 0.0f);
+                for (uint32_t out_i = 0; out_i < H; ++out_i)
+                    for (uint32_t k = 0; k < H; ++k) w1t[(size_t)k * H + out_i] = (*w1)[(size_t)out_i * H + k];
+                for (uint32_t out_i = 0; out_i < N; ++out_i) {
+                    for (uint32_t k = 0; k < H; ++k) w2t[(size_t)k * o.Npad + out_i] = (*w2)[(size_t)out_i * H + k];
+                    b2p[out_i] = (*b2)[out_i];
+                }
+                o.w1t = net->upload(w1t, ok);
+                o.b1 = net->upload(*b1, ok);
+                o.w2t = net->upload(w2t, ok);
+                o.b2 = net->upload(b2p, ok);
+                net->has_own = true;
+            }
+        }
     } else if (b.arch == ARCH_SYMMETRIC) {
         if (!fold_linear(b, "shared_encoder.0", "shared_encoder.1", wt, bias, in, out, err)) return nets_fail(AR_E_BACKEND, err);
         if ((int)in != d.hw * 5 + 1) return nets_fail(AR_E_BACKEND, "SymmetricMLP input width does not match the board size");
@@ -1471,10 +1505,12 @@ static int net_rebind_mazes(ArNet* net, const uint32_t* d_ids, int n, hipStream_
 
 template <int NW>
 static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcount, uint32_t n_max, const char* boards,
-                      size_t board_stride, ar::EvalOut* out, float* logits, hipStream_t stream) {
+                      size_t board_stride, ar::EvalOut* out, float* logits, hipStream_t stream, float* feat = nullptr) {
     using namespace arnet;
     if (n_max == 0) return AR_OK;
     const bool mlp_mfma = net->dev.arch == ARCH_MLP && mlp_all_mfma(net->dev.H);
+    // `feat` (the trunk's output, [n_max][H]) is written by k_mlp_mfma_feat alone
+    if (feat && !mlp_mfma) return nets_fail(AR_E_INVALID, "this network's evaluator does not give its trunk output");
     // (k_symmetric_mfma2 stages the shared encoder's operand, hw + 1 values, at the head of a row of its buffer)
     const bool sym_mfma = net->dev.arch == ARCH_SYMMETRIC && symmetric_mfma_ok(net->dev.H) && !getenv("AR_SYM_FMA") &&
                           ((net->dev.hw + 2) & ~1) <= net->dev.H + 4;
@@ -1508,11 +1544,21 @@ static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcou
         if (fl == 0 && K1e > net->dev.H + 4) fl = 1;
         decltype(&k_mlp_mfma<NW, MLP_MFMA_MT, 0>) const fns[3] = {k_mlp_mfma<NW, MLP_MFMA_MT, 0>, k_mlp_mfma<NW, MLP_MFMA_MT, 1>,
                                                                    k_mlp_mfma<NW, MLP_MFMA_MT, 2>};
-        if (smem > 48 * 1024 &&
-            hipFuncSetAttribute((const void*)fns[fl], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the MLP kernel");
-        hipLaunchKernelGGL(fns[fl], dim3(blocks), dim3(NTHREADS), smem, stream, net->dev, q, qcount, n_max, boards, board_stride,
-                           out, logits);
+        if (feat) {
+            decltype(&k_mlp_mfma_feat<NW, MLP_MFMA_MT, 0>) const ffns[3] = {
+                k_mlp_mfma_feat<NW, MLP_MFMA_MT, 0>, k_mlp_mfma_feat<NW, MLP_MFMA_MT, 1>, k_mlp_mfma_feat<NW, MLP_MFMA_MT, 2>};
+            if (smem > 48 * 1024 &&
+                hipFuncSetAttribute((const void*)ffns[fl], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+                return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the MLP kernel");
+            hipLaunchKernelGGL(ffns[fl], dim3(blocks), dim3(NTHREADS), smem, stream, net->dev, q, qcount, n_max, boards,
+                               board_stride, out, logits, feat);
+        } else {
+            if (smem > 48 * 1024 &&
+                hipFuncSetAttribute((const void*)fns[fl], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+                return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the MLP kernel");
+            hipLaunchKernelGGL(fns[fl], dim3(blocks), dim3(NTHREADS), smem, stream, net->dev, q, qcount, n_max, boards,
+                               board_stride, out, logits);
+        }
     } else if (net->dev.arch == ARCH_MLP) {
         if (net->smem > 48 * 1024 &&
             hipFuncSetAttribute((const void*)k_mlp<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)net->smem) !=
@@ -1537,6 +1583,24 @@ static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcou
     }
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) return nets_fail(AR_E_DEVICE, std::string("network kernel launch failed: ") + hipGetErrorString(le));
+    return AR_OK;
+}
+
+// the ownership head and its loss terms over requests whose trunk output `feat` net_launch stored (k_own_mfma)
+template <int NW>
+static int net_launch_own(ArNet* net, const float* feat, const ar::LeafReq<NW>* q, const uint8_t* outcomes, uint32_t n,
+                          double* row_ce, uint32_t* row_cells, float* row_value, float* logits, hipStream_t stream) {
+    using namespace arnet;
+    if (n == 0) return AR_OK;
+    if (!net->has_own) return nets_fail(AR_E_INVALID, "the network has no ownership head");
+    const size_t smem = own_smem_bytes(net->own.H);
+    // (always: the kernel's static LDS, 40 KB, counts towards the default limit too)
+    if (hipFuncSetAttribute((const void*)k_own_mfma<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+        return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the ownership kernel");
+    hipLaunchKernelGGL(k_own_mfma<NW>, dim3((n + OWN_ROWS - 1) / OWN_ROWS), dim3(NTHREADS), smem, stream, net->own, feat, q,
+                       outcomes, n, row_ce, row_cells, row_value, logits);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return nets_fail(AR_E_DEVICE, std::string("ownership kernel launch failed: ") + hipGetErrorString(le));
     return AR_OK;
 }
 

@@ -106,6 +106,11 @@ class RowDataset:
         over the val half of a split (``alpharat_amd.validate``). Needs no order and disturbs none."""
         return self.rowset.validate(net, self._positions, chunk_rows, return_rows)
 
+    def validate_lv(self, net, chunk_rows: int = 0, loss_batch_rows: int = 0, return_rows: bool = False):
+        """``validate`` for a ``local_value`` net with its ownership head, over this dataset's ``positions`` in their order
+        (the batches of ``loss_batch_rows`` are cut from it): ``(ValSums, OwnSums[, outputs])``."""
+        return self.rowset.validate_lv(net, self._positions, chunk_rows, loss_batch_rows, return_rows)
+
     def epoch_iter(self, batch_size: int, *, epoch: int = 0, seed: int = 0, augment: bool = True, p_swap: float = 0.5,
                    shuffle: bool = True, drop_last: bool = True) -> Iterator[dict]:
         """One epoch as dicts of device tensors in ``GPUDataset``'s shapes: observation ``(N, h*w*7+6)`` and policies

@@ -28,6 +28,12 @@ class Net:
 
         return cls(checkpoint_to_blob(checkpoint), device)
 
+    @property
+    def has_ownership(self) -> bool:
+        """the blob carried LocalValueMLP's ownership head (``checkpoint_to_blob(..., keep_ownership=True)``) and it was
+        built: what ``alpharat_amd.validate.validate_lv`` needs"""
+        return bool(self.handle) and bool(_lib.load().ar_net_has_ownership(self.handle))
+
     def close(self) -> None:
         if getattr(self, "handle", None):
             _lib.load().ar_net_free(self.handle)

@@ -224,6 +224,13 @@ class RowSet:
 
         return validate(self, net, rows, chunk_rows, return_rows)
 
+    def validate_lv(self, net, rows, chunk_rows: int = 0, loss_batch_rows: int = 0, return_rows: bool = False):
+        """``validate`` for a ``local_value`` net with its ownership head: ``(ValSums, OwnSums[, outputs])``
+        (``alpharat_amd.validate.validate_lv``)."""
+        from .validate import validate_lv
+
+        return validate_lv(self, net, rows, chunk_rows, loss_batch_rows, return_rows)
+
     def clear(self) -> None:
         """Forgets the games, and the order with them."""
         _lib.check(_lib.load().ar_rows_clear(self._handle()))

@@ -11,7 +11,13 @@ Tensor names are the torch ``state_dict`` keys; integer buffers (num_batches_tra
 
 A ``local_value`` checkpoint (LocalValueMLP, ``alpharat/nn/models/local_value.py``) becomes an ``mlp`` blob: at
 inference it is PyRatMLP (same trunk, policy and value heads; ``predict()`` takes its values from
-``value_head``), so its auxiliary ``ownership_head.*`` and the ``outcome_values`` buffer are left out.
+``value_head``), so by default its auxiliary ``ownership_head.*`` and the ``outcome_values`` buffer are left out.
+
+``checkpoint_to_blob(pt, keep_ownership=True)`` keeps ``ownership_head.0.{weight,bias}`` and
+``ownership_head.2.{weight,bias}`` in that ``mlp`` blob (written as ``<stem>.lv.arnet``, beside the default
+``<stem>.arnet``): the loader then also builds the ownership head, which ``alpharat_amd.validate.validate_lv``
+needs for the architecture's validation loss. Samplers and evaluators do with such a blob what they do with the
+plain one. ``outcome_values`` is still dropped: it is the constant [1, 0, 0, -1].
 """
 from __future__ import annotations
 
@@ -77,14 +83,17 @@ def read_blob(path: str | Path) -> tuple[str, int, int, dict[str, np.ndarray]]:
     return arch, width, height, out
 
 
-def checkpoint_to_blob(checkpoint_path: str | Path, blob_path: str | Path | None = None) -> Path:
+def checkpoint_to_blob(checkpoint_path: str | Path, blob_path: str | Path | None = None,
+                       keep_ownership: bool = False) -> Path:
     """``.pt`` checkpoint (``alpharat/nn/training/loop.py:392-424`` layout: ``model_state_dict``,
     ``config.model.architecture``, ``width``, ``height``) -> blob next to it (``.arnet``), cached
-    like the reference caches ``.onnx`` next to the ``.pt``."""
+    like the reference caches ``.onnx`` next to the ``.pt``. ``keep_ownership``: a ``local_value`` checkpoint keeps
+    its ownership head (default name ``<stem>.lv.arnet``, a cache of its own); any other architecture raises
+    ``ValueError``."""
     import torch
 
     pt = Path(checkpoint_path)
-    blob = Path(blob_path) if blob_path is not None else pt.with_suffix(".arnet")
+    blob = Path(blob_path) if blob_path is not None else pt.with_suffix(".lv.arnet" if keep_ownership else ".arnet")
     if blob.exists() and blob.stat().st_mtime >= pt.stat().st_mtime:
         return blob
     ckpt = torch.load(pt, map_location="cpu", weights_only=True)
@@ -98,7 +107,10 @@ def checkpoint_to_blob(checkpoint_path: str | Path, blob_path: str | Path | None
     missing = [k for k in _REQUIRED.get(arch, ()) if k not in sd]
     if missing:
         raise ValueError(f"unsupported architecture {arch!r} layout in {pt}: the state_dict lacks {', '.join(missing)}")
+    if keep_ownership and arch != "local_value":
+        raise ValueError(f"keep_ownership: {pt} is a {arch!r} checkpoint, only 'local_value' has an ownership head")
     if arch == "local_value":  # PyRatMLP at inference time
         arch = "mlp"
-        sd = {k: v for k, v in sd.items() if not k.startswith("ownership_head.") and k != "outcome_values"}
+        sd = {k: v for k, v in sd.items()
+              if (keep_ownership or not k.startswith("ownership_head.")) and k != "outcome_values"}
     return write_blob(blob, arch, int(width), int(height), sd)

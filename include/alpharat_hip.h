@@ -434,6 +434,45 @@ typedef struct ArValRows {
 int ar_rows_validate(ArRowSet* set, ArNet* net, const uint64_t* rows, uint64_t n, uint32_t chunk_rows, ArValSums* sums,
                      const ArValRows* rows_out);
 
+/* ---- validation of a local_value checkpoint (LocalValueMLP) with its ownership head ------------------------------------
+ * The reference's val/loss for that architecture adds ownership_weight * loss_ownership
+ * (architectures/local_value/loss.py:55-59): the cross-entropy of the head's per-cell logits [hw][4] against the game's
+ * cheese outcomes over the cells that still hold their cheese (losses/ownership.py:26-46). The head is in an mlp blob that
+ * alpharat_amd/weights.py wrote with keep_ownership (ownership_head.0 / .2, all four tensors or none; wrong shapes:
+ * AR_E_BACKEND at load) and is built where the hidden width runs on the matrix cores (a multiple of 32, at most 256);
+ * sampling, ar_net_evaluate and ar_rows_validate do with such a net exactly what they do with the plain blob.
+ * 1 if `net` has the head, else 0 (a null net too). */
+int ar_net_has_ownership(const ArNet* net);
+/* ce and cells are additive over rows: the sum over active cells of logsumexp(l) - l[outcome], and their number. The
+ * reference does not pool: per batch it takes ce_b / cells_b (0.0 for a batch without an active cell) and averages the
+ * batches weighted by their size. With loss_batch_rows > 0 the request is cut into consecutive batches of that many rows,
+ * the last one short: batch_weighted = sum_b B_b * (ce_b / cells_b), batch sums taken in row order. With
+ * loss_batch_rows == 0, batch_weighted and batch_rows are 0. */
+typedef struct ArOwnSums {
+    uint64_t n, cells;
+    double ce;
+    double batch_weighted;
+    uint64_t batch_rows;
+} ArOwnSums;
+/* per-row outputs in request order, host memory; any array may be NULL. A row's ce and value (the reference's
+ * ownership_value under cheese_mask = cheese_outcomes >= 0) are sums over its active cells in increasing cell order,
+ * accumulated in double from f32 terms. */
+typedef struct ArOwnRows {
+    double* ce;      /* [n]        */
+    uint32_t* cells; /* [n]        */
+    float* value;    /* [n]        */
+    float* logits;   /* [n][hw][4] */
+} ArOwnRows;
+/* Everything ar_rows_validate does, with the same checks, refusals and waits; the evaluator also stores its trunk output,
+ * from which the ownership head and the terms of every row are computed. chunk_rows is rounded up to a multiple of
+ * loss_batch_rows. The workspace grows by chunk * H floats (64 MB at the default chunk and H = 256), 16 bytes a row and,
+ * only when own_out->logits is asked for, chunk * hw * 16 bytes. *sums and rows_out are the bytes ar_rows_validate gives
+ * for the same request in the same chunks. Additionally AR_E_INVALID with nothing touched: a net without an ownership
+ * head, a null `own`. rows_out and own_out may be NULL. */
+int ar_rows_validate_lv(ArRowSet* set, ArNet* net, const uint64_t* rows, uint64_t n, uint32_t chunk_rows,
+                        uint32_t loss_batch_rows, ArValSums* sums, ArOwnSums* own, const ArValRows* rows_out,
+                        const ArOwnRows* own_out);
+
 #ifdef __cplusplus
 }
 #endif
