@@ -571,6 +571,59 @@ __device__ inline void mfma_pass(const float* bp0, bool two, int K, int H, int h
     }
 }
 
+// The chain starts of FL == 2 (k_mlp_mfma explains them): act[l][:] = (maze constant + row of the p1 cell) + row of the
+// p2 cell, 16 bytes per item. L H/4 items over the block's threads is exactly L H / (4 NTHREADS) per thread (H % 32 == 0),
+// so the loop has that trip count and no bound per item -- a guarded item is a branch, and the compiler then waits out
+// each item's loads before it issues the next item's. A pass issues the 3 N loads of N items before it stores the first
+// sum; item i of a thread is tid + i NTHREADS, walked as (leaf, column) without a division per item.
+template <int N>
+__device__ inline void mlp_chain_starts_pass(const NetDev& net, const LeafFeat* feat, float* act, int H4, int dq, int dr,
+                                             int& l, int& c4) {
+    const int H = net.H, hw = net.hw, ld = H + 4;
+    float4 a[N], b[N], c[N];
+    float* dst[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const LeafFeat& f = feat[l];
+        a[i] = ((const float4*)(net.cmaze + (size_t)f.maze_id * H))[c4];
+        b[i] = ((const float4*)(net.w1t + (size_t)(4 * hw + f.p1) * H))[c4];
+        c[i] = ((const float4*)(net.w1t + (size_t)(5 * hw + f.p2) * H))[c4];
+        dst[i] = act + (size_t)l * ld + 4 * c4;
+        l += dq;
+        c4 += dr;
+        if (c4 >= H4) {
+            c4 -= H4;
+            ++l;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        float4 sum;
+        sum.x = (a[i].x + b[i].x) + c[i].x;
+        sum.y = (a[i].y + b[i].y) + c[i].y;
+        sum.z = (a[i].z + b[i].z) + c[i].z;
+        sum.w = (a[i].w + b[i].w) + c[i].w;
+        *(float4*)dst[i] = sum;
+    }
+}
+template <int L>
+__device__ inline void mlp_chain_starts(const NetDev& net, const LeafFeat* feat, float* act, int tid) {
+    // H itself is not checked here: the host launches these kernels only where mlp_all_mfma(H) holds (H % 32 == 0,
+    // H <= 256), so H4 is a multiple of 8 and at most NTHREADS / 4
+    static_assert((L * 8) % (2 * NTHREADS) == 0, "an even number of items per thread wherever mlp_all_mfma(H) holds");
+    const int H4 = net.H >> 2;
+    const int n_items = L * H4 / NTHREADS;
+    const int dq = NTHREADS / H4, dr = NTHREADS - dq * H4;  // the step from one item of a thread to its next
+    int l = tid / H4, c4 = tid - l * H4;
+    int i = 0;
+    for (; i + 8 <= n_items; i += 8) mlp_chain_starts_pass<8>(net, feat, act, H4, dq, dr, l, c4);
+    if (i + 4 <= n_items) {
+        mlp_chain_starts_pass<4>(net, feat, act, H4, dq, dr, l, c4);
+        i += 4;
+    }
+    if (i + 2 <= n_items) mlp_chain_starts_pass<2>(net, feat, act, H4, dq, dr, l, c4);
+}
+
 // (amdgpu_num_vgpr: with the limit the compiler keeps the accumulators in ordinary vector registers and needs 148 in all,
 // without it 130 + 64 accumulator registers = 196 (200 allocated): two such wavefronts leave a SIMD 112 of its 512
 // registers, and a tree-reuse wavefront (k_advance: 128) on a SIMD then kept the CU's second evaluator workgroup out for
@@ -618,20 +671,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))
         //   (maze constant + row of the p1 cell) + row of the p2 cell
         // -- the same bits -- and the matrix cores only take the hw + 6 cheese and scalar rows: 28 k-steps instead of 77
         // at 7x7. The starts are summed 16 bytes at a time into `act` and picked up from there in accumulator layout.
-        const int H4 = H >> 2;
-        for (int item = tid; item < L * H4; item += NTHREADS) {
-            const int l = item / H4, c4 = item - l * H4;
-            const LeafFeat& f = feat[l];
-            const float4 a = ((const float4*)(net.cmaze + (size_t)f.maze_id * H))[c4];
-            const float4 b = ((const float4*)(net.w1t + (size_t)(4 * hw + f.p1) * H))[c4];
-            const float4 c = ((const float4*)(net.w1t + (size_t)(5 * hw + f.p2) * H))[c4];
-            float4 sum;
-            sum.x = (a.x + b.x) + c.x;
-            sum.y = (a.y + b.y) + c.y;
-            sum.z = (a.z + b.z) + c.z;
-            sum.w = (a.w + b.w) + c.w;
-            *(float4*)(act + (size_t)l * ld + 4 * c4) = sum;
-        }
+        mlp_chain_starts<L>(net, feat, act, tid);
         __syncthreads();
     }
     if (staged) {

@@ -75,20 +75,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))
     const int K1 = 3 * hw + 6, K1e = (K1 + 1) & ~1;
     constexpr bool staged = FL == 0;
     if (FL == 2) {
-        const int H4 = H >> 2;
-        for (int item = tid; item < L * H4; item += NTHREADS) {
-            const int l = item / H4, c4 = item - l * H4;
-            const LeafFeat& f = feat[l];
-            const float4 a = ((const float4*)(net.cmaze + (size_t)f.maze_id * H))[c4];
-            const float4 b = ((const float4*)(net.w1t + (size_t)(4 * hw + f.p1) * H))[c4];
-            const float4 c = ((const float4*)(net.w1t + (size_t)(5 * hw + f.p2) * H))[c4];
-            float4 sum;
-            sum.x = (a.x + b.x) + c.x;
-            sum.y = (a.y + b.y) + c.y;
-            sum.z = (a.z + b.z) + c.z;
-            sum.w = (a.w + b.w) + c.w;
-            *(float4*)(act + (size_t)l * ld + 4 * c4) = sum;
-        }
+        mlp_chain_starts<L>(net, feat, act, tid);
         __syncthreads();
     }
     if (staged) {
