@@ -571,23 +571,119 @@ __device__ inline void mfma_pass(const float* bp0, bool two, int K, int H, int h
     }
 }
 
+// mfma_pass for a kernel that is short of registers (k_mlp_mfma_halves): the same ring, chunks and guards, the same
+// products in the same order, going on from whatever `c` holds. Only the weight addresses differ. mfma_pass ends up with
+// a 64-bit pointer for each of its 2 R loads, 34 registers; here the loads are buffer loads from rows [0, K) of `w`
+// (wave-uniform: the descriptor sits in scalar registers): a lane gives one 32-bit byte offset per ring slot, `lane_off`
+// (its row h and its column in the first tile) + 2 j rows, R registers in all, and the chunk's first row and the
+// distance d1 to the second column tile (in floats; 0 without one) go into the instruction's scalar offset.
+// The first chunk's loads are a call of their own (mfma_rows_prime), so that a kernel can issue them in front of the
+// barriers and LDS writes that precede a pass and not wait out their round trip behind them.
+template <int R>
+__device__ inline void mfma_rows_prime(const float* w, int d1, uint32_t lane_off, int K, int H, int h, float (&wa)[R],
+                                       float (&wb)[R]) {
+    const __amdgpu_buffer_rsrc_t rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w), 0, K * H * 4, 0x00020000);
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int k = 2 * j;
+        const uint32_t off = lane_off + (uint32_t)(k * H) * 4u;
+        wa[j] = k + h < K ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0)) : 0.0f;
+        wb[j] = k + h < K ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off, d1 * 4, 0)) : 0.0f;
+    }
+}
+template <int MT, int R = 8, class AFn>
+__device__ inline void mfma_pass_rows(const float* w, int d1, uint32_t lane_off, int K, int H, int h, AFn a_of,
+                                      f32x16 (&c)[MT][2], float (&wa)[R], float (&wb)[R]) {
+    const __amdgpu_buffer_rsrc_t rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w), 0, K * H * 4, 0x00020000);
+    uint32_t off[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) off[j] = lane_off + (uint32_t)(2 * j * H) * 4u;
+    // column tile `tile` (0 / 1) of row k0 + 2 j + h
+    auto wt = [&](int tile, int j, int k0) -> float {
+        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off[j], (k0 * H + (tile ? d1 : 0)) * 4, 0));
+    };
+    float na[R], nb[R];
+    const int K_main = K - K % (2 * R);
+    int k0 = 0;
+    for (; k0 + 4 * R <= K; k0 += 2 * R) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            na[j] = wt(0, j, k0 + 2 * R);
+            nb[j] = wt(1, j, k0 + 2 * R);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (mfma_pass: the loads go out before the chunk's MFMAs)
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                const float a = a_of(k0 + 2 * j, t);
+                c[t][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wa[j], c[t][0], 0, 0, 0);
+                c[t][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wb[j], c[t][1], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            wa[j] = na[j];
+            wb[j] = nb[j];
+        }
+    }
+    for (; k0 < K_main; k0 += 2 * R) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {  // next chunk (a load past K yields 0 without touching memory)
+            const int k = k0 + 2 * R + 2 * j;
+            na[j] = k + h < K ? wt(0, j, k0 + 2 * R) : 0.0f;
+            nb[j] = k + h < K ? wt(1, j, k0 + 2 * R) : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                const float a = a_of(k0 + 2 * j, t);
+                c[t][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wa[j], c[t][0], 0, 0, 0);
+                c[t][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wb[j], c[t][1], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            wa[j] = na[j];
+            wb[j] = nb[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        const int k = k0 + 2 * j;
+        if (k < K) {  // wave-uniform
+#pragma unroll
+            for (int t = 0; t < MT; ++t) {
+                const float a = a_of(k, t);
+                c[t][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wa[j], c[t][0], 0, 0, 0);
+                c[t][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wb[j], c[t][1], 0, 0, 0);
+            }
+        }
+    }
+}
+
 // The chain starts of FL == 2 (k_mlp_mfma explains them): act[l][:] = (maze constant + row of the p1 cell) + row of the
 // p2 cell, 16 bytes per item. L H/4 items over the block's threads is exactly L H / (4 NTHREADS) per thread (H % 32 == 0),
 // so the loop has that trip count and no bound per item -- a guarded item is a branch, and the compiler then waits out
 // each item's loads before it issues the next item's. A pass issues the 3 N loads of N items before it stores the first
 // sum; item i of a thread is tid + i NTHREADS, walked as (leaf, column) without a division per item.
+// With a column range [col0, col0 + Hc) (k_mlp_mfma_halves: half a layer) the items are L Hc/4, Hc / 16 per thread, and
+// land at act[l][0 .. Hc) in rows of `ld` floats; H4 then is Hc / 4 and c0 is col0 / 4.
 template <int N>
 __device__ inline void mlp_chain_starts_pass(const NetDev& net, const LeafFeat* feat, float* act, int H4, int dq, int dr,
-                                             int& l, int& c4) {
-    const int H = net.H, hw = net.hw, ld = H + 4;
+                                             int& l, int& c4, int c0, int ld) {
+    const int H = net.H, hw = net.hw;
     float4 a[N], b[N], c[N];
     float* dst[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         const LeafFeat& f = feat[l];
-        a[i] = ((const float4*)(net.cmaze + (size_t)f.maze_id * H))[c4];
-        b[i] = ((const float4*)(net.w1t + (size_t)(4 * hw + f.p1) * H))[c4];
-        c[i] = ((const float4*)(net.w1t + (size_t)(5 * hw + f.p2) * H))[c4];
+        a[i] = ((const float4*)(net.cmaze + (size_t)f.maze_id * H))[c0 + c4];
+        b[i] = ((const float4*)(net.w1t + (size_t)(4 * hw + f.p1) * H))[c0 + c4];
+        c[i] = ((const float4*)(net.w1t + (size_t)(5 * hw + f.p2) * H))[c0 + c4];
         dst[i] = act + (size_t)l * ld + 4 * c4;
         l += dq;
         c4 += dr;
@@ -607,21 +703,26 @@ __device__ inline void mlp_chain_starts_pass(const NetDev& net, const LeafFeat* 
     }
 }
 template <int L>
-__device__ inline void mlp_chain_starts(const NetDev& net, const LeafFeat* feat, float* act, int tid) {
+__device__ inline void mlp_chain_starts(const NetDev& net, const LeafFeat* feat, float* act, int tid, int col0, int Hc,
+                                        int ld) {
     // H itself is not checked here: the host launches these kernels only where mlp_all_mfma(H) holds (H % 32 == 0,
-    // H <= 256), so H4 is a multiple of 8 and at most NTHREADS / 4
+    // H <= 256) and Hc is H or half a layer, a multiple of 32: H4 is a multiple of 8 and at most NTHREADS / 4
     static_assert((L * 8) % (2 * NTHREADS) == 0, "an even number of items per thread wherever mlp_all_mfma(H) holds");
-    const int H4 = net.H >> 2;
+    const int H4 = Hc >> 2, c0 = col0 >> 2;
     const int n_items = L * H4 / NTHREADS;
     const int dq = NTHREADS / H4, dr = NTHREADS - dq * H4;  // the step from one item of a thread to its next
     int l = tid / H4, c4 = tid - l * H4;
     int i = 0;
-    for (; i + 8 <= n_items; i += 8) mlp_chain_starts_pass<8>(net, feat, act, H4, dq, dr, l, c4);
+    for (; i + 8 <= n_items; i += 8) mlp_chain_starts_pass<8>(net, feat, act, H4, dq, dr, l, c4, c0, ld);
     if (i + 4 <= n_items) {
-        mlp_chain_starts_pass<4>(net, feat, act, H4, dq, dr, l, c4);
+        mlp_chain_starts_pass<4>(net, feat, act, H4, dq, dr, l, c4, c0, ld);
         i += 4;
     }
-    if (i + 2 <= n_items) mlp_chain_starts_pass<2>(net, feat, act, H4, dq, dr, l, c4);
+    if (i + 2 <= n_items) mlp_chain_starts_pass<2>(net, feat, act, H4, dq, dr, l, c4, c0, ld);
+}
+template <int L>
+__device__ inline void mlp_chain_starts(const NetDev& net, const LeafFeat* feat, float* act, int tid) {
+    mlp_chain_starts<L>(net, feat, act, tid, 0, net.H, net.H + 4);  // the whole layer into act[L][H + 4]
 }
 
 // (amdgpu_num_vgpr: with the limit the compiler keeps the accumulators in ordinary vector registers and needs 148 in all,
@@ -829,6 +930,244 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))
 
 __host__ __device__ inline bool mlp_all_mfma(int H) { return (H & 31) == 0 && H <= 64 * (NTHREADS / 64); }
 static const int MLP_MFMA_MT = 2;  // 64 leaves per block
+
+// ---- k_mlp_mfma's FL = 2 path with both hidden layers split at column Ha of the hidden dimension ----
+// LDS holds half a layer's activations, act[64][Ha + 4], instead of a whole layer's: 33,792 B + 7,424 B static at
+// H = 256 against 73,984 B, so a CU takes three workgroups and not two (the registers already allowed three wavefronts a
+// SIMD), and one more workgroup's MFMAs are there to fill the phases in which the others issue none (features, chain
+// starts, heads). The tile is still 64 leaves on four wavefronts and every weight is still fetched once per tile.
+//   Ha = 32 ceil(H / 64), Hb = H - Ha: 128 / 128 at H = 256, 128 / 96 at 224, 64 / 32 at 96, 32 / 0 at 32.
+// Every output's sum keeps its k-order, so the bits are k_mlp_mfma's:
+// - first layer: wavefront w owns columns [32 w, 32 w + 32) of each half (w < Ha / 32, w < Hb / 32). The chain starts
+//   of half A go through `act` into its accumulators, then those of half B; x (cheese | six scalars) is staged once
+//   and one mfma_pass takes both column tiles, Ha columns apart, through the K2 rows;
+// - second layer: relu of half A goes to `act`, the wavefront's two column tiles [64 w, 64 w + 64) take k in [0, Ha);
+//   relu of half B replaces it, the weight pointer moves on Ha rows and the same accumulators take k in [Ha, H);
+// - heads: the second layer's column tiles that start below Ha go to `act`, the heads take k in [0, Ha) and keep their
+//   f32x4; the other tiles replace them and the heads go on (Ha and Hb are multiples of 32, a head step is 4).
+// Registers at the peak (the second layer's first half): 64 second-layer accumulators, the 32 of the first layer's half
+// B, a ring of 32 -- 152 in all with mfma_pass_rows' addressing, 168 + scratch with mfma_pass's
+// (profiles/mlp_halves_resource_usage.txt). amdgpu_num_vgpr as on k_mlp_mfma; amdgpu_waves_per_eu(3, 3) states the three
+// wavefronts a SIMD that the LDS is sized for, so that passing 168 registers shows as scratch in the resource table and
+// not as a CU that silently holds two workgroups again.
+__host__ __device__ inline int mlp_half_a(int H) { return 32 * ((H + 63) / 64); }
+__host__ __device__ inline size_t mlp_halves_static_lds() {  // feat, cheese, hl of a tile
+    return (size_t)32 * MLP_MFMA_MT * (sizeof(LeafFeat) + 4 * sizeof(unsigned long long) + 12 * sizeof(float));
+}
+__host__ __device__ inline size_t mlp_halves_smem_bytes(int H) {
+    return (size_t)32 * MLP_MFMA_MT * (mlp_half_a(H) + 4) * 4;
+}
+// host rule: x fits a row of the half tile and three workgroups fit a CU's 160 KiB of LDS
+__host__ __device__ inline bool mlp_halves_ok(int H, int hw) {
+    return mlp_all_mfma(H) && ((hw + 6 + 1) & ~1) <= mlp_half_a(H) + 4 &&
+           3 * (mlp_halves_smem_bytes(H) + mlp_halves_static_lds()) <= (size_t)160 * 1024;
+}
+
+template <int NW>
+__global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128), amdgpu_waves_per_eu(3, 3))) k_mlp_mfma_halves(NetDev net, const ar::LeafReq<NW>* q, const uint32_t* qcount,
+                                                       uint32_t n_fixed, const char* boards, size_t board_stride,
+                                                       ar::EvalOut* out, float* logits) {
+    constexpr int MT = MLP_MFMA_MT, L = 32 * MT;
+    static_assert(2 * MT == NTHREADS / 64, "the heads give 16 leaves to each wavefront");
+    extern __shared__ float smem[];
+    const int H = net.H, hw = net.hw, Ha = mlp_half_a(H), Hb = H - Ha, ld = Ha + 4;
+    float* act = smem;  // [L][ld]: chain starts, x and the relu of a half of each hidden layer in turn
+    __shared__ LeafFeat feat[L];
+    __shared__ unsigned long long cheese[L][4];
+    __shared__ float hl[L * 12];
+    const uint32_t n = qcount ? *qcount : n_fixed;
+    const uint32_t base = blockIdx.x * L;
+    if (base >= n) return;
+    const int cnt = (int)((n - base) < (uint32_t)L ? (n - base) : (uint32_t)L);
+    const int tid = threadIdx.x;
+    if (tid < L) {
+        const int l = tid < cnt ? tid : 0;
+        const ar::LeafReq<NW>& r = q[base + l];
+        const ar::Board& b = *(const ar::Board*)(boards + (size_t)r.slot * board_stride);
+        leaf_features<NW>(r.st, b, hw, feat[tid]);
+        for (int k = 0; k < 4; ++k) cheese[tid][k] = k < NW ? r.st.cheese[k] : 0ULL;
+    }
+    __syncthreads();
+    // (the wavefront's number in a scalar register: the conditions and weight pointers derived from it are wave-uniform)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, h = lane >> 5;
+    // first layer: column tile m0 of half A in c1[t][0], of half B in c1[t][1]
+    const int m0 = wave * 32;
+    const bool hasA = m0 < Ha, hasB = m0 < Hb;
+    f32x16 c1[MT][2];
+    mlp_chain_starts<L>(net, feat, act, tid, 0, Ha, ld);
+    __syncthreads();
+    if (hasA) {
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                c1[t][0][v] = act[(size_t)i * ld + m0 + r];
+            }
+            if (!hasB) c1[t][1] = c1[t][0];  // (with no tile in half B the pass repeats the first one, as k_mlp_mfma's does)
+        }
+    }
+    __syncthreads();
+    if (Hb) {
+        mlp_chain_starts<L>(net, feat, act, tid, Ha, Hb, ld);
+        __syncthreads();
+        if (hasB) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t)
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                    c1[t][1][v] = act[(size_t)i * ld + m0 + r];
+                }
+        }
+        __syncthreads();  // the starts are in registers: `act` now takes the operand
+    }
+    // (each pass's first weights go out ahead of the LDS phase in front of it: mfma_rows_prime)
+    float wa[8], wb[8];
+    const float* w1 = net.w1t + (size_t)(6 * hw) * H;
+    const uint32_t w1_off = (uint32_t)(h * H + m0 + r) * 4u;
+    if (hasA) mfma_rows_prime<8>(w1, hasB ? Ha : 0, w1_off, hw + 6, H, h, wa, wb);
+    {
+        // x over [cheese | six scalars], K2e floats per leaf at the head of its row of `act`
+        const int K2 = hw + 6, K2e = (K2 + 1) & ~1;
+        constexpr int TPL = NTHREADS / L;  // threads per leaf
+        const int l = tid / TPL;
+        const LeafFeat& f = feat[l];
+        float* x = act + (size_t)l * ld;
+        for (int kk = tid % TPL; kk < K2e; kk += TPL) {
+            float v;
+            if (kk < hw) v = (cheese[l][kk >> 6] >> (kk & 63)) & 1ULL ? 1.0f : 0.0f;
+            else v = kk < K2 ? f.sc[kk - hw] : 0.0f;
+            x[kk] = v;
+        }
+    }
+    __syncthreads();
+    const float* ap = act + (size_t)r * ld + h;
+    auto a_of = [&](int k, int t) -> float { return ap[(size_t)(32 * t) * ld + k]; };
+    if (hasA) {
+        mfma_pass_rows<MT, 8>(w1, hasB ? Ha : 0, w1_off, hw + 6, H, h, a_of, c1, wa, wb);
+    }
+    // second layer: column tiles n0 and n0 + 32 over all of H, held in the accumulators through both halves of k
+    const int n0 = wave * 64;
+    const bool has = n0 < H, two = n0 + 32 < H;
+    const uint32_t w2_off = (uint32_t)(h * H + n0 + r) * 4u;
+    if (has) mfma_rows_prime<8>(net.w2t, two ? 32 : 0, w2_off, Ha, H, h, wa, wb);
+    __syncthreads();  // every wavefront is done reading x before the results go over it
+    if (hasA) {
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                act[(size_t)i * ld + m0 + r] = fmaxf(c1[t][0][v], 0.0f);
+            }
+    }
+    __syncthreads();
+    f32x16 c[MT][2];
+    if (has) {
+        const float b0 = net.b2[n0 + r], b1 = net.b2[n0 + (two ? 32 : 0) + r];
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                c[t][0][v] = b0;
+                c[t][1][v] = b1;
+            }
+        mfma_pass_rows<MT, 8>(net.w2t, two ? 32 : 0, w2_off, Ha, H, h, a_of, c, wa, wb);
+    }
+    if (Hb) {
+        const float* w2 = net.w2t + (size_t)Ha * H;
+        if (has) mfma_rows_prime<8>(w2, two ? 32 : 0, w2_off, Hb, H, h, wa, wb);
+        __syncthreads();
+        if (hasB) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t)
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                    act[(size_t)i * ld + m0 + r] = fmaxf(c1[t][1][v], 0.0f);
+                }
+        }
+        __syncthreads();
+        if (has) {
+            mfma_pass_rows<MT, 8>(w2, two ? 32 : 0, w2_off, Hb, H, h, a_of, c, wa, wb);
+        }
+    }
+    __syncthreads();
+    // heads: wavefront w takes leaves 16 w .. 16 w + 15 (heads_mfma16's layout and sum), k in two spans. The weights of
+    // 8 k-steps are loaded as a set in front of their MFMAs (a span is a multiple of 32 columns): one wait per set,
+    // 8 dependent L2 trips a tile where heads_mfma16's loop, which the compiler leaves rolled, makes 64. With three
+    // workgroups a CU this is measured faster (profiles/mlp_halves_ab.txt); all 64 at once beside two was slower.
+    const int hr = lane & 15, hq = lane >> 4;
+    const bool hcol = hr < 12;
+    const float* hap = act + (size_t)(wave * 16 + hr) * ld + hq;
+    const float* hbp = net.wh + (size_t)(hcol ? hr : 0) * H + hq;
+    const float hb = hcol ? net.bh[hr] : 0.0f;
+    f32x4 hc = {hb, hb, hb, hb};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int col = n0 + 32 * j;  // a tile belongs to the half of its first column
+        if (col < Ha) {
+#pragma unroll
+            for (int t = 0; t < MT; ++t)
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                    act[(size_t)i * ld + col + r] = fmaxf(c[t][j][v], 0.0f);
+                }
+        }
+    }
+    __syncthreads();
+    for (int k = 0; k < Ha; k += 32) {
+        float wv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wv[j] = hbp[k + 4 * j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            hc = __builtin_amdgcn_mfma_f32_16x16x4f32(hap[k + 4 * j], hcol ? wv[j] : 0.0f, hc, 0, 0, 0);
+    }
+    if (Hb) {
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = n0 + 32 * j;
+            if (col >= Ha && col < H) {
+#pragma unroll
+                for (int t = 0; t < MT; ++t)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) {
+                        const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                        act[(size_t)i * ld + col - Ha + r] = fmaxf(c[t][j][v], 0.0f);
+                    }
+            }
+        }
+        __syncthreads();
+        hbp += Ha;
+        for (int k = 0; k < Hb; k += 32) {
+        float wv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) wv[j] = hbp[k + 4 * j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            hc = __builtin_amdgcn_mfma_f32_16x16x4f32(hap[k + 4 * j], hcol ? wv[j] : 0.0f, hc, 0, 0, 0);
+    }
+    }
+    if (hcol)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) hl[(wave * 16 + 4 * hq + v) * 12 + hr] = hc[v];
+    __syncthreads();
+    if (tid < cnt) {
+        const float* hh = hl + tid * 12;
+        ar::EvalOut o;
+        softmax5(hh, o.p1);
+        softmax5(hh + 5, o.p2);
+        o.v1 = softplusf(hh[10]);
+        o.v2 = softplusf(hh[11]);
+        out[base + tid] = o;
+        if (logits)
+            for (int k = 0; k < 10; ++k) logits[(size_t)(base + tid) * 10 + k] = hh[k];
+    }
+}
 
 // ---- SymmetricMLP -----------------------------------------------------------------------------
 template <int NW>
@@ -1592,6 +1931,11 @@ static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcou
                 return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the MLP kernel");
             hipLaunchKernelGGL(ffns[fl], dim3(blocks), dim3(NTHREADS), smem, stream, net->dev, q, qcount, n_max, boards,
                                board_stride, out, logits, feat);
+        } else if (fl == 2 && mlp_halves_ok(net->dev.H, net->dev.hw)) {
+            // the same sums with half a layer in LDS at a time, three workgroups a CU (k_mlp_mfma_halves); boards whose
+            // x passes a row of the half tile stay with the whole tile below
+            hipLaunchKernelGGL(k_mlp_mfma_halves<NW>, dim3(blocks), dim3(NTHREADS), mlp_halves_smem_bytes(net->dev.H), stream,
+                               net->dev, q, qcount, n_max, boards, board_stride, out, logits);
         } else {
             if (smem > 48 * 1024 &&
                 hipFuncSetAttribute((const void*)fns[fl], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
