@@ -159,6 +159,27 @@ __device__ inline void leaf_features(const ar::State<NW>& st, const ar::Board& b
     f.maze_id = (int)(b.maze_off / (uint32_t)(hw * 4));
 }
 
+// The two helpers below are shared by the evaluators of nets.h, nets_ownership.h and nets_cnn.h. A helper goes in only in
+// a form that leaves every kernel's instructions as they were (tools/isa_diff.py). The other blocks the evaluators repeat
+// (ReLU of the accumulators into LDS, their bias start, the staged operand, the output epilogue, the heads' span loop of
+// k_mlp_mfma_halves) each changed a kernel as a function or a lambda and stay written out: profiles/mlp_shared_isa.txt.
+
+// a tile's prologue: thread l < L takes request base + l (past `cnt`: the tile's first) into feat[l] and cheese[l]
+template <int NW, int L>
+__device__ inline void tile_leaves(const ar::LeafReq<NW>* q, uint32_t base, int cnt, const char* boards, size_t board_stride,
+                                   int hw, LeafFeat* feat, unsigned long long (*cheese)[4], int tid) {
+    if (tid < L) {
+        const int l = tid < cnt ? tid : 0;
+        const ar::LeafReq<NW>& r = q[base + l];
+        const ar::Board& b = *(const ar::Board*)(boards + (size_t)r.slot * board_stride);
+        leaf_features<NW>(r.st, b, hw, feat[tid]);
+        for (int k = 0; k < 4; ++k) cheese[tid][k] = k < NW ? r.st.cheese[k] : 0ULL;
+    }
+}
+
+// row of a 32x32 MFMA result that register v of a lane in half h = lane >> 5 holds, in row tile t (mfma_tile_pair)
+__device__ inline int acc_row(int t, int v, int h) { return 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h; }
+
 // acc[l] += sum_k wt[k*H + n] * act[l*ld + k]   (act in LDS, broadcast reads)
 template <int L>
 __device__ inline void dense_acc(const float* __restrict__ wt, int K, int H, int n, const float* act, int ld,
@@ -243,7 +264,7 @@ __device__ inline void dense_mfma32_relu(const float* __restrict__ wt, const flo
         if (has) {
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int i = (v & 3) + 8 * (v >> 2) + 4 * h;
+                const int i = acc_row(0, v, h);
                 out[(size_t)i * ld + n0 + r] = fmaxf(c0[v], 0.0f);
                 if (two) out[(size_t)i * ld + n0 + 32 + r] = fmaxf(c1[v], 0.0f);
             }
@@ -370,13 +391,7 @@ __global__ void __launch_bounds__(NTHREADS) k_mlp(NetDev net, const ar::LeafReq<
     if (base >= n) return;
     const int cnt = (int)((n - base) < (uint32_t)L ? (n - base) : (uint32_t)L);
     const int tid = threadIdx.x;
-    if (tid < L) {
-        const int l = tid < cnt ? tid : 0;
-        const ar::LeafReq<NW>& r = q[base + l];
-        const ar::Board& b = *(const ar::Board*)(boards + (size_t)r.slot * board_stride);
-        leaf_features<NW>(r.st, b, hw, feat[tid]);
-        for (int k = 0; k < 4; ++k) cheese[tid][k] = k < NW ? r.st.cheese[k] : 0ULL;
-    }
+    tile_leaves<NW, L>(q, base, cnt, boards, board_stride, hw, feat, cheese, tid);
     __syncthreads();
     const float* w1p1 = net.w1t + (size_t)(hw * 4) * H;
     const float* w1p2 = net.w1t + (size_t)(hw * 5) * H;
@@ -729,10 +744,14 @@ __device__ inline void mlp_chain_starts(const NetDev& net, const LeafFeat* feat,
 // without it 130 + 64 accumulator registers = 196 (200 allocated): two such wavefronts leave a SIMD 112 of its 512
 // registers, and a tree-reuse wavefront (k_advance: 128) on a SIMD then kept the CU's second evaluator workgroup out for
 // as long as it ran. A/B of the two builds: +1.3 % simulations/s.)
-template <int NW, int MT, int FL>
+// FEAT: the trunk's output, the tile's [cnt][H] floats that the heads read from `act`, also goes to feat_out[request][H]
+// (validation of a local_value checkpoint: nets_ownership.h); without FEAT feat_out is not read. The flag sits on the
+// kernel itself: each instantiation then is the code a separate kernel had (profiles/mlp_shared_isa.txt), where a shared
+// force-inlined body under two kernels was not.
+template <int NW, int MT, int FL, bool FEAT = false>
 __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))) k_mlp_mfma(NetDev net, const ar::LeafReq<NW>* q, const uint32_t* qcount,
                                                        uint32_t n_fixed, const char* boards, size_t board_stride,
-                                                       ar::EvalOut* out, float* logits) {
+                                                       ar::EvalOut* out, float* logits, float* feat_out) {
     constexpr int L = 32 * MT;
     extern __shared__ float smem[];
     const int H = net.H, hw = net.hw, ld = H + 4;
@@ -745,13 +764,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))
     if (base >= n) return;
     const int cnt = (int)((n - base) < (uint32_t)L ? (n - base) : (uint32_t)L);
     const int tid = threadIdx.x;
-    if (tid < L) {
-        const int l = tid < cnt ? tid : 0;
-        const ar::LeafReq<NW>& r = q[base + l];
-        const ar::Board& b = *(const ar::Board*)(boards + (size_t)r.slot * board_stride);
-        leaf_features<NW>(r.st, b, hw, feat[tid]);
-        for (int k = 0; k < 4; ++k) cheese[tid][k] = k < NW ? r.st.cheese[k] : 0ULL;
-    }
+    tile_leaves<NW, L>(q, base, cnt, boards, board_stride, hw, feat, cheese, tid);
     __syncthreads();
     const int wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int n0 = wave * 64;
@@ -799,7 +812,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))
             for (int t = 0; t < MT; ++t) {
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
-                    const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                    const int i = acc_row(t, v, h);
                     c[t][0][v] = act[(size_t)i * ld + n0 + r];
                     c[t][1][v] = act[(size_t)i * ld + n0 + (two ? 32 : 0) + r];
                 }
@@ -833,7 +846,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))
         for (int t = 0; t < MT; ++t)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                const int i = acc_row(t, v, h);
                 const float* cm = net.cmaze + (size_t)feat[i].maze_id * H + n0 + r;
                 c[t][0][v] = cm[0];
                 c[t][1][v] = cm[two ? 32 : 0];
@@ -881,7 +894,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))
         for (int t = 0; t < MT; ++t)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                const int i = acc_row(t, v, h);
                 act[(size_t)i * ld + n0 + r] = fmaxf(c[t][0][v], 0.0f);
                 if (two) act[(size_t)i * ld + n0 + 32 + r] = fmaxf(c[t][1][v], 0.0f);
             }
@@ -907,12 +920,19 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))
         for (int t = 0; t < MT; ++t)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                const int i = acc_row(t, v, h);
                 act[(size_t)i * ld + n0 + r] = fmaxf(c[t][0][v], 0.0f);
                 if (two) act[(size_t)i * ld + n0 + 32 + r] = fmaxf(c[t][1][v], 0.0f);
             }
     }
     __syncthreads();
+    if constexpr (FEAT) {
+        const int H4 = H >> 2;
+        for (int item = tid; item < cnt * H4; item += NTHREADS) {
+            const int l = item / H4, c4 = item - l * H4;
+            ((float4*)(feat_out + (size_t)(base + l) * H))[c4] = *(const float4*)(act + (size_t)l * ld + 4 * c4);
+        }
+    }
     heads_mfma16(net.wh, net.bh, 12, H, act, ld, hl, tid, 2 * MT);
     __syncthreads();
     if (tid < cnt) {
@@ -980,13 +1000,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128),
     if (base >= n) return;
     const int cnt = (int)((n - base) < (uint32_t)L ? (n - base) : (uint32_t)L);
     const int tid = threadIdx.x;
-    if (tid < L) {
-        const int l = tid < cnt ? tid : 0;
-        const ar::LeafReq<NW>& r = q[base + l];
-        const ar::Board& b = *(const ar::Board*)(boards + (size_t)r.slot * board_stride);
-        leaf_features<NW>(r.st, b, hw, feat[tid]);
-        for (int k = 0; k < 4; ++k) cheese[tid][k] = k < NW ? r.st.cheese[k] : 0ULL;
-    }
+    tile_leaves<NW, L>(q, base, cnt, boards, board_stride, hw, feat, cheese, tid);
     __syncthreads();
     // (the wavefront's number in a scalar register: the conditions and weight pointers derived from it are wave-uniform)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -1001,7 +1015,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128),
         for (int t = 0; t < MT; ++t) {
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                const int i = acc_row(t, v, h);
                 c1[t][0][v] = act[(size_t)i * ld + m0 + r];
             }
             if (!hasB) c1[t][1] = c1[t][0];  // (with no tile in half B the pass repeats the first one, as k_mlp_mfma's does)
@@ -1016,7 +1030,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128),
             for (int t = 0; t < MT; ++t)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
-                    const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                    const int i = acc_row(t, v, h);
                     c1[t][1][v] = act[(size_t)i * ld + m0 + r];
                 }
         }
@@ -1058,7 +1072,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128),
         for (int t = 0; t < MT; ++t)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                const int i = acc_row(t, v, h);
                 act[(size_t)i * ld + m0 + r] = fmaxf(c1[t][0][v], 0.0f);
             }
     }
@@ -1084,7 +1098,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128),
             for (int t = 0; t < MT; ++t)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
-                    const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                    const int i = acc_row(t, v, h);
                     act[(size_t)i * ld + m0 + r] = fmaxf(c1[t][1][v], 0.0f);
                 }
         }
@@ -1112,7 +1126,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128),
             for (int t = 0; t < MT; ++t)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
-                    const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                    const int i = acc_row(t, v, h);
                     act[(size_t)i * ld + col + r] = fmaxf(c[t][j][v], 0.0f);
                 }
         }
@@ -1136,7 +1150,7 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128),
                 for (int t = 0; t < MT; ++t)
 #pragma unroll
                     for (int v = 0; v < 16; ++v) {
-                        const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                        const int i = acc_row(t, v, h);
                         act[(size_t)i * ld + col - Ha + r] = fmaxf(c[t][j][v], 0.0f);
                     }
             }
@@ -1144,13 +1158,13 @@ __global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128),
         __syncthreads();
         hbp += Ha;
         for (int k = 0; k < Hb; k += 32) {
-        float wv[8];
+            float wv[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) wv[j] = hbp[k + 4 * j];
+            for (int j = 0; j < 8; ++j) wv[j] = hbp[k + 4 * j];
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-            hc = __builtin_amdgcn_mfma_f32_16x16x4f32(hap[k + 4 * j], hcol ? wv[j] : 0.0f, hc, 0, 0, 0);
-    }
+            for (int j = 0; j < 8; ++j)
+                hc = __builtin_amdgcn_mfma_f32_16x16x4f32(hap[k + 4 * j], hcol ? wv[j] : 0.0f, hc, 0, 0, 0);
+        }
     }
     if (hcol)
 #pragma unroll
@@ -1188,13 +1202,7 @@ __global__ void __launch_bounds__(NTHREADS) k_symmetric(NetDev net, const ar::Le
     if (base >= n) return;
     const int cnt = (int)((n - base) < (uint32_t)L ? (n - base) : (uint32_t)L);
     const int tid = threadIdx.x;
-    if (tid < L) {
-        const int l = tid < cnt ? tid : 0;
-        const ar::LeafReq<NW>& r = q[base + l];
-        const ar::Board& b = *(const ar::Board*)(boards + (size_t)r.slot * board_stride);
-        leaf_features<NW>(r.st, b, hw, feat[tid]);
-        for (int k = 0; k < 4; ++k) cheese[tid][k] = k < NW ? r.st.cheese[k] : 0ULL;
-    }
+    tile_leaves<NW, L>(q, base, cnt, boards, board_stride, hw, feat, cheese, tid);
     __syncthreads();
     // shared encoder input = [maze hw*4 | cheese hw | progress]
     const float* wch = net.w1t + (size_t)(hw * 4) * H;
@@ -1306,13 +1314,7 @@ __global__ void __launch_bounds__(NTHREADS) k_symmetric_mfma2(NetDev net, const 
     if (base >= n) return;
     const int cnt = (int)((n - base) < (uint32_t)L ? (n - base) : (uint32_t)L);
     const int tid = threadIdx.x;
-    if (tid < L) {
-        const int l = tid < cnt ? tid : 0;
-        const ar::LeafReq<NW>& r = q[base + l];
-        const ar::Board& b = *(const ar::Board*)(boards + (size_t)r.slot * board_stride);
-        leaf_features<NW>(r.st, b, hw, feat[tid]);
-        for (int k = 0; k < 4; ++k) cheese[tid][k] = k < NW ? r.st.cheese[k] : 0ULL;
-    }
+    tile_leaves<NW, L>(q, base, cnt, boards, board_stride, hw, feat, cheese, tid);
     __syncthreads();
     const int wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int n0 = wave * 64;
@@ -1324,7 +1326,7 @@ __global__ void __launch_bounds__(NTHREADS) k_symmetric_mfma2(NetDev net, const 
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                const int i = acc_row(t, v, h);
                 bufB[(size_t)i * ld + n0 + r] = fmaxf(c[t][0][v], 0.0f);
                 if (two) bufB[(size_t)i * ld + n0 + 32 + r] = fmaxf(c[t][1][v], 0.0f);
             }
@@ -1354,7 +1356,7 @@ __global__ void __launch_bounds__(NTHREADS) k_symmetric_mfma2(NetDev net, const 
     if (has) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const int i = (v & 3) + 8 * (v >> 2) + 4 * h;
+            const int i = acc_row(0, v, h);
             const float* cm = net.cmaze + (size_t)feat[i].maze_id * H + n0 + r;
             cs[0][0][v] = cm[0];
             cs[0][1][v] = cm[c1];
@@ -1367,7 +1369,7 @@ __global__ void __launch_bounds__(NTHREADS) k_symmetric_mfma2(NetDev net, const 
     if (has) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const int i = (v & 3) + 8 * (v >> 2) + 4 * h;
+            const int i = acc_row(0, v, h);
             bufB[(size_t)i * ld + n0 + r] = fmaxf(cs[0][0][v], 0.0f);
             if (two) bufB[(size_t)i * ld + n0 + 32 + r] = fmaxf(cs[0][1][v], 0.0f);
         }
@@ -1882,13 +1884,26 @@ static int net_rebind_mazes(ArNet* net, const uint32_t* d_ids, int n, hipStream_
     return AR_OK;
 }
 
+// one evaluator launch of `blocks` x NTHREADS: the kernel's dynamic-LDS limit is raised first where `smem` passes the
+// default 48 KiB; `what` names the kernel in that error
+template <class... P, class... A>
+static int net_launch_kernel(void (*fn)(P...), const char* what, uint32_t blocks, size_t smem, hipStream_t stream, A... args) {
+    if (smem > 48 * 1024 &&
+        hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+        return nets_fail(AR_E_DEVICE, std::string("cannot reserve LDS for the ") + what + " kernel");
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(arnet::NTHREADS), smem, stream, args...);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return nets_fail(AR_E_DEVICE, std::string("network kernel launch failed: ") + hipGetErrorString(le));
+    return AR_OK;
+}
+
 template <int NW>
 static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcount, uint32_t n_max, const char* boards,
                       size_t board_stride, ar::EvalOut* out, float* logits, hipStream_t stream, float* feat = nullptr) {
     using namespace arnet;
     if (n_max == 0) return AR_OK;
     const bool mlp_mfma = net->dev.arch == ARCH_MLP && mlp_all_mfma(net->dev.H);
-    // `feat` (the trunk's output, [n_max][H]) is written by k_mlp_mfma_feat alone
+    // `feat` (the trunk's output, [n_max][H]) is written by k_mlp_mfma<.., FEAT = true> alone
     if (feat && !mlp_mfma) return nets_fail(AR_E_INVALID, "this network's evaluator does not give its trunk output");
     // (k_symmetric_mfma2 stages the shared encoder's operand, hw + 1 values, at the head of a row of its buffer)
     const bool sym_mfma = net->dev.arch == ARCH_SYMMETRIC && symmetric_mfma_ok(net->dev.H) && !getenv("AR_SYM_FMA") &&
@@ -1900,18 +1915,13 @@ static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcou
         const bool kg = net->dev.arch == ARCH_CNN_KATAGO;
         decltype(&k_cnn_mfma<NW, 1, false>) const fn = net->cnn.MT == 2 ? (kg ? k_cnn_mfma<NW, 2, true> : k_cnn_mfma<NW, 2, false>)
                                                                         : (kg ? k_cnn_mfma<NW, 1, true> : k_cnn_mfma<NW, 1, false>);
-        if (net->smem > 48 * 1024 &&
-            hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)net->smem) != hipSuccess)
-            return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the CNN kernel");
-        hipLaunchKernelGGL(fn, dim3(blocks), dim3(NTHREADS), net->smem, stream, net->cnn, q, qcount, n_max, boards, board_stride,
-                           net->bound_pool, out, logits);
-    } else if (net->dev.arch == ARCH_CNN) {
-        if (net->smem > 48 * 1024 && hipFuncSetAttribute((const void*)k_cnn<NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                         (int)net->smem) != hipSuccess)
-            return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the CNN kernel");
-        hipLaunchKernelGGL(k_cnn<NW>, dim3(blocks), dim3(NTHREADS), net->smem, stream, net->cnn, q, qcount, n_max, boards,
-                           board_stride, net->bound_pool, out, logits);
-    } else if (mlp_mfma) {
+        return net_launch_kernel(fn, "CNN", blocks, net->smem, stream, net->cnn, q, qcount, n_max, boards, board_stride,
+                                 net->bound_pool, out, logits);
+    }
+    if (net->dev.arch == ARCH_CNN)
+        return net_launch_kernel(k_cnn<NW>, "CNN", blocks, net->smem, stream, net->cnn, q, qcount, n_max, boards, board_stride,
+                                 net->bound_pool, out, logits);
+    if (mlp_mfma) {
         const size_t smem = (size_t)32 * MLP_MFMA_MT * (net->dev.H + 4) * 4;
         // first-layer variant (k_mlp_mfma's FL): 2 unless AR_MLP_FL says otherwise (read per launch: a test toggles it);
         // 0 needs the whole observation's non-maze part in a row of `act`
@@ -1921,53 +1931,25 @@ static int net_launch(ArNet* net, const ar::LeafReq<NW>* q, const uint32_t* qcou
         if (fl < 0 || fl > 2) fl = 2;
         if (fl == 2 && K2e > net->dev.H + 4) fl = 1;  // (the staged operand is a row of `act`: narrow hidden layers on big boards)
         if (fl == 0 && K1e > net->dev.H + 4) fl = 1;
-        decltype(&k_mlp_mfma<NW, MLP_MFMA_MT, 0>) const fns[3] = {k_mlp_mfma<NW, MLP_MFMA_MT, 0>, k_mlp_mfma<NW, MLP_MFMA_MT, 1>,
-                                                                   k_mlp_mfma<NW, MLP_MFMA_MT, 2>};
-        if (feat) {
-            decltype(&k_mlp_mfma_feat<NW, MLP_MFMA_MT, 0>) const ffns[3] = {
-                k_mlp_mfma_feat<NW, MLP_MFMA_MT, 0>, k_mlp_mfma_feat<NW, MLP_MFMA_MT, 1>, k_mlp_mfma_feat<NW, MLP_MFMA_MT, 2>};
-            if (smem > 48 * 1024 &&
-                hipFuncSetAttribute((const void*)ffns[fl], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-                return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the MLP kernel");
-            hipLaunchKernelGGL(ffns[fl], dim3(blocks), dim3(NTHREADS), smem, stream, net->dev, q, qcount, n_max, boards,
-                               board_stride, out, logits, feat);
-        } else if (fl == 2 && mlp_halves_ok(net->dev.H, net->dev.hw)) {
-            // the same sums with half a layer in LDS at a time, three workgroups a CU (k_mlp_mfma_halves); boards whose
-            // x passes a row of the half tile stay with the whole tile below
-            hipLaunchKernelGGL(k_mlp_mfma_halves<NW>, dim3(blocks), dim3(NTHREADS), mlp_halves_smem_bytes(net->dev.H), stream,
-                               net->dev, q, qcount, n_max, boards, board_stride, out, logits);
-        } else {
-            if (smem > 48 * 1024 &&
-                hipFuncSetAttribute((const void*)fns[fl], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-                return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the MLP kernel");
-            hipLaunchKernelGGL(fns[fl], dim3(blocks), dim3(NTHREADS), smem, stream, net->dev, q, qcount, n_max, boards,
-                               board_stride, out, logits);
-        }
-    } else if (net->dev.arch == ARCH_MLP) {
-        if (net->smem > 48 * 1024 &&
-            hipFuncSetAttribute((const void*)k_mlp<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)net->smem) !=
-                hipSuccess)
-            return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the MLP kernel");
-        hipLaunchKernelGGL(k_mlp<NW>, dim3(blocks), dim3(NTHREADS), net->smem, stream, net->dev, q, qcount, n_max, boards,
-                           board_stride, out, logits);
-    } else if (sym_mfma) {
-        const size_t smem = (size_t)2 * 32 * (net->dev.H + 4) * 4;
-        if (smem > 48 * 1024 && hipFuncSetAttribute((const void*)k_symmetric_mfma2<NW>,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-            return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the SymmetricMLP kernel");
-        hipLaunchKernelGGL(k_symmetric_mfma2<NW>, dim3(blocks), dim3(NTHREADS), smem, stream, net->dev, q, qcount, n_max, boards,
-                           board_stride, out, logits);
-    } else {
-        if (net->smem > 48 * 1024 && hipFuncSetAttribute((const void*)k_symmetric<NW>,
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                         (int)net->smem) != hipSuccess)
-            return nets_fail(AR_E_DEVICE, "cannot reserve LDS for the SymmetricMLP kernel");
-        hipLaunchKernelGGL(k_symmetric<NW>, dim3(blocks), dim3(NTHREADS), net->smem, stream, net->dev, q, qcount, n_max,
-                           boards, board_stride, out, logits);
+        // the same sums with half a layer in LDS at a time, three workgroups a CU (k_mlp_mfma_halves); boards whose
+        // x passes a row of the half tile, and a launch that stores the trunk's output, stay with the whole tile
+        if (!feat && fl == 2 && mlp_halves_ok(net->dev.H, net->dev.hw))
+            return net_launch_kernel(k_mlp_mfma_halves<NW>, "MLP", blocks, mlp_halves_smem_bytes(net->dev.H), stream, net->dev, q,
+                                     qcount, n_max, boards, board_stride, out, logits);
+        decltype(&k_mlp_mfma<NW, MLP_MFMA_MT, 0>) const fns[2][3] = {
+            {k_mlp_mfma<NW, MLP_MFMA_MT, 0>, k_mlp_mfma<NW, MLP_MFMA_MT, 1>, k_mlp_mfma<NW, MLP_MFMA_MT, 2>},
+            {k_mlp_mfma<NW, MLP_MFMA_MT, 0, true>, k_mlp_mfma<NW, MLP_MFMA_MT, 1, true>, k_mlp_mfma<NW, MLP_MFMA_MT, 2, true>}};
+        return net_launch_kernel(fns[feat ? 1 : 0][fl], "MLP", blocks, smem, stream, net->dev, q, qcount, n_max, boards,
+                                 board_stride, out, logits, feat);
     }
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return nets_fail(AR_E_DEVICE, std::string("network kernel launch failed: ") + hipGetErrorString(le));
-    return AR_OK;
+    if (net->dev.arch == ARCH_MLP)
+        return net_launch_kernel(k_mlp<NW>, "MLP", blocks, net->smem, stream, net->dev, q, qcount, n_max, boards, board_stride,
+                                 out, logits);
+    if (sym_mfma)
+        return net_launch_kernel(k_symmetric_mfma2<NW>, "SymmetricMLP", blocks, (size_t)2 * 32 * (net->dev.H + 4) * 4, stream,
+                                 net->dev, q, qcount, n_max, boards, board_stride, out, logits);
+    return net_launch_kernel(k_symmetric<NW>, "SymmetricMLP", blocks, net->smem, stream, net->dev, q, qcount, n_max, boards,
+                             board_stride, out, logits);
 }
 
 // the ownership head and its loss terms over requests whose trunk output `feat` net_launch stored (k_own_mfma)

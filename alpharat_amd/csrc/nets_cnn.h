@@ -192,7 +192,7 @@ __device__ inline void conv3x3_tile_mfma(const float* __restrict__ wt, const flo
         }
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-            const int mo = wave * 32 + (v & 3) + 8 * (v >> 2) + 4 * h2;
+            const int mo = acc_row(wave, v, h2);
             if (mo < M) {
                 const int l = mo / hw, cell = mo % hw, y = cell / w, x = cell % w;
                 emit(l, n0 + r, y, x, c0[v]);
@@ -722,7 +722,7 @@ __global__ void __launch_bounds__(NTHREADS, MT == 1 ? 3 : 2) k_cnn_mfma(CnnDev n
         else if (n_on >= 1) conv3x3_rows_mfma<MT, 1>(wt, bias, Cin, C, P, arow, rok, chs, WP, r, h2, two, c);
     };
     // result rows of this lane: tile t, register v -> row mo
-    auto row_of = [&](int t, int v) -> int { return (wave + 4 * t) * 32 + (v & 3) + 8 * (v >> 2) + 4 * h2; };
+    auto row_of = [&](int t, int v) -> int { return acc_row(wave + 4 * t, v, h2); };
     f32x16 xs[MT][2], acc[MT][2];
     if (KATAGO) {
         // stem: conv(7 -> C) with stem_bn folded, + the leaf's bias, ReLU

@@ -1,8 +1,8 @@
 // The ownership head of LocalValueMLP (alpharat/nn/models/local_value.py:103-107, 182-193) and the terms of its loss
 // (dev_ownership.h) for a tile of stored positions, on the matrix cores:
 //   logits[hw][4] = Linear(H -> 4 hw)(relu(Linear(H -> H)(features))),
-// where `features` is the trunk's output that k_mlp_mfma_feat stored. Validation only: no evaluator of the self-play loop
-// runs this head (model.predict() takes its values from value_head).
+// where `features` is the trunk's output that k_mlp_mfma<.., FEAT = true> (nets.h) stored. Validation only: no evaluator
+// of the self-play loop runs this head (model.predict() takes its values from value_head).
 //
 // One block of four wavefronts takes 64 rows. The feature tile sits in LDS as [64][H + 4], k_mlp_mfma's layout. The hidden
 // layer is one mfma_pass per wavefront (64 of the H columns each), held in the accumulators until every wavefront has read
@@ -38,201 +38,6 @@ inline size_t own_smem_bytes(int H) { return (size_t)OWN_ROWS * (H + 4) * 4; }
 template <int K>
 __device__ inline float quad_bcast(float x) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), K * 0x55, 0xF, 0xF, true));
-}
-
-// k_mlp_mfma (nets.h) restated with one more output: the trunk's output, the tile's [cnt][H] floats that the heads read
-// from `act`, also goes to feat_out[request][H]. The statements are k_mlp_mfma's, in its order (its comments explain
-// them), so the logits and values are the same bytes; the copy exists because routing both kernels through one inlined
-// body changed k_mlp_mfma's instruction stream, which the self-play loop runs (profiles/ownership_resource_usage.txt).
-// A change to k_mlp_mfma's arithmetic must be made here too: tests/test_gpu_validate_lv.py compares the two byte for byte.
-template <int NW, int MT, int FL>
-__global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_num_vgpr(128))) k_mlp_mfma_feat(NetDev net, const ar::LeafReq<NW>* q, const uint32_t* qcount,
-                                                       uint32_t n_fixed, const char* boards, size_t board_stride,
-                                                       ar::EvalOut* out, float* logits, float* feat_out) {
-    constexpr int L = 32 * MT;
-    extern __shared__ float smem[];
-    const int H = net.H, hw = net.hw, ld = H + 4;
-    float* act = smem;  // [L][ld], both hidden layers in turn
-    __shared__ LeafFeat feat[L];
-    __shared__ unsigned long long cheese[L][4];
-    __shared__ float hl[L * 12];
-    const uint32_t n = qcount ? *qcount : n_fixed;
-    const uint32_t base = blockIdx.x * L;
-    if (base >= n) return;
-    const int cnt = (int)((n - base) < (uint32_t)L ? (n - base) : (uint32_t)L);
-    const int tid = threadIdx.x;
-    if (tid < L) {
-        const int l = tid < cnt ? tid : 0;
-        const ar::LeafReq<NW>& r = q[base + l];
-        const ar::Board& b = *(const ar::Board*)(boards + (size_t)r.slot * board_stride);
-        leaf_features<NW>(r.st, b, hw, feat[tid]);
-        for (int k = 0; k < 4; ++k) cheese[tid][k] = k < NW ? r.st.cheese[k] : 0ULL;
-    }
-    __syncthreads();
-    const int wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int n0 = wave * 64;
-    const bool has = n0 < H, two = n0 + 32 < H;  // wave-uniform; H <= 64 * waves
-    const int K1 = 3 * hw + 6, K1e = (K1 + 1) & ~1;
-    constexpr bool staged = FL == 0;
-    if (FL == 2) {
-        mlp_chain_starts<L>(net, feat, act, tid);
-        __syncthreads();
-    }
-    if (staged) {
-        constexpr int TPL = NTHREADS / L;  // threads per leaf
-        const int l = tid / TPL;
-        const LeafFeat& f = feat[l];
-        float* x = act + (size_t)l * ld;
-        for (int kk = tid % TPL; kk < K1e; kk += TPL) {
-            float v;
-            if (kk < hw) v = kk == f.p1 ? 1.0f : 0.0f;
-            else if (kk < 2 * hw) v = kk - hw == f.p2 ? 1.0f : 0.0f;
-            else if (kk < 3 * hw) {
-                const int bit = kk - 2 * hw;
-                v = (cheese[l][bit >> 6] >> (bit & 63)) & 1ULL ? 1.0f : 0.0f;
-            } else v = kk < K1 ? f.sc[kk - 3 * hw] : 0.0f;
-            x[kk] = v;
-        }
-        __syncthreads();
-    }
-    f32x16 c[MT][2];
-    if (FL == 2) {
-        if (has) {
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-#pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
-                    c[t][0][v] = act[(size_t)i * ld + n0 + r];
-                    c[t][1][v] = act[(size_t)i * ld + n0 + (two ? 32 : 0) + r];
-                }
-                __builtin_amdgcn_sched_barrier(0);  // (one row tile's 32 reads at a time)
-            }
-        }
-        __syncthreads();  // the starts are in registers: `act` now takes the operand
-        {
-            const int K2 = hw + 6, K2e = (K2 + 1) & ~1;
-            constexpr int TPL = NTHREADS / L;  // threads per leaf
-            const int l = tid / TPL;
-            const LeafFeat& f = feat[l];
-            float* x = act + (size_t)l * ld;
-            for (int kk = tid % TPL; kk < K2e; kk += TPL) {
-                float v;
-                if (kk < hw) v = (cheese[l][kk >> 6] >> (kk & 63)) & 1ULL ? 1.0f : 0.0f;
-                else v = kk < K2 ? f.sc[kk - hw] : 0.0f;
-                x[kk] = v;
-            }
-        }
-        __syncthreads();
-        if (has) {
-            const float* xp = act + (size_t)r * ld + h;
-            auto x_lds = [&](int k, int t) -> float { return xp[(size_t)(32 * t) * ld + k]; };
-            mfma_pass<MT, 8>(net.w1t + (size_t)(6 * hw + h) * H + n0 + r, two, hw + 6, H, h, x_lds, c);
-        }
-    } else if (has) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
-                const float* cm = net.cmaze + (size_t)feat[i].maze_id * H + n0 + r;
-                c[t][0][v] = cm[0];
-                c[t][1][v] = cm[two ? 32 : 0];
-            }
-        const float* w1 = net.w1t + (size_t)(4 * hw + h) * H + n0 + r;
-        if (staged) {
-            const float* xp = act + (size_t)r * ld + h;
-            auto x_lds = [&](int k, int t) -> float { return xp[(size_t)(32 * t) * ld + k]; };
-            mfma_pass<MT, 8>(w1, two, K1, H, h, x_lds, c);
-        } else {
-            int p1[MT], p2[MT];
-            unsigned long long ch[MT][NW];
-            float sc[MT][6];
-#pragma unroll
-            for (int t = 0; t < MT; ++t) {
-                const LeafFeat& f = feat[32 * t + r];
-                p1[t] = f.p1;
-                p2[t] = f.p2;
-                for (int s6 = 0; s6 < 6; ++s6) sc[t][s6] = f.sc[s6];
-                for (int w = 0; w < NW; ++w) ch[t][w] = cheese[32 * t + r][w];
-            }
-            auto x_of = [&](int k, int t) -> float {
-                const int kk = k + h;
-                if (kk < hw) return kk == p1[t] ? 1.0f : 0.0f;
-                if (kk < 2 * hw) return kk - hw == p2[t] ? 1.0f : 0.0f;
-                if (kk < 3 * hw) {
-                    const int bit = kk - 2 * hw;
-                    unsigned long long word = ch[t][0];
-#pragma unroll
-                    for (int w = 1; w < NW; ++w) word = (bit >> 6) == w ? ch[t][w] : word;
-                    return (word >> (bit & 63)) & 1ULL ? 1.0f : 0.0f;
-                }
-                const int s6 = kk - 3 * hw;
-                float v = 0.0f;
-#pragma unroll
-                for (int j = 0; j < 6; ++j) v = s6 == j ? sc[t][j] : v;
-                return v;
-            };
-            mfma_pass<MT, 8>(w1, two, K1, H, h, x_of, c);
-        }
-    }
-    if (FL != 1) __syncthreads();  // every wavefront is done reading x before the results go over it
-    if (has) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
-                act[(size_t)i * ld + n0 + r] = fmaxf(c[t][0][v], 0.0f);
-                if (two) act[(size_t)i * ld + n0 + 32 + r] = fmaxf(c[t][1][v], 0.0f);
-            }
-    }
-    __syncthreads();
-    if (has) {
-        const float b0 = net.b2[n0 + r], b1 = net.b2[n0 + (two ? 32 : 0) + r];
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                c[t][0][v] = b0;
-                c[t][1][v] = b1;
-            }
-        const float* ap = act + (size_t)r * ld + h;
-        auto a_of = [&](int k, int t) -> float { return ap[(size_t)(32 * t) * ld + k]; };
-        mfma_pass<MT, 8>(net.w2t + (size_t)h * H + n0 + r, two, H, H, h, a_of, c);
-    }
-    __syncthreads();
-    if (has) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
-                act[(size_t)i * ld + n0 + r] = fmaxf(c[t][0][v], 0.0f);
-                if (two) act[(size_t)i * ld + n0 + 32 + r] = fmaxf(c[t][1][v], 0.0f);
-            }
-    }
-    __syncthreads();
-    {
-        const int H4 = H >> 2;
-        for (int item = tid; item < cnt * H4; item += NTHREADS) {
-            const int l = item / H4, c4 = item - l * H4;
-            ((float4*)(feat_out + (size_t)(base + l) * H))[c4] = *(const float4*)(act + (size_t)l * ld + 4 * c4);
-        }
-    }
-    heads_mfma16(net.wh, net.bh, 12, H, act, ld, hl, tid, 2 * MT);
-    __syncthreads();
-    if (tid < cnt) {
-        const float* hh = hl + tid * 12;
-        ar::EvalOut o;
-        softmax5(hh, o.p1);
-        softmax5(hh + 5, o.p2);
-        o.v1 = softplusf(hh[10]);
-        o.v2 = softplusf(hh[11]);
-        out[base + tid] = o;
-        if (logits)
-            for (int k = 0; k < 10; ++k) logits[(size_t)(base + tid) * 10 + k] = hh[k];
-    }
 }
 
 // `feat` [n][H]: the trunk's output of request i; `req` [n]: its position and, as `slot`, its stored game; `outcomes`
@@ -289,7 +94,7 @@ __global__ void __launch_bounds__(NTHREADS) k_own_mfma(OwnDev own, const float* 
             for (int t = 0; t < MT; ++t)
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
-                    const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                    const int i = acc_row(t, v, h);
                     act[(size_t)i * ld + n0 + r] = fmaxf(c[t][0][v], 0.0f);
                     if (two) act[(size_t)i * ld + n0 + 32 + r] = fmaxf(c[t][1][v], 0.0f);
                 }
@@ -330,7 +135,7 @@ __global__ void __launch_bounds__(NTHREADS) k_own_mfma(OwnDev own, const float* 
                 for (int s = 0; s < 2; ++s)
 #pragma unroll
                     for (int v = 0; v < 16; ++v) {
-                        const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * h;
+                        const int i = acc_row(t, v, h);
                         const int col = q0 + 32 * s + r;
                         const float x = c[t][s][v];
                         if (logits && i < cnt && col < 4 * hw) logits[(size_t)(base + i) * row_floats + col] = x;

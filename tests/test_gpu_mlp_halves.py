@@ -96,8 +96,8 @@ def test_both_sides_of_the_host_rule(w, h, kernel, tmp_path, monkeypatch):
 
 
 def test_feat_kernel_gives_the_bits_of_the_halved_evaluator(tmp_path):
-    """H = 256 with an ownership head on 5x5, 65 rows: validate_lv runs k_mlp_mfma_feat (a whole tile in LDS, the
-    structure k_mlp_mfma has), validate runs k_mlp_mfma_halves"""
+    """H = 256 with an ownership head on 5x5, 65 rows: validate_lv runs k_mlp_mfma with FEAT (a whole tile in
+    LDS), validate runs k_mlp_mfma_halves"""
     from alpharat_amd.nets import Net
     from alpharat_amd.shards import RowSet
     from alpharat_amd.weights import write_blob

@@ -23,8 +23,9 @@ them against the oracle). Bit for bit (test_gpu_boards.py's _same_bits) are:
   H = 32 and 64 the two comparisons are one);
 - a leaf evaluated in a call of 1, 63, 64 or 65, taken from the front and from the back of the 130, against the call of
   130: the same leaf at other rows of a tile, next to other leaves, in a partial tile;
-- k_mlp_mfma_feat against k_mlp_mfma at H = 96, through RowSet.validate_lv and RowSet.validate on the rows of
-  tests/_validate.py's "5x5 open" board (its entry point takes a seeded net of any width)."""
+- k_mlp_mfma with FEAT (the trunk's output stored as well) against the evaluator without it at H = 96, through
+  RowSet.validate_lv and RowSet.validate on the rows of tests/_validate.py's "5x5 open" board (its entry point takes a
+  seeded net of any width), at the default first-layer variant and at AR_MLP_FL = 0 and 1."""
 import numpy as np
 import pytest
 import torch  # noqa: F401  before anything loads libalpharat_hip (INTEGRATION.md)
@@ -78,8 +79,8 @@ def test_outputs_at_every_width_and_leaf_count(H, leaves, tmp_path, monkeypatch)
 
 
 def test_feat_kernel_gives_the_bits_of_the_evaluator(tmp_path):
-    """H = 96 (a starts pass of 4 and one of 2) with an ownership head: validate_lv runs k_mlp_mfma_feat, validate runs
-    k_mlp_mfma"""
+    """H = 96 (a starts pass of 4 and one of 2) with an ownership head: validate_lv runs k_mlp_mfma<.., FEAT = true>,
+    validate runs the evaluator of the self-play loop"""
     from alpharat_amd.nets import Net
     from alpharat_amd.shards import RowSet
     from alpharat_amd.weights import write_blob
@@ -102,4 +103,35 @@ def test_feat_kernel_gives_the_bits_of_the_evaluator(tmp_path):
             for k in keys:
                 assert out[k].tobytes() == out_lv[k].tobytes(), (cnt, k)
                 np.testing.assert_allclose(out_lv[k], want[k][idx], atol=1e-5, rtol=1e-5, err_msg=f"{cnt} rows {k}")
+    net.close()
+
+
+def test_feat_kernel_at_every_first_layer_variant(tmp_path, monkeypatch):
+    """k_mlp_mfma<.., FEAT = true> with FL = 0 and FL = 1, which no other test launches: 5x5 and H = 96, so that
+    K1e = 82 <= H + 4 and AR_MLP_FL=0 really is variant 0; 65 rows, a full tile and a tile of one. Under either setting
+    validate_lv (FEAT) and validate (no FEAT) give the same sums and the same bytes of logits and values, and those are
+    the bytes of the default run (FL = 2)."""
+    from alpharat_amd.nets import Net
+    from alpharat_amd.shards import RowSet
+    from alpharat_amd.weights import write_blob
+
+    H, cnt = 96, 65
+    games, rows = V.board("5x5 open")
+    t = random_mlp(5, 5, H, V.SEED)
+    net = Net(write_blob(tmp_path / "h96.lv.arnet", "mlp", 5, 5, {**t, **ON.random_ownership(5, 5, H, 17)}))
+    assert net.has_ownership
+    idx = np.arange(cnt) % len(rows["value_p1"])
+    keys = ("logits_p1", "logits_p2", "value_p1", "value_p2")
+    with RowSet(5, 5, len(rows["value_p1"])) as rs:
+        rs.add_games(games)
+        monkeypatch.delenv("AR_MLP_FL", raising=False)
+        sums_ref, _, out_ref = rs.validate_lv(net, idx, return_rows=True)
+        for fl in ("0", "1"):
+            monkeypatch.setenv("AR_MLP_FL", fl)
+            sums_lv, _, out_lv = rs.validate_lv(net, idx, return_rows=True)
+            sums, out = rs.validate(net, idx, return_rows=True)
+            assert sums == sums_lv == sums_ref, fl
+            for k in keys:
+                assert out_lv[k].tobytes() == out[k].tobytes(), (fl, k)
+                assert out_lv[k].tobytes() == out_ref[k].tobytes(), (fl, k)
     net.close()

@@ -1,5 +1,5 @@
-"""Validation of a local_value checkpoint with its ownership head on the device: ar_rows_validate_lv (k_mlp_mfma_feat,
-k_own_mfma, k_own_sum), RowSet.validate_lv and alpharat_amd/validate.py OwnSums / local_value_metrics, against the float64
+"""Validation of a local_value checkpoint with its ownership head on the device: ar_rows_validate_lv (k_mlp_mfma with
+FEAT, k_own_mfma, k_own_sum), RowSet.validate_lv and alpharat_amd/validate.py OwnSums / local_value_metrics, against the float64
 restatement of the head and its loss (tests/_ownership_np.py, tied to the reference by tests/golden/ownership).
 
 The rows are the oracle games of tests/_rows.py BOARDS. Their recorded outcomes are lopsided (few SIMULTANEOUS, no P2_WIN
