@@ -37,6 +37,7 @@
 #include "dev_agents.h"
 #include "dev_rows.h"
 #include "dev_validate.h"
+#include "host_games.h"
 #include "zig_norm_tables.inc"
 
 using namespace ar;
@@ -1642,181 +1643,19 @@ __global__ void __launch_bounds__(64) k_match_move_agents(Slot<NW>* sa, Slot<NW>
 }
 
 // ------------------------------------------------------------------------------------------------
-// host: game generation (our own seeded sampler, DESIGN.md "game generation")
+// host (game generation and the supply of a run's games: host_games.h)
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-struct HostRng {  // same generator family as the device stream, host copy for game generation
-    Rng r;
-    explicit HostRng(uint64_t seed) { rng_seed(r, seed); }
-    uint32_t below(uint32_t n) { return rng_below(r, n); }
-};
-
-struct HostGame {
-    uint8_t width, height;
-    uint16_t max_turns, turn;
-    uint8_t p1, p2, m1, m2;
-    float s1, s2;
-    std::vector<uint8_t> cheese;  // [hw]
-    uint16_t total_cheese;
-    std::vector<uint8_t> cost;    // [hw * 4] this game's generated maze; empty = the run's shared maze
-};
-
-// 180-degree-symmetric cheese: shuffle the pair representatives (i < N-1-i, start cells excluded)
-// with Fisher-Yates driven by gen_range, take count/2 pairs; an odd count uses the centre cell.
-bool place_cheese(HostGame& g, uint32_t count, bool symmetric, uint64_t seed, std::string& err) {
-    const int n = g.width * g.height;
-    g.cheese.assign(n, 0);
-    HostRng rng(seed);
-    std::vector<int> cand;
-    uint32_t need = count;
-    if (symmetric) {
-        int centre = -1;
-        for (int i = 0; i < n; ++i) {
-            const int j = n - 1 - i;
-            if (i == g.p1 || i == g.p2 || j == g.p1 || j == g.p2) continue;
-            if (i < j) cand.push_back(i);
-            else if (i == j) centre = i;
-        }
-        if (need & 1u) {
-            if (centre < 0) {
-                err = "odd symmetric cheese count needs a free centre cell";
-                return false;
-            }
-            g.cheese[centre] = 1;
-            need -= 1;
-        }
-        if (need / 2 > cand.size()) {
-            err = "cheese_count does not fit the board";
-            return false;
-        }
-        for (int i = (int)cand.size() - 1; i >= 1; --i) std::swap(cand[i], cand[rng.below((uint32_t)i + 1)]);
-        for (uint32_t k = 0; k < need / 2; ++k) {
-            g.cheese[cand[k]] = 1;
-            g.cheese[n - 1 - cand[k]] = 1;
-        }
-    } else {
-        for (int i = 0; i < n; ++i)
-            if (i != g.p1 && i != g.p2) cand.push_back(i);
-        if (need > cand.size()) {
-            err = "cheese_count does not fit the board";
-            return false;
-        }
-        for (int i = (int)cand.size() - 1; i >= 1; --i) std::swap(cand[i], cand[rng.below((uint32_t)i + 1)]);
-        for (uint32_t k = 0; k < need; ++k) g.cheese[cand[k]] = 1;
-    }
-    g.total_cheese = (uint16_t)count;
-    return true;
-}
-
-std::vector<uint8_t> open_maze_cost(int w, int h) {
-    std::vector<uint8_t> c((size_t)w * h * 4, 0);
-    for (int y = 0; y < h; ++y)
-        for (int x = 0; x < w; ++x) {
-            uint8_t* p = &c[((size_t)y * w + x) * 4];
-            p[DIR_UP] = y + 1 < h;
-            p[DIR_RIGHT] = x + 1 < w;
-            p[DIR_DOWN] = y > 0;
-            p[DIR_LEFT] = x > 0;
-        }
-    return c;
-}
-
-// Random walls + mud: the reference delegates to the pyrat-rust engine (absent, own RNG), so this is our
-// own generator -- specification in DESIGN.md "game generation", second implementation in
-// oracle/pyrat_engine.hpp::make_maze (the two are compared game by game in the parity tests).
-std::vector<uint8_t> generate_maze(int w, int h, float wall_density, float mud_density, bool symmetric, uint64_t seed) {
-    HostRng rng(seed ^ 0x6D617A65ULL);
-    const int n = w * h;
-    std::vector<std::pair<int, int>> ed;  // (a, b), a < b; per cell: RIGHT then UP
-    std::vector<int> right_of(n, -1), up_of(n, -1);
-    for (int i = 0; i < n; ++i) {
-        if (i % w + 1 < w) {
-            right_of[i] = (int)ed.size();
-            ed.emplace_back(i, i + 1);
-        }
-        if (i / w + 1 < h) {
-            up_of[i] = (int)ed.size();
-            ed.emplace_back(i, i + w);
-        }
-    }
-    const int ne = (int)ed.size();
-    std::vector<int> image(ne);
-    for (int k = 0; k < ne; ++k) {
-        if (!symmetric) {
-            image[k] = k;
-            continue;
-        }
-        const int a = n - 1 - ed[k].second, b = n - 1 - ed[k].first;  // a < b again
-        image[k] = b == a + 1 ? right_of[a] : up_of[a];
-    }
-    std::vector<uint8_t> val(ne, 1);
-    const uint32_t wall_thr = (uint32_t)(wall_density * 16777216.0f), mud_thr = (uint32_t)(mud_density * 16777216.0f);
-    for (int k = 0; k < ne; ++k)
-        if (k <= image[k] && rng.below(1u << 24) < wall_thr) val[k] = val[image[k]] = 0;
-    std::vector<int> up(n);
-    for (int i = 0; i < n; ++i) up[i] = i;
-    int comps = n;
-    auto root = [&](int v) {
-        while (up[v] != v) v = up[v] = up[up[v]];
-        return v;
-    };
-    auto join = [&](int a, int b) {
-        a = root(a);
-        b = root(b);
-        if (a == b) return;
-        if (a < b) up[b] = a;
-        else up[a] = b;
-        --comps;
-    };
-    for (int k = 0; k < ne; ++k)
-        if (val[k]) join(ed[k].first, ed[k].second);
-    std::vector<int> closed;
-    for (int k = 0; k < ne; ++k)
-        if (k <= image[k] && !val[k]) closed.push_back(k);
-    for (int i = (int)closed.size() - 1; i >= 1; --i) std::swap(closed[i], closed[rng.below((uint32_t)i + 1)]);
-    for (int k : closed) {
-        if (comps == 1) break;
-        const int m = image[k];
-        if (root(ed[k].first) == root(ed[k].second) && root(ed[m].first) == root(ed[m].second)) continue;
-        val[k] = val[m] = 1;
-        join(ed[k].first, ed[k].second);
-        join(ed[m].first, ed[m].second);
-    }
-    for (int k = 0; k < ne; ++k)
-        if (k <= image[k] && val[k] && rng.below(1u << 24) < mud_thr) val[k] = val[image[k]] = (uint8_t)(2 + rng.below(2));
-    std::vector<uint8_t> c((size_t)n * 4, 0);
-    for (int k = 0; k < ne; ++k) {
-        const int a = ed[k].first, b = ed[k].second;
-        const int d = b == a + 1 ? DIR_RIGHT : DIR_UP;
-        c[(size_t)a * 4 + d] = val[k];
-        c[(size_t)b * 4 + ((d + 2) & 3)] = val[k];
-    }
-    return c;
-}
-
+// a new game's record for k_init_games; the caller sets rng_seed and single
 template <int NW>
-void fill_state(const HostGame& g, Board& b, State<NW>& st, uint32_t maze_off) {
-    b.width = g.width;
-    b.height = g.height;
-    b.max_turns = g.max_turns;
-    b.total_cheese = g.total_cheese;
-    b.maze_off = maze_off;
-    for (int k = 0; k < NW; ++k) st.cheese[k] = 0;
-    uint16_t rem = 0;
-    for (size_t i = 0; i < g.cheese.size(); ++i)
-        if (g.cheese[i]) {
-            st.cheese[NW == 1 ? 0 : (i >> 6)] |= 1ULL << (i & 63);
-            ++rem;
-        }
-    st.remaining = rem;
-    st.s1 = g.s1;
-    st.s2 = g.s2;
-    st.turn = g.turn;
-    st.p1 = g.p1;
-    st.p2 = g.p2;
-    st.m1 = g.m1;
-    st.m2 = g.m2;
+GameInit<NW> game_init(const HostGame& g, uint32_t slot, uint32_t index, uint32_t maze_off) {
+    GameInit<NW> gi;
+    memset(&gi, 0, sizeof gi);
+    fill_state<NW>(g, gi.board, gi.st, maze_off);
+    gi.game_index = index;
+    gi.slot = slot;
+    return gi;
 }
 
 SearchCfg to_cfg(const ArSearchConfig& c, uint32_t sims, uint32_t batch) {
@@ -1853,7 +1692,49 @@ int check_cfg(const SearchCfg& c) {
 // ------------------------------------------------------------------------------------------------
 // host: the engine -- device-resident slots and the step loop
 // ------------------------------------------------------------------------------------------------
-struct GameRecordHost {  // owning twin of ArGameRecordView
+// A game's positions and moves as the columns of its record (self-play and match records share them)
+struct PosColumns {
+    std::vector<uint8_t> p1_pos, p2_pos, p1_mud, p2_mud, cheese_mask, a1, a2;
+    std::vector<float> p1_score, p2_score;
+    std::vector<uint16_t> turn;
+    void resize(size_t n, int hw) {
+        for (auto* v : {&p1_pos, &p2_pos}) v->resize(n * 2);
+        for (auto* v : {&p1_mud, &p2_mud, &a1, &a2}) v->resize(n);
+        for (auto* v : {&p1_score, &p2_score}) v->resize(n);
+        turn.resize(n);
+        cheese_mask.resize(n * hw);
+    }
+    template <int NW>
+    void set(size_t i, const State<NW>& s, uint32_t act1, uint32_t act2, int w, int hw) {
+        p1_pos[i * 2] = s.p1 % w;
+        p1_pos[i * 2 + 1] = s.p1 / w;
+        p2_pos[i * 2] = s.p2 % w;
+        p2_pos[i * 2 + 1] = s.p2 / w;
+        p1_mud[i] = s.m1;
+        p2_mud[i] = s.m2;
+        turn[i] = s.turn;
+        p1_score[i] = s.s1;
+        p2_score[i] = s.s2;
+        for (int c = 0; c < hw; ++c) cheese_mask[i * hw + c] = st_has_cheese(s, c) ? 1 : 0;
+        a1[i] = (uint8_t)act1;
+        a2[i] = (uint8_t)act2;
+    }
+    template <typename View>
+    void point(View& v) const {  // ArGameRecordView / ArMatchGameView
+        v.p1_pos = p1_pos.data();
+        v.p2_pos = p2_pos.data();
+        v.p1_score = p1_score.data();
+        v.p2_score = p2_score.data();
+        v.p1_mud = p1_mud.data();
+        v.p2_mud = p2_mud.data();
+        v.turn = turn.data();
+        v.cheese_mask = cheese_mask.data();
+        v.action_p1 = a1.data();
+        v.action_p2 = a2.data();
+    }
+};
+
+struct GameRecordHost : PosColumns {  // owning twin of ArGameRecordView
     uint8_t width, height;
     uint16_t max_turns;
     uint32_t game_index, n;
@@ -1863,9 +1744,7 @@ struct GameRecordHost {  // owning twin of ArGameRecordView
     uint8_t result;
     uint16_t cheese_available;
     uint64_t sims, nn, term, coll;
-    std::vector<uint8_t> p1_pos, p2_pos, p1_mud, p2_mud, cheese_mask, a1, a2;
-    std::vector<float> p1_score, p2_score, v1, v2, vc1, vc2, pr1, pr2, po1, po2;
-    std::vector<uint16_t> turn;
+    std::vector<float> v1, v2, vc1, vc2, pr1, pr2, po1, po2;
     ArGameRecordView view() const {
         ArGameRecordView v;
         memset(&v, 0, sizeof v);
@@ -1885,14 +1764,7 @@ struct GameRecordHost {  // owning twin of ArGameRecordView
         v.total_nn_evals = nn;
         v.total_terminals = term;
         v.total_collisions = coll;
-        v.p1_pos = p1_pos.data();
-        v.p2_pos = p2_pos.data();
-        v.p1_score = p1_score.data();
-        v.p2_score = p2_score.data();
-        v.p1_mud = p1_mud.data();
-        v.p2_mud = p2_mud.data();
-        v.turn = turn.data();
-        v.cheese_mask = cheese_mask.data();
+        point(v);
         v.value_p1 = v1.data();
         v.value_p2 = v2.data();
         v.visit_counts_p1 = vc1.data();
@@ -1901,8 +1773,6 @@ struct GameRecordHost {  // owning twin of ArGameRecordView
         v.prior_p2 = pr2.data();
         v.policy_p1 = po1.data();
         v.policy_p2 = po2.data();
-        v.action_p1 = a1.data();
-        v.action_p2 = a2.data();
         return v;
     }
 };
@@ -2177,9 +2047,28 @@ struct Engine {
         return GatherKernel::Lane;
     }
 
+    // What a driver decides before setup(). `n`: the evaluator, nullptr = SmartUniform; `host_eval`: the leaves go to the
+    // caller's predict_fn instead. SmartUniform runs in the fused step kernel, or in the split pipeline of the network path
+    // with k_uniform_eval as its evaluator: the default for `games` resident games, or AR_UNIFORM=fused | queue (results
+    // are identical). `slot_maze_cells` != 0: generated mazes, one pool entry of that many cells per slot, filled when a
+    // game starts there. `arena_knob`: the run honours the AR_ARENA_NODES test knob (small arenas: trees stall and grow).
+    uint32_t arena_nodes = 0;
+    void configure(ArNet* n, uint32_t games, uint32_t slot_maze_cells, bool arena_knob = true, bool host_eval = false) {
+        net = host_eval ? nullptr : n;
+        const char* e = getenv("AR_UNIFORM");
+        uniform_queue = !host_eval && net == nullptr && (e ? std::string(e) == "queue" : default_uniform_queue(games));
+        per_slot_maze = slot_maze_cells != 0;
+        maze_stride = slot_maze_cells * 4u;
+        arena_nodes = arena_knob && getenv("AR_ARENA_NODES") ? (uint32_t)atoi(getenv("AR_ARENA_NODES")) : 0u;
+    }
+
+    // After configure(). `shared_maze`: the maze pool of a run without generated mazes.
     // `tree_bytes`: device memory for the trees (0 = one smallest block per game: every growth goes through the host)
-    int setup(int device, uint32_t n_slots, const SearchCfg& c, uint32_t mt, const std::vector<uint8_t>& maze_bytes,
-              uint32_t arena_nodes, bool need_queue, size_t tree_bytes = 0) {
+    int setup(int device, uint32_t n_slots, const SearchCfg& c, uint32_t mt, const std::vector<uint8_t>& shared_maze,
+              size_t tree_bytes = 0) {
+        const std::vector<uint8_t> slot_mazes(per_slot_maze ? (size_t)n_slots * maze_stride : 0, (uint8_t)0);
+        const std::vector<uint8_t>& maze_bytes = per_slot_maze ? slot_mazes : shared_maze;
+        const bool need_queue = use_queue();
         dev = device;
         S = n_slots;
         cfg = c;
@@ -2685,6 +2574,22 @@ struct Engine {
         return AR_OK;
     }
 
+    // What the host does after a run of steps: the scan (`c` as scan() fills it), the guard of the tree kernels, and room
+    // for the stalled trees. `may_wait`: a tree that cannot grow now may wait while other games are active (c[2]).
+    // `secs`, when given, gains the wall time of the scan in [0] and of the rest in [1] (the AR_TIMING line).
+    int visit(uint32_t c[4], bool may_wait = false, double* secs = nullptr) {
+        const auto t0 = std::chrono::steady_clock::now();
+        int rc = scan(c);
+        const auto t1 = std::chrono::steady_clock::now();
+        if (rc == AR_OK && c[3] != 0) rc = fail(AR_E_DEVICE, "internal capacity guard tripped in a tree kernel (slot.error != 0)");
+        if (rc == AR_OK) rc = handle_stalls(c[1], may_wait && c[2] > 0);
+        if (secs) {
+            secs[0] += std::chrono::duration<double>(t1 - t0).count();
+            secs[1] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+        }
+        return rc;
+    }
+
     // copies the finished games' headers + positions to pinned host memory and frees their slots
     int drain(uint32_t n_done) {
         if (n_done == 0) return AR_OK;
@@ -2725,15 +2630,7 @@ void record_from_device(const DoneInfo<NW>& d, const PosRec<NW>* pos, const Host
     r.term = d.t_term;
     r.coll = d.t_coll;
     const size_t n = r.n;
-    r.p1_pos.resize(n * 2);
-    r.p2_pos.resize(n * 2);
-    r.p1_mud.resize(n);
-    r.p2_mud.resize(n);
-    r.cheese_mask.resize(n * hw);
-    r.a1.resize(n);
-    r.a2.resize(n);
-    r.p1_score.resize(n);
-    r.p2_score.resize(n);
+    r.resize(n, hw);
     r.v1.resize(n);
     r.v2.resize(n);
     r.vc1.resize(n * 5);
@@ -2742,19 +2639,9 @@ void record_from_device(const DoneInfo<NW>& d, const PosRec<NW>* pos, const Host
     r.pr2.resize(n * 5);
     r.po1.resize(n * 5);
     r.po2.resize(n * 5);
-    r.turn.resize(n);
     for (size_t i = 0; i < n; ++i) {
         const PosRec<NW>& p = pos[i];
-        r.p1_pos[i * 2] = p.st.p1 % w;
-        r.p1_pos[i * 2 + 1] = p.st.p1 / w;
-        r.p2_pos[i * 2] = p.st.p2 % w;
-        r.p2_pos[i * 2 + 1] = p.st.p2 / w;
-        r.p1_mud[i] = p.st.m1;
-        r.p2_mud[i] = p.st.m2;
-        r.turn[i] = p.st.turn;
-        r.p1_score[i] = p.st.s1;
-        r.p2_score[i] = p.st.s2;
-        for (int c = 0; c < hw; ++c) r.cheese_mask[i * hw + c] = st_has_cheese(p.st, c) ? 1 : 0;
+        r.set(i, p.st, p.a1, p.a2, w, hw);
         r.v1[i] = p.res.value[0];
         r.v2[i] = p.res.value[1];
         memcpy(&r.vc1[i * 5], p.res.visit_counts[0], 20);
@@ -2763,8 +2650,6 @@ void record_from_device(const DoneInfo<NW>& d, const PosRec<NW>* pos, const Host
         memcpy(&r.pr2[i * 5], p.res.prior[1], 20);
         memcpy(&r.po1[i * 5], p.res.policy[0], 20);
         memcpy(&r.po2[i * 5], p.res.policy[1], 20);
-        r.a1[i] = p.a1;
-        r.a2[i] = p.a2;
     }
     // selfplay.rs:415-471 compute_cheese_outcomes: the rule is dev_rows.h rows_cell_outcome, which an attached row set runs on
     // the device for the same records
@@ -3464,11 +3349,10 @@ template <int NW>
 struct SelfPlaySession : SessionBase {
     ArSelfPlayParams p;  // strings are copied below; the pointers in here are not used after open()
     SearchCfg cfg;
+    GameSupply supply;
     std::vector<uint8_t> cost;
-    int hw = 0;
-    uint64_t gseed = 0, rseed = 0;
-    bool random_pos = false, gen_maze = false, maze_sym = true, unbounded = false;
-    float wall_d = 0.0f, mud_d = 0.0f;
+    uint64_t rseed = 0;
+    bool unbounded = false;
     uint32_t S = 0;
     Engine<NW> eng;
     ArNet* net = nullptr;  // owned by the ArSelfPlaySession wrapper (freed after the engine)
@@ -3531,25 +3415,6 @@ struct SelfPlaySession : SessionBase {
         // the engine has to go first -- done explicitly in close(); here only as a last resort
     }
 
-    bool make_game(uint32_t index, HostGame& g) {
-        if (gen_maze) g.cost = generate_maze(p.width, p.height, wall_d, mud_d, maze_sym, gseed + index);
-        g.width = p.width;
-        g.height = p.height;
-        g.max_turns = p.max_turns;
-        g.turn = 0;
-        g.m1 = g.m2 = 0;
-        g.s1 = g.s2 = 0.0f;
-        g.p1 = 0;
-        g.p2 = (uint8_t)(hw - 1);
-        if (random_pos) {
-            HostRng rng((gseed + index) ^ 0x9E3779B97F4A7C15ULL);
-            g.p1 = (uint8_t)rng.below((uint32_t)hw);
-            g.p2 = (uint8_t)(hw - 1 - g.p1);
-            if (!p.cheese_symmetric) g.p2 = (uint8_t)rng.below((uint32_t)hw);
-        }
-        return place_cheese(g, p.cheese_count, p.cheese_symmetric != 0, gseed + index, err);
-    }
-
     bool supply_left() const { return unbounded || next_game < p.num_games; }
     bool all_finished() const { return !unbounded && finished >= p.num_games; }
 
@@ -3587,26 +3452,24 @@ struct SelfPlaySession : SessionBase {
             }
             slot_busy[sl] = 1;
             zone_busy[sl / POOL_ZONE_SLOTS] += 1;
-            const uint32_t index = p.first_game_index + (uint32_t)next_game;  // wraps in an unbounded session
+            const uint32_t index = supply.index(next_game);
             HostGame g;
-            if (!make_game(index, g)) return fail(AR_E_INVALID, err);
-            GameInit<NW> gi;
-            memset(&gi, 0, sizeof gi);
-            fill_state<NW>(g, gi.board, gi.st, gen_maze ? sl * eng.maze_stride : 0u);
-            if (gen_maze) mazes.insert(mazes.end(), g.cost.begin(), g.cost.end());
+            if (!supply.make_game(index, g, err)) return fail(AR_E_INVALID, err);
+            GameInit<NW> gi = game_init<NW>(g, sl, index, sl * eng.maze_stride);
+            mazes.insert(mazes.end(), g.cost.begin(), g.cost.end());
             gi.rng_seed = rseed + index;
-            gi.game_index = index;
-            gi.slot = sl;
             gi.single = 0;
             inits.push_back(gi);
             slot_game[sl] = std::move(g);
             ++next_game;
         }
-        return eng.start_games(inits, gen_maze ? &mazes : nullptr);
+        return eng.start_games(inits, supply.gen_maze ? &mazes : nullptr);
     }
 
-    int open(const ArSelfPlayParams& params, int device, ArNet* owned_net, ArProgress* prog, ArGameSink sk, void* sk_user) {
+    int open(const ArSelfPlayParams& params, const GameSupply& games, int device, ArNet* owned_net, ArProgress* prog,
+             ArGameSink sk, void* sk_user) {
         p = params;
+        supply = games;
         net = owned_net;
         progress = prog;
         sink = sk;
@@ -3617,24 +3480,8 @@ struct SelfPlaySession : SessionBase {
         cfg = to_cfg(p.search, p.simulations, p.batch_size);
         if (int rc = check_cfg(cfg)) return rc;
         cost = open_maze_cost(p.width, p.height);
-        hw = p.width * p.height;
         unbounded = p.num_games == 0xFFFFFFFFu;
-
-        gseed = p.game_seed_base;
-        rseed = p.rng_seed_base;
-        if (!p.has_seed) {  // reference behaviour: entropy (selfplay.rs:622, bindings.rs:530-532)
-            std::random_device rd;
-            gseed = ((uint64_t)rd() << 32) | rd();
-            rseed = ((uint64_t)rd() << 32) | rd();
-        }
-        random_pos = p.positions && std::string(p.positions) == "random";
-        // "classic" = the engine's default walls and mud (bindings.rs:507 with_classic_maze; taken here as density
-        // 0.7 / 0.1, symmetric -- the defaults of the binding's own signature), "random" = the caller's parameters
-        const std::string maze_type = p.maze_type ? p.maze_type : "open";
-        gen_maze = maze_type != "open";
-        wall_d = maze_type == "classic" ? 0.7f : p.wall_density;
-        mud_d = maze_type == "classic" ? 0.1f : p.mud_density;
-        maze_sym = maze_type == "classic" ? true : p.maze_symmetric != 0;
+        rseed = p.has_seed ? p.rng_seed_base : entropy_seed();
         to_disk = p.output_dir != nullptr;
         if (to_disk) {
             writer.dir = p.output_dir;
@@ -3646,9 +3493,9 @@ struct SelfPlaySession : SessionBase {
         S = p.concurrent_games ? p.concurrent_games : 16384;
         if (S > p.num_games) S = p.num_games;
         size_t pool_bytes = 0;
-        const uint32_t arena_nodes = getenv("AR_ARENA_NODES") ? (uint32_t)atoi(getenv("AR_ARENA_NODES")) : 0u;  // test knob
         t0 = std::chrono::steady_clock::now();
         if (S == 0) return AR_OK;
+        eng.configure(net, S, supply.gen_maze ? (uint32_t)supply.hw : 0u);
         {
             size_t free_b = 0, total_b = 0;
             if (hipSetDevice(device) != hipSuccess) return fail(AR_E_DEVICE, "hipSetDevice failed");
@@ -3656,17 +3503,13 @@ struct SelfPlaySession : SessionBase {
             free_b += arena_cached_bytes(device);  // the block kept from the previous call is ours to reuse
             if (const char* e = getenv("AR_MEM_FRACTION"))  // several processes on one device (bench rehearsals): each
                 if (atof(e) > 0.0 && atof(e) <= 1.0) free_b = (size_t)((double)free_b * atof(e));  // takes its share
-            // SmartUniform runs: the fused step kernel, or the split pipeline of the network path with k_uniform_eval as
-            // its evaluator (AR_UNIFORM=fused | queue; results are identical)
-            eng.uniform_queue = net == nullptr && default_uniform_queue(S);
-            if (const char* e = getenv("AR_UNIFORM")) eng.uniform_queue = net == nullptr && std::string(e) == "queue";
             // device memory per resident game: its scratch and queue share, and its tree. A tree lives in a block of the
             // smallest size class (4/3 apart) that holds it plus one full search; averaged over a game's life that is about
             // twice a fresh game's block at the tuned 7x7 configuration (measured: mean tree top 2150 nodes at 1897
             // simulations per move), which is what the resident count is sized by -- games beyond what the region can
             // serve would only wait for blocks.
-            const size_t fresh = arena_bytes(arena_nodes ? arena_nodes : initial_arena_nodes(cfg));
-            const size_t overhead = Engine<NW>::per_game_overhead(cfg, p.max_turns, net != nullptr || eng.uniform_queue);
+            const size_t fresh = arena_bytes(eng.arena_nodes ? eng.arena_nodes : initial_arena_nodes(cfg));
+            const size_t overhead = Engine<NW>::per_game_overhead(cfg, p.max_turns, eng.use_queue());
             const size_t reserve = (size_t)4 << 30;  // the evaluator's buffers, arenas beyond the largest class (host-allocated)
             const size_t usable = free_b > reserve ? free_b - reserve : 0;
             const size_t per_game = 2 * fresh + overhead;
@@ -3681,7 +3524,6 @@ struct SelfPlaySession : SessionBase {
         auto since = [](std::chrono::steady_clock::time_point a) {
             return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count();
         };
-        eng.net = net;
         if (p.cache_size && net != nullptr) {
             // the reference sizes one table per worker thread (capacity x 1.9 slots, nn_cache.rs:49); one table
             // serves every game here, so it gets the threads' worth, rounded up to a power of two
@@ -3693,16 +3535,10 @@ struct SelfPlaySession : SessionBase {
         if (getenv("AR_NO_POOL")) pool_bytes = 0;  // test knob: one smallest block per game, every growth goes through the host path
         if (const char* e = getenv("AR_TREE_GB"))  // test knob: a small tree region (games wait for blocks, trees move between classes)
             if (atof(e) > 0.0) pool_bytes = (size_t)(atof(e) * 1073741824.0);
-        eng.per_slot_maze = gen_maze;
-        eng.maze_stride = (uint32_t)hw * 4u;
         // rounds per gather launch (dev_search.h gather_machine_limited): no limit unless AR_GATHER_ROUNDS sets one
         // (0 = no limit); a limit keeps the walk on the lane kernel
         if (const char* e = getenv("AR_GATHER_ROUNDS")) eng.gather_rounds = atoi(e) > 0 ? (uint32_t)atoi(e) : 0xFFFFFFFFu;
-        {
-            // generated mazes: one pool entry per slot (filled when a game starts there); open: the one shared maze
-            const std::vector<uint8_t> pool_init = gen_maze ? std::vector<uint8_t>((size_t)S * hw * 4, (uint8_t)0) : cost;
-            if (int rc = eng.setup(device, S, cfg, p.max_turns, pool_init, arena_nodes, net != nullptr || eng.uniform_queue, pool_bytes)) return rc;
-        }
+        if (int rc = eng.setup(device, S, cfg, p.max_turns, cost, pool_bytes)) return rc;
         tm[0] = since(tp);
         {
             // groups of games pipelined against each other (Engine::group_step); AR_GROUPS overrides
@@ -3828,20 +3664,11 @@ struct SelfPlaySession : SessionBase {
             auto tp = now();
             if ((rc = run_chunk(chunk)) != AR_OK) break;
             tm[2] += since(tp);
-            tp = now();
             uint32_t c[4];
-            if ((rc = eng.scan(c)) != AR_OK) break;
+            if ((rc = eng.visit(c, true, &tm[3])) != AR_OK) break;  // (tm[3] scan-wait, tm[4] grow)
             for (int k = 0; k < LIVE_N; ++k) live[k] = eng.h_live.p[k];
             if (eng.h_live.p[13] >= 256)  // tree pages of a game that has played a few moves, in this run
                 pages_per_game = std::max((double)eng.pool.fresh_pages, 1.1 * (double)eng.h_live.p[12] / (double)eng.h_live.p[13]);
-            tm[3] += since(tp);
-            tp = now();
-            if (c[3] != 0) {
-                rc = fail(AR_E_DEVICE, "internal capacity guard tripped in a tree kernel (slot.error != 0)");
-                break;
-            }
-            if (c[1] && (rc = eng.handle_stalls(c[1], c[2] > 0)) != AR_OK) break;
-            tm[4] += since(tp);
             tp = now();
             if (c[0]) {
                 const uint32_t n_done = c[0];
@@ -4010,22 +3837,16 @@ int search_impl(const ArGameSpec* games, uint32_t n, const SearchCfg& cfg, const
         if (hg[i].max_turns > max_turns) max_turns = hg[i].max_turns;
     }
     Engine<NW> eng;
-    eng.net = predict_fn ? nullptr : net;
-    eng.uniform_queue = !predict_fn && net == nullptr && default_uniform_queue(n);
-    if (const char* e = getenv("AR_UNIFORM")) eng.uniform_queue = !predict_fn && net == nullptr && std::string(e) == "queue";
+    eng.configure(net, n, 0u, /*arena_knob=*/false, /*host_eval=*/predict_fn != nullptr);
     if (eng.net != nullptr)
         for (uint32_t i = 0; i < n; ++i)
             if (games[i].width != net->dev.width || games[i].height != net->dev.height)
                 return fail(AR_E_INVALID, "game size does not match the network's board size");
-    if (int rc = eng.setup(device, n, cfg, max_turns, mazes, 0, eng.use_queue())) return rc;
+    if (int rc = eng.setup(device, n, cfg, max_turns, mazes)) return rc;
     std::vector<GameInit<NW>> inits(n);
-    std::random_device rd;
     for (uint32_t i = 0; i < n; ++i) {
-        memset(&inits[i], 0, sizeof inits[i]);
-        fill_state<NW>(hg[i], inits[i].board, inits[i].st, maze_off[i]);
-        inits[i].rng_seed = seeds ? seeds[i] : (((uint64_t)rd() << 32) | rd());
-        inits[i].game_index = i;
-        inits[i].slot = i;
+        inits[i] = game_init<NW>(hg[i], i, i, maze_off[i]);
+        inits[i].rng_seed = seeds ? seeds[i] : entropy_seed();
         inits[i].single = 1;
     }
     if (int rc = eng.start_games(inits)) return rc;
@@ -4045,12 +3866,8 @@ int search_impl(const ArGameSpec* games, uint32_t n, const SearchCfg& cfg, const
         const int w = hg[0].width;
         for (;;) {
             uint32_t c[4];
-            if (int rc = eng.scan(c)) return rc;
-            if (c[3]) return fail(AR_E_DEVICE, "internal capacity guard tripped in a tree kernel");
-            if (c[1]) {
-                if (int rc = eng.handle_stalls(c[1])) return rc;
-                continue;
-            }
+            if (int rc = eng.visit(c)) return rc;
+            if (c[1]) continue;
             if (c[2] == 0) break;
             eng.launch_gather(false);
             hipLaunchKernelGGL(k_export_leaves<NW>, dim3(1), dim3(64), 0, eng.stream, eng.slots.p, 0u, eng.bases(),
@@ -4098,11 +3915,7 @@ int search_impl(const ArGameSpec* games, uint32_t n, const SearchCfg& cfg, const
         for (;;) {
             if (int rc = eng.run_steps(4, 8)) return rc;
             uint32_t c[4];
-            if (int rc = eng.scan(c)) return rc;
-            if (c[3]) return fail(AR_E_DEVICE, "internal capacity guard tripped in a tree kernel");
-            if (c[1]) {
-                if (int rc = eng.handle_stalls(c[1])) return rc;
-            }
+            if (int rc = eng.visit(c)) return rc;
             if (c[2] == 0 && c[1] == 0) break;
         }
     }
@@ -4175,12 +3988,10 @@ struct MatchRun {
     bool has_a = true, has_b = true;
     AgentDesc da, db;
     hipStream_t own_stream = nullptr, ms = nullptr;  // ms: the stream the match's own kernels run on
+    GameSupply supply;
     std::vector<uint8_t> cost;
-    int hw = 0;
     uint32_t S = 0;
-    uint64_t gseed = 0, seed_a = 0, seed_b = 0;
-    bool random_pos = false, gen_maze = false, maze_sym = true;
-    float wall_d = 0.0f, mud_d = 0.0f;
+    uint64_t seed_a = 0, seed_b = 0;
     DevBuf<MatchGame<NW>> games, info;
     DevBuf<MatchPos<NW>> recs, staging;
     DevBuf<MatchAux<NW>> aux;
@@ -4209,39 +4020,16 @@ struct MatchRun {
         if (ev_m) hipEventDestroy(ev_m);
     }
 
-    bool make_game(uint32_t index, HostGame& g) {  // the game self-play generates for this index (SelfPlaySession::make_game)
-        if (gen_maze) g.cost = generate_maze(p.width, p.height, wall_d, mud_d, maze_sym, gseed + index);
-        g.width = p.width;
-        g.height = p.height;
-        g.max_turns = p.max_turns;
-        g.turn = 0;
-        g.m1 = g.m2 = 0;
-        g.s1 = g.s2 = 0.0f;
-        g.p1 = 0;
-        g.p2 = (uint8_t)(hw - 1);
-        if (random_pos) {
-            HostRng rng((gseed + index) ^ 0x9E3779B97F4A7C15ULL);
-            g.p1 = (uint8_t)rng.below((uint32_t)hw);
-            g.p2 = (uint8_t)(hw - 1 - g.p1);
-            if (!p.cheese_symmetric) g.p2 = (uint8_t)rng.below((uint32_t)hw);
-        }
-        return place_cheese(g, p.cheese_count, p.cheese_symmetric != 0, gseed + index, err);
-    }
-
     int setup_engine(Engine<NW>& e, const SearchCfg& cfg, ArNet* net, int device) {
-        e.net = net;
-        e.uniform_queue = net == nullptr && default_uniform_queue(S);
-        if (const char* env = getenv("AR_UNIFORM")) e.uniform_queue = net == nullptr && std::string(env) == "queue";
+        e.configure(net, S, supply.gen_maze ? (uint32_t)supply.hw : 0u);
         e.overlap_advance = false;  // one stream per engine: every hand-off is in stream order (phase 0)
-        e.per_slot_maze = gen_maze;
-        e.maze_stride = (uint32_t)hw * 4u;
-        const std::vector<uint8_t> pool_init = gen_maze ? std::vector<uint8_t>((size_t)S * hw * 4, (uint8_t)0) : cost;
-        const uint32_t arena_nodes = getenv("AR_ARENA_NODES") ? (uint32_t)atoi(getenv("AR_ARENA_NODES")) : 0u;  // test knob
-        return e.setup(device, S, cfg, p.max_turns, pool_init, arena_nodes, e.use_queue());
+        return e.setup(device, S, cfg, p.max_turns, cost);
     }
 
-    int open(const ArMatchParams& params, int device, ArNet* net_a, ArNet* net_b, ArMatchSink sk, void* sk_user) {
+    int open(const ArMatchParams& params, const GameSupply& match_games, int device, ArNet* net_a, ArNet* net_b, ArMatchSink sk,
+             void* sk_user) {
         p = params;
+        supply = match_games;
         sink = sk;
         sink_user = sk_user;
         memset(&st, 0, sizeof st);
@@ -4252,22 +4040,10 @@ struct MatchRun {
         da = AgentDesc{p.a.kind, p.a.temperature, cfg_a.n_sims, 0u};
         db = AgentDesc{p.b.kind, p.b.temperature, cfg_b.n_sims, 0u};
         cost = open_maze_cost(p.width, p.height);
-        hw = p.width * p.height;
-        gseed = p.game_seed_base;
-        seed_a = p.a.rng_seed_base;
-        seed_b = p.b.rng_seed_base;
-        if (!p.has_seed) {
-            std::random_device rd;
-            gseed = ((uint64_t)rd() << 32) | rd();
-            seed_a = ((uint64_t)rd() << 32) | rd();
-            seed_b = ((uint64_t)rd() << 32) | rd();
-        }
-        random_pos = p.positions && std::string(p.positions) == "random";
-        const std::string maze_type = p.maze_type ? p.maze_type : "open";
-        gen_maze = maze_type != "open";
-        wall_d = maze_type == "classic" ? 0.7f : p.wall_density;
-        mud_d = maze_type == "classic" ? 0.1f : p.mud_density;
-        maze_sym = maze_type == "classic" ? true : p.maze_symmetric != 0;
+        seed_a = p.has_seed ? p.a.rng_seed_base : entropy_seed();
+        seed_b = p.has_seed ? p.b.rng_seed_base : entropy_seed();
+        const int hw = supply.hw;
+        const bool gen_maze = supply.gen_maze;
         p.maze_type = p.positions = p.device = p.a.weights_path = p.b.weights_path = nullptr;  // caller-owned strings
 
         S = p.concurrent_games ? p.concurrent_games : 4096u;
@@ -4326,15 +4102,11 @@ struct MatchRun {
         std::vector<uint8_t> mazes;
         for (uint32_t sl : free_slots) {
             if (next_game >= p.num_games) break;
-            const uint32_t index = p.first_game_index + next_game;
+            const uint32_t index = supply.index(next_game);
             HostGame g;
-            if (!make_game(index, g)) return fail(AR_E_INVALID, err);
-            GameInit<NW> gi;
-            memset(&gi, 0, sizeof gi);
-            fill_state<NW>(g, gi.board, gi.st, gen_maze ? sl * ((uint32_t)hw * 4u) : 0u);
-            if (gen_maze) mazes.insert(mazes.end(), g.cost.begin(), g.cost.end());
-            gi.game_index = index;
-            gi.slot = sl;
+            if (!supply.make_game(index, g, err)) return fail(AR_E_INVALID, err);
+            GameInit<NW> gi = game_init<NW>(g, sl, index, sl * maze_stride);
+            mazes.insert(mazes.end(), g.cost.begin(), g.cost.end());
             gi.single = 1;  // the search stops in SLOT_DONE; the move is the match's
             gi.rng_seed = seed_a + index;
             ia.push_back(gi);
@@ -4354,12 +4126,12 @@ struct MatchRun {
         }
         if (mi.empty()) return AR_OK;
         if (has_a)
-            if (int rc = ea.start_games(ia, gen_maze ? &mazes : nullptr)) return rc;
+            if (int rc = ea.start_games(ia, supply.gen_maze ? &mazes : nullptr)) return rc;
         if (has_b)
-            if (int rc = eb.start_games(ib, gen_maze ? &mazes : nullptr)) return rc;
+            if (int rc = eb.start_games(ib, supply.gen_maze ? &mazes : nullptr)) return rc;
         // (the engines' streams are at rest: start_games waits for its kernel)
         HIP_TRY(hipMemcpyAsync(init.p, mi.data(), sizeof(MatchAuxInit<NW>) * mi.size(), hipMemcpyHostToDevice, ms));
-        if (gen_maze) HIP_TRY(hipMemcpyAsync(maze_stage.p, mazes.data(), mazes.size(), hipMemcpyHostToDevice, ms));
+        if (supply.gen_maze) HIP_TRY(hipMemcpyAsync(maze_stage.p, mazes.data(), mazes.size(), hipMemcpyHostToDevice, ms));
         hipLaunchKernelGGL(k_match_init_agents<NW>, dim3((uint32_t)mi.size()), dim3(64), 0, ms, games.p, aux.p, slots_a(), slots_b(),
                            (const MatchAuxInit<NW>*)init.p, (uint32_t)mi.size(), (const uint8_t*)maze_stage.p, maze.p, maze_stride);
         HIP_TRY(hipGetLastError());
@@ -4420,27 +4192,14 @@ struct MatchRun {
             st.collisions_b += pos[i].b.collisions;
         }
         if (!sink) return;
-        const int w = p.width;
-        std::vector<uint8_t> p1_pos(n * 2), p2_pos(n * 2), p1_mud(n), p2_mud(n), mask(n * hw), a1(n), a2(n);
-        std::vector<float> s1(n), s2(n);
-        std::vector<uint16_t> turn(n);
+        PosColumns col;
+        col.resize(n, supply.hw);
         MatchSideHost sa, sb;
         sa.resize(n);
         sb.resize(n);
         for (size_t i = 0; i < n; ++i) {
             const MatchPos<NW>& q = pos[i];
-            p1_pos[i * 2] = q.st.p1 % w;
-            p1_pos[i * 2 + 1] = q.st.p1 / w;
-            p2_pos[i * 2] = q.st.p2 % w;
-            p2_pos[i * 2 + 1] = q.st.p2 / w;
-            p1_mud[i] = q.st.m1;
-            p2_mud[i] = q.st.m2;
-            turn[i] = q.st.turn;
-            s1[i] = q.st.s1;
-            s2[i] = q.st.s2;
-            for (int c = 0; c < hw; ++c) mask[i * hw + c] = st_has_cheese(q.st, c) ? 1 : 0;
-            a1[i] = q.a1;
-            a2[i] = q.a2;
+            col.set(i, q.st, q.a1, q.a2, p.width, supply.hw);
             sa.set(i, q.a);
             sb.set(i, q.b);
         }
@@ -4455,16 +4214,7 @@ struct MatchRun {
         v.result = result;
         v.final_p1_score = f1;
         v.final_p2_score = f2;
-        v.p1_pos = p1_pos.data();
-        v.p2_pos = p2_pos.data();
-        v.p1_score = s1.data();
-        v.p2_score = s2.data();
-        v.p1_mud = p1_mud.data();
-        v.p2_mud = p2_mud.data();
-        v.turn = turn.data();
-        v.cheese_mask = mask.data();
-        v.action_p1 = a1.data();
-        v.action_p2 = a2.data();
+        col.point(v);
         v.a = sa.view();
         v.b = sb.view();
         sink(sink_user, &v);
@@ -4474,14 +4224,9 @@ struct MatchRun {
     int visit() {
         uint32_t ca[4] = {0, 0, 0, 0}, cb[4] = {0, 0, 0, 0};
         if (has_a)
-            if (int rc = ea.scan(ca)) return rc;
+            if (int rc = ea.visit(ca, true)) return rc;
         if (has_b)
-            if (int rc = eb.scan(cb)) return rc;
-        if (ca[3] || cb[3]) return fail(AR_E_DEVICE, "internal capacity guard tripped in a tree kernel (slot.error != 0)");
-        if (ca[1])
-            if (int rc = ea.handle_stalls(ca[1], ca[2] > 0)) return rc;
-        if (cb[1])
-            if (int rc = eb.handle_stalls(cb[1], cb[2] > 0)) return rc;
+            if (int rc = eb.visit(cb, true)) return rc;
         HIP_TRY(hipMemsetAsync(counts.p, 0, 32, ms));
         hipLaunchKernelGGL(k_match_scan<NW>, dim3(grid(S)), dim3(64), 0, ms, (const MatchGame<NW>*)games.p, S, counts.p,
                            done_list.p);
@@ -4543,10 +4288,19 @@ struct MatchRun {
 };
 
 template <int NW>
-int match_impl(const ArMatchParams& p, int dev, ArNet* net_a, ArNet* net_b, ArMatchSink sink, void* user, ArMatchStats* out) {
+int match_impl(const ArMatchParams& p, const GameSupply& games, int dev, ArNet* net_a, ArNet* net_b, ArMatchSink sink, void* user,
+               ArMatchStats* out) {
     MatchRun<NW> run;  // (destroyed before the caller frees the evaluators: ~Engine synchronises its streams)
-    if (int rc = run.open(p, dev, net_a, net_b, sink, user)) return rc;
+    if (int rc = run.open(p, games, dev, net_a, net_b, sink, user)) return rc;
     return run.run(out);
+}
+
+// the reference fails on the ONNX input shape when the model was trained for another board (`who`: "" or "agent A: ")
+int check_net_board(const ArNet* net, int width, int height, const std::string& who = "") {
+    if (net->dev.width == width && net->dev.height == height) return AR_OK;
+    return fail(AR_E_INVALID, who + "the network was built for a " + std::to_string(net->dev.width) + "x" +
+                                  std::to_string(net->dev.height) + " board, the games are " + std::to_string(width) + "x" +
+                                  std::to_string(height));
 }
 
 }  // namespace
@@ -4741,34 +4495,25 @@ int ar_selfplay_open(const ArSelfPlayParams* p, ArProgress* progress, ArGameSink
                      ArSelfPlaySession** out) {
     if (!p || !out) return fail(AR_E_INVALID, "null argument");
     *out = nullptr;
-    const std::string mt = p->maze_type ? p->maze_type : "open";
-    if (mt != "open") {
-        if (mt != "classic" && mt != "random") return fail(AR_E_INVALID, "unknown maze_type: " + mt);
-    }
-    const std::string pos = p->positions ? p->positions : "corners";
-    if (pos != "corners" && pos != "random") return fail(AR_E_INVALID, "unknown positions: " + pos);
-    if (p->width == 0 || p->height == 0 || (int)p->width * p->height > 256)
-        return fail(AR_E_INVALID, "board must have 1..256 cells");
+    GameSupply games;
+    std::string err;
+    if (!games.init(*p, err)) return fail(AR_E_INVALID, err);
     int dev = 0;
     if (int rc = parse_device(p->device, p->device_index, dev)) return rc;
     std::unique_ptr<ArSelfPlaySession> s(new ArSelfPlaySession());
     if (p->weights_path) {
         if (int rc = ar_net_load(p->weights_path, dev, &s->net)) return rc;
-        // the reference fails on the ONNX input shape when the model was trained for another board
-        if (s->net->dev.width != p->width || s->net->dev.height != p->height)
-            return fail(AR_E_INVALID, "the network was built for a " + std::to_string(s->net->dev.width) + "x" +
-                                          std::to_string(s->net->dev.height) + " board, the games are " +
-                                          std::to_string(p->width) + "x" + std::to_string(p->height));
+        if (int rc = check_net_board(s->net, p->width, p->height)) return rc;
     }
     int rc;
-    if ((int)p->width * p->height <= 64) {
+    if (games.hw <= 64) {
         auto* impl = new SelfPlaySession<1>();
         s->impl = impl;
-        rc = impl->open(*p, dev, s->net, progress, sink, sink_user);
+        rc = impl->open(*p, games, dev, s->net, progress, sink, sink_user);
     } else {
         auto* impl = new SelfPlaySession<4>();
         s->impl = impl;
-        rc = impl->open(*p, dev, s->net, progress, sink, sink_user);
+        rc = impl->open(*p, games, dev, s->net, progress, sink, sink_user);
     }
     if (rc != AR_OK) return rc;
     *out = s.release();
@@ -4936,12 +4681,9 @@ int ar_rows_validate_lv(ArRowSet* s, ArNet* net, const uint64_t* rows, uint64_t 
 int ar_match_run(const ArMatchParams* p, ArMatchSink sink, void* sink_user, ArMatchStats* out) {
     if (!p || !out) return fail(AR_E_INVALID, "null argument");
     memset(out, 0, sizeof *out);
-    const std::string mt = p->maze_type ? p->maze_type : "open";
-    if (mt != "open" && mt != "classic" && mt != "random") return fail(AR_E_INVALID, "unknown maze_type: " + mt);
-    const std::string pos = p->positions ? p->positions : "corners";
-    if (pos != "corners" && pos != "random") return fail(AR_E_INVALID, "unknown positions: " + pos);
-    if (p->width == 0 || p->height == 0 || (int)p->width * p->height > 256)
-        return fail(AR_E_INVALID, "board must have 1..256 cells");
+    GameSupply games;
+    std::string err;
+    if (!games.init(*p, err)) return fail(AR_E_INVALID, err);
     const ArMatchAgent* agents[2] = {&p->a, &p->b};
     for (int k = 0; k < 2; ++k) {
         const ArMatchAgent& ag = *agents[k];
@@ -4968,13 +4710,10 @@ int ar_match_run(const ArMatchParams* p, ArMatchSink sink, void* sink_user, ArMa
     for (int k = 0; k < 2; ++k) {
         if (!agents[k]->weights_path) continue;
         if (int rc = ar_net_load(agents[k]->weights_path, dev, &nets.n[k])) return rc;
-        if (nets.n[k]->dev.width != p->width || nets.n[k]->dev.height != p->height)
-            return fail(AR_E_INVALID, std::string("agent ") + (k ? "B" : "A") + ": the network was built for a " +
-                                          std::to_string(nets.n[k]->dev.width) + "x" + std::to_string(nets.n[k]->dev.height) +
-                                          " board, the games are " + std::to_string(p->width) + "x" + std::to_string(p->height));
+        if (int rc = check_net_board(nets.n[k], p->width, p->height, k ? "agent B: " : "agent A: ")) return rc;
     }
-    return (int)p->width * p->height <= 64 ? match_impl<1>(*p, dev, nets.n[0], nets.n[1], sink, sink_user, out)
-                                           : match_impl<4>(*p, dev, nets.n[0], nets.n[1], sink, sink_user, out);
+    return games.hw <= 64 ? match_impl<1>(*p, games, dev, nets.n[0], nets.n[1], sink, sink_user, out)
+                          : match_impl<4>(*p, games, dev, nets.n[0], nets.n[1], sink, sink_user, out);
 }
 
 int ar_net_load(const char* blob_path, int device, ArNet** out) {

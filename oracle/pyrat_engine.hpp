@@ -257,7 +257,7 @@ inline bool make_cheese(GameState& g, uint16_t count, bool symmetric, uint64_t s
 // Random walls + mud. The reference delegates this to the pyrat-rust engine (GameBuilder::with_random_maze /
 // with_classic_maze, bindings.rs:505-517), whose generator and RNG (rand 0.10) are not in the container:
 // PARITY UNPINNED. This is our own generator, specified in DESIGN.md "game generation" and implemented
-// twice (here and in alpharat_hip.hip::generate_maze):
+// twice (here and in alpharat_amd/csrc/host_games.h generate_maze):
 //   edges in the order (cell 0..n-1: RIGHT edge, then UP edge); with symmetry an edge and its 180-degree
 //   image (cells i -> n-1-i) are decided together, the one with the smaller index deciding;
 //   1. every deciding edge becomes a wall when below(2^24) < (u32)(wall_density * 2^24);

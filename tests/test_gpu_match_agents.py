@@ -1,7 +1,7 @@
 """-m gpu: device-resident matches with agents that do not search (ar_match_run: k_match_greedy, the engine-less path,
 k_match_move_agents) and with a sampling temperature, against the semantics restated on the CPU (tests/_agents.py
 oracle_game) at record level: positions, both actions, both agents' search outputs and counters, results and scores.
-Bar: bit-exact."""
+Bar: bit-exact. Last: a match's games against self-play's and the CPU harness of the game supply (tests/hostsim_games)."""
 from pathlib import Path
 
 import numpy as np
@@ -139,3 +139,34 @@ def test_pure_network_agent_against_random(temperature):
     ev = HipEvaluator(blob, 5, 5, 30)
     a = A.Agent(A.SEARCH, M.Agent(O.make_config(), 1, 1, SEED_A, backend=4, net=ev.backend), temperature)
     _compare(games, lambda i: O.Game(5, 5, 30).random_cheese(5, True, i), a, A.Agent(A.RANDOM, seed=SEED_B), (0, 5, 11))
+
+
+def test_a_match_plays_the_games_self_play_generates():
+    """Generated mazes and random start cells: game i of a match is the game self-play generates for the same index, and
+    both are the game of the one GameSupply (tests/hostsim_games, the same header on the CPU)."""
+    import _games as G
+    from alpharat_amd.match import MatchAgent, play_match
+    from alpharat_amd.sampling import rust_self_play
+
+    res = play_match(MatchAgent.random(seed=SEED_A), MatchAgent.greedy(), num_games=8, seed=3, positions="random",
+                     keep_games=True, **MAZE7)
+    match = _by_index(res)
+    played = {}
+    rust_self_play(num_games=8, seed=3, positions="random", simulations=8, batch_size=4, output_dir=None,
+                   on_game=lambda g: played.__setitem__(g["game_index"], g), **MAZE7)
+    assert sorted(match) == sorted(played) == list(range(8))
+    starts = set()
+    for i in range(8):
+        want = G.make_game(i, seed=3, positions="random", **MAZE7)
+        assert want["index"] == i and want["generated"]
+        for rec, who in ((match[i], "match"), (played[i], "self-play")):
+            for side in ("p1", "p2"):
+                x, y = (int(v) for v in rec[f"{side}_pos"][0])
+                assert y * 7 + x == want[side], (i, who, side)
+            np.testing.assert_array_equal(rec["cheese_mask"][0], want["cheese"], err_msg=f"game {i}, {who}")
+        np.testing.assert_array_equal(match[i]["p1_pos"][0], played[i]["p1_pos"][0])
+        np.testing.assert_array_equal(match[i]["p2_pos"][0], played[i]["p2_pos"][0])
+        np.testing.assert_array_equal(match[i]["cheese_mask"][0], played[i]["cheese_mask"][0])
+        np.testing.assert_array_equal(np.where(played[i]["maze"] < 0, 0, played[i]["maze"]), want["cost"], err_msg=f"maze {i}")
+        starts.add((want["p1"], want["p2"]))
+    assert len(starts) > 2  # (drawn, not the corners)
