@@ -202,6 +202,22 @@ class ArOwnRows(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("ce", "cells", "value", "logits")]
 
 
+MLP_TENSORS = ("trunk0_w", "trunk0_b", "bn1_w", "bn1_b", "trunk4_w", "trunk4_b", "bn2_w", "bn2_b", "p1_w", "p1_b", "p2_w", "p2_b",
+               "value_w", "value_b")
+
+
+class ArMlpTensors(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in MLP_TENSORS]
+
+
+class ArMlpBnStats(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("mean1", "var1", "mean2", "var2")]
+
+
+class ArTrainOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("losses", "logits_p1", "logits_p2", "value_p1", "value_p2")]
+
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -247,6 +263,9 @@ EXPORTS = {
     "ar_rows_validate_lv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                       C.POINTER(ArValSums), C.POINTER(ArOwnSums), C.POINTER(ArValRows),
                                       C.POINTER(ArOwnRows)]),
+    "ar_rows_grad_mlp": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArMlpTensors),
+                                   C.POINTER(ArMlpTensors), C.POINTER(ArMlpBnStats), C.c_float, C.c_float,
+                                   C.POINTER(ArTrainOut), C.c_void_p]),
 }
 
 _lib = None

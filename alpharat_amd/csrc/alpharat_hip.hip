@@ -37,6 +37,7 @@
 #include "dev_agents.h"
 #include "dev_rows.h"
 #include "dev_validate.h"
+#include "train_mlp.h"
 #include "host_games.h"
 #include "zig_norm_tables.inc"
 
@@ -2799,6 +2800,9 @@ struct RowStore {
     DevBuf<OwnAcc> own_total;
     size_t own_feat_n = 0, own_logits_n = 0;
     uint32_t own_chunk = 0;
+    // ar_rows_grad_mlp: the workspace of one training step (train_mlp.h), one allocation grown to the largest request
+    DevBuf<uint8_t> train_ws;
+    size_t train_ws_bytes = 0;
     // uploads and builds run on the null stream: they wait for the attached session's last append, nothing else
     hipError_t wait_appends() const { return has_append ? hipEventSynchronize(ev_append) : hipSuccess; }
 
@@ -3146,6 +3150,236 @@ static hipError_t regrow(DevBuf<T>& b, size_t count) {
         if (e != hipSuccess) return e;
     }
     return b.alloc(count);
+}
+
+// ar_rows_grad_mlp: the loss and the gradients of PyRatMLP over rows first .. first + n of the order (train_mlp.h), on the
+// caller's stream. Everything is checked before the first launch; it then only launches, and allocates only when the
+// workspace must grow (after waiting for what may still use the old one). ev_batch sits behind the last launch, so
+// whatever waits for pending batches waits for a pending step too.
+static const char* const kMlpTensorNames[14] = {"trunk0_w", "trunk0_b", "bn1_w",  "bn1_b",  "trunk4_w", "trunk4_b", "bn2_w",
+                                                "bn2_b",    "p1_w",     "p1_b",   "p2_w",   "p2_b",     "value_w",  "value_b"};
+template <int NW>
+int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const ArMlpTensors& p, const ArMlpTensors& g,
+                  const ArMlpBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream) {
+    if (!R.has_order) return fail(AR_E_INVALID, "the row set has no order: ar_rows_order_set comes first");
+    if (first > R.ord_n || n64 > R.ord_n - first)
+        return fail(AR_E_INVALID, "rows " + std::to_string(first) + " + " + std::to_string(n64) + " go beyond the order of " +
+                                      std::to_string(R.ord_n));
+    if (n64 < 2) return fail(AR_E_INVALID, "a training BatchNorm needs at least two rows");
+    if (n64 > (uint64_t)TRAIN_MAX_ROWS) return fail(AR_E_INVALID, "at most 65536 rows a step");
+    if (H == 0 || H % 32 != 0 || H > 256)
+        return fail(AR_E_INVALID, "hidden_dim must be a multiple of 32, at most 256 (got " + std::to_string(H) + ")");
+    static_assert(sizeof(ArMlpTensors) == 14 * sizeof(float*), "fourteen pointers");
+    float* const* pp = (float* const*)&p;
+    float* const* gp = (float* const*)&g;
+    for (int i = 0; i < 14; ++i) {
+        if (!pp[i] || !gp[i]) return fail(AR_E_INVALID, std::string("null tensor: ") + kMlpTensorNames[i]);
+        if (int rc = rows_check_device_ptr(R, pp[i], 4, kMlpTensorNames[i])) return rc;
+        if (int rc = rows_check_device_ptr(R, gp[i], 4, kMlpTensorNames[i])) return rc;
+    }
+    if (run) {
+        float* const rs[4] = {run->mean1, run->var1, run->mean2, run->var2};
+        for (float* q : rs) {
+            if (!q) return fail(AR_E_INVALID, "null running statistic");
+            if (int rc = rows_check_device_ptr(R, q, 4, "running statistic")) return rc;
+        }
+    }
+    if (out) {
+        float* const os[5] = {out->losses, out->logits_p1, out->logits_p2, out->value_p1, out->value_p2};
+        for (float* q : os)
+            if (q)
+                if (int rc = rows_check_device_ptr(R, q, 4, "output")) return rc;
+    }
+    const int n = (int)n64, D = (int)rows_obs_dim(R.hw), Hi = (int)H;
+    // fixed partitions: of the rows for the column sums, of the batch for the products reduced over it
+    TrainCols tc;
+    tc.n = n;
+    tc.H = Hi;
+    tc.P = std::min<int>(TRAIN_MAX_PARTS, (n + 63) / 64);
+    tc.rpp = (n + tc.P - 1) / tc.P;
+    tc.P = (n + tc.rpp - 1) / tc.rpp;
+    int S = std::min<int>(TRAIN_MAX_SPLITS, (n + 255) / 256);
+    const int kps = ((n + S - 1) / S + TG_KC - 1) / TG_KC * TG_KC;
+    S = (n + kps - 1) / kps;
+    const int head_blocks = (n + TRAIN_HEAD_ROWS - 1) / TRAIN_HEAD_ROWS;
+    // the workspace: offsets into one allocation, every array 256-byte aligned
+    size_t total = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t nH = (size_t)n * H * 4;
+    const size_t o_x = take((size_t)n * D * 4), o_t1 = take((size_t)n * 20), o_t2 = take((size_t)n * 20), o_y1 = take((size_t)n * 4),
+                 o_y2 = take((size_t)n * 4), o_a1 = take(n), o_a2 = take(n), o_co = take((size_t)n * R.hw), o_z1 = take(nH),
+                 o_act1 = take(nH), o_z2 = take(nH), o_act2 = take(nH), o_dout = take((size_t)n * 48), o_dz2 = take(nH),
+                 o_dz1 = take(nH), o_parts = take((size_t)6 * TRAIN_MAX_PARTS * H * 8), o_mean = take((size_t)2 * H * 8), o_rstd = take((size_t)2 * H * 4),
+                 o_wpart = take((size_t)S * H * std::max(D, Hi) * 4), o_bpart = take((size_t)S * H * 4),
+                 o_lpart = take((size_t)head_blocks * 32), o_loss = take(6 * 4);
+    int before = 0;
+    HIP_TRY(hipGetDevice(&before));  // the caller's framework keeps its own current device
+    if (before != R.device) HIP_TRY(hipSetDevice(R.device));
+    if (total > R.train_ws_bytes) {
+        hipError_t e = R.wait_batches();  // a pending step may still use the old workspace
+        if (e == hipSuccess) e = regrow(R.train_ws, total);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            R.train_ws_bytes = 0;
+            if (before != R.device) (void)hipSetDevice(before);
+            return fail(AR_E_NOMEM, "not enough device memory for a training workspace of " + std::to_string(total) + " bytes");
+        }
+        R.train_ws_bytes = total;
+    }
+    uint8_t* ws = R.train_ws.p;
+    auto F = [&](size_t at) { return (float*)(ws + at); };
+    float *X = F(o_x), *Z1 = F(o_z1), *A1 = F(o_act1), *Z2 = F(o_z2), *A2 = F(o_act2), *dOut = F(o_dout), *dZ2 = F(o_dz2),
+          *dZ1 = F(o_dz1), *rstds = F(o_rstd), *wpart = F(o_wpart), *bpart = F(o_bpart);
+    double *parts = (double*)(ws + o_parts), *means = (double*)(ws + o_mean);
+    auto part = [&](int i) { return parts + (size_t)i * TRAIN_MAX_PARTS * H; };
+    hipError_t err = hipSuccess;
+    // the workspace is shared by every step of this set: a step on another stream starts behind the last one
+    if (R.has_batch) err = hipStreamWaitEvent(stream, R.ev_batch, 0);
+    auto launched = [&]() {
+        if (err == hipSuccess) err = hipGetLastError();
+    };
+    RowOut ro;
+    ro.observation = X;
+    ro.policy_p1 = F(o_t1);
+    ro.policy_p2 = F(o_t2);
+    ro.value_p1 = F(o_y1);
+    ro.value_p2 = F(o_y2);
+    ro.action_p1 = (int8_t*)(ws + o_a1);
+    ro.action_p2 = (int8_t*)(ws + o_a2);
+    ro.cheese_outcomes = (int8_t*)(ws + o_co);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(k_rows_batch<NW>, dim3((n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(ROWS_PER_BLOCK * ROWS_LANES), 0,
+                           stream, (const PosRec<NW>*)R.recs.p, (const uint32_t*)R.pos_game.p, (const RowGame*)R.games.p,
+                           (const uint8_t*)R.mazes.p, (const uint8_t*)R.outcomes.p, (const uint64_t*)R.ord_rows.p,
+                           (const uint8_t*)R.ord_swap.p, first, (uint64_t)0, (uint32_t)n, ro);
+        launched();
+    }
+    // C[M][N] = sum_k A(m, k) B(k, n)
+    auto gemm = [&](const float* a, long sam, long sak, int a_kfast, const float* b, long sbk, long sbn, int b_kfast, float* c, int M,
+                    int N, int K, const float* bias, int splits, int k_per_split, float* colsum) {
+        if (err != hipSuccess) return;
+        TrainGemm t;
+        t.a = a;
+        t.b = b;
+        t.bias = bias;
+        t.c = c;
+        t.colsum = colsum;
+        t.M = M;
+        t.N = N;
+        t.K = K;
+        t.k_per_split = k_per_split;
+        t.ldc = N;
+        t.sam = sam;
+        t.sak = sak;
+        t.sbk = sbk;
+        t.sbn = sbn;
+        t.c_split = (size_t)M * N;
+        t.a_kfast = a_kfast;
+        t.b_kfast = b_kfast;
+        hipLaunchKernelGGL(k_train_gemm, dim3((N + TG_TILE - 1) / TG_TILE, (M + TG_TILE - 1) / TG_TILE, splits), dim3(TG_THREADS), 0,
+                           stream, t);
+        launched();
+    };
+    // dW = dOut^T In and db = colsum(dOut) over the batch: per row range, then the ranges in order
+    auto grad_w = [&](const float* d, int M, const float* in, int N, float* w0, float* b0, int r0, float* w1, float* b1, int r1,
+                      float* w2, float* b2, int r2) {
+        gemm(d, 1, M, 0, in, N, 1, 0, wpart, M, N, n, nullptr, S, kps, bpart);
+        if (err != hipSuccess) return;
+        TrainReduce t;
+        t.wpart = wpart;
+        t.bpart = bpart;
+        t.S = S;
+        t.M = M;
+        t.N = N;
+        t.w[0] = w0, t.w[1] = w1, t.w[2] = w2;
+        t.b[0] = b0, t.b[1] = b1, t.b[2] = b2;
+        t.rows[0] = r0, t.rows[1] = r1, t.rows[2] = r2;
+        const size_t count = (size_t)M * N + M;
+        hipLaunchKernelGGL(k_train_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, t);
+        launched();
+    };
+    const dim3 cgrid((H + 63) / 64, tc.P);
+    // z -> relu(bn(z)) with the batch's statistics (two passes over z), layer 0 / 1
+    auto bn_forward = [&](int layer, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
+        if (err != hipSuccess) return;
+        TrainColArgs a;
+        memset(&a, 0, sizeof a);
+        a.z = z;
+        a.part0 = part(2 * layer);
+        hipLaunchKernelGGL(k_train_colsum<TC_SUM>, cgrid, dim3(256), 0, stream, tc, a);
+        a.sum_in = part(2 * layer);
+        a.part0 = part(2 * layer + 1);
+        hipLaunchKernelGGL(k_train_colsum<TC_SQ>, cgrid, dim3(256), 0, stream, tc, a);
+        hipLaunchKernelGGL(k_train_bn_apply, cgrid, dim3(256), 0, stream, tc, z, (const double*)part(2 * layer),
+                           (const double*)part(2 * layer + 1), gamma, beta, act, means + (size_t)layer * H,
+                           rstds + (size_t)layer * H, rm, rv);
+        launched();
+    };
+    auto bn_backward = [&](int layer, bool head, const float* z, const float* act, float* d, const float* gamma, float* dgamma,
+                           float* dbeta) {
+        if (err != hipSuccess) return;
+        TrainColArgs a;
+        memset(&a, 0, sizeof a);
+        a.z = z;
+        a.act = act;
+        a.d = d;
+        a.dout = dOut;
+        a.w_p1 = p.p1_w;
+        a.w_p2 = p.p2_w;
+        a.w_v = p.value_w;
+        a.mu = means + (size_t)layer * H;
+        a.rstd = rstds + (size_t)layer * H;
+        a.part0 = part(4);
+        a.part1 = part(5);
+        if (head) hipLaunchKernelGGL(k_train_colsum<TC_DHEAD>, cgrid, dim3(256), 0, stream, tc, a);
+        else hipLaunchKernelGGL(k_train_colsum<TC_DTRUNK>, cgrid, dim3(256), 0, stream, tc, a);
+        hipLaunchKernelGGL(k_train_bn_bwd, cgrid, dim3(256), 0, stream, tc, z, d, (const double*)part(4), (const double*)part(5),
+                           a.mu, a.rstd, gamma, dgamma, dbeta);
+        launched();
+    };
+    // forward
+    gemm(X, D, 1, 1, p.trunk0_w, 1, D, 1, Z1, n, Hi, D, p.trunk0_b, 1, D, nullptr);
+    bn_forward(0, Z1, p.bn1_w, p.bn1_b, A1, run ? run->mean1 : nullptr, run ? run->var1 : nullptr);
+    gemm(A1, Hi, 1, 1, p.trunk4_w, 1, Hi, 1, Z2, n, Hi, Hi, p.trunk4_b, 1, Hi, nullptr);
+    bn_forward(1, Z2, p.bn2_w, p.bn2_b, A2, run ? run->mean2 : nullptr, run ? run->var2 : nullptr);
+    if (err == hipSuccess) {
+        TrainHeads t;
+        t.act = A2;
+        t.w_p1 = p.p1_w, t.b_p1 = p.p1_b, t.w_p2 = p.p2_w, t.b_p2 = p.p2_b, t.w_v = p.value_w, t.b_v = p.value_b;
+        t.t1 = ro.policy_p1, t.t2 = ro.policy_p2, t.y1 = ro.value_p1, t.y2 = ro.value_p2;
+        t.dout = dOut;
+        t.loss_part = (double*)(ws + o_lpart);
+        t.logits_p1 = out ? out->logits_p1 : nullptr;
+        t.logits_p2 = out ? out->logits_p2 : nullptr;
+        t.value_p1 = out ? out->value_p1 : nullptr;
+        t.value_p2 = out ? out->value_p2 : nullptr;
+        t.n = n;
+        t.H = Hi;
+        t.pw_n = pw / (float)n;
+        t.vw_n = vw / (float)n;
+        hipLaunchKernelGGL(k_train_heads, dim3(head_blocks), dim3(256), (size_t)12 * H * 4, stream, t);
+        hipLaunchKernelGGL(k_train_loss_sum, dim3(1), dim3(256), 0, stream, (const double*)(ws + o_lpart), (uint32_t)head_blocks,
+                           (uint32_t)n, pw, vw, F(o_loss), out ? out->losses : nullptr);
+        launched();
+    }
+    // backward
+    grad_w(dOut, 12, A2, Hi, g.p1_w, g.p1_b, 5, g.p2_w, g.p2_b, 5, g.value_w, g.value_b, 2);
+    bn_backward(1, true, Z2, A2, dZ2, p.bn2_w, g.bn2_w, g.bn2_b);
+    grad_w(dZ2, Hi, A1, Hi, g.trunk4_w, g.trunk4_b, Hi, nullptr, nullptr, 0, nullptr, nullptr, 0);
+    gemm(dZ2, Hi, 1, 1, p.trunk4_w, Hi, 1, 0, dZ1, n, Hi, Hi, nullptr, 1, Hi, nullptr);
+    bn_backward(0, false, Z1, A1, dZ1, p.bn1_w, g.bn1_w, g.bn1_b);
+    grad_w(dZ1, Hi, X, D, g.trunk0_w, g.trunk0_b, Hi, nullptr, nullptr, 0, nullptr, nullptr, 0);
+    if (err == hipSuccess) {
+        err = hipEventRecord(R.ev_batch, stream);
+        R.has_batch = true;
+    }
+    if (before != R.device) (void)hipSetDevice(before);
+    HIP_TRY(err);
+    return AR_OK;
 }
 
 // ar_rows_validate: the request in chunks of `chunk` rows -- requests from the stored records (k_val_requests), the
@@ -4627,6 +4861,16 @@ int ar_rows_build_device(ArRowSet* s, uint64_t first, uint64_t n, const ArTrainR
     static const ArTrainRows none = {};
     return s->impl->nw == 1 ? rows_build_device<1>(*s->impl, first, n, out ? *out : none, (hipStream_t)stream)
                             : rows_build_device<4>(*s->impl, first, n, out ? *out : none, (hipStream_t)stream);
+}
+
+int ar_rows_grad_mlp(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArMlpTensors* params,
+                     const ArMlpTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
+                     const ArTrainOut* out, void* stream) {
+    if (!s || !s->impl || !params || !grads) return fail(AR_E_INVALID, "null argument");
+    return s->impl->nw == 1 ? rows_grad_mlp<1>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight, value_weight,
+                                               out, (hipStream_t)stream)
+                            : rows_grad_mlp<4>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight, value_weight,
+                                               out, (hipStream_t)stream);
 }
 
 int ar_rows_clear(ArRowSet* s) {

@@ -24,6 +24,7 @@ from typing import Iterator
 import numpy as np
 
 from .shards import KEYS, RowSet, row_shapes
+from .train import MLPGradStep  # noqa: F401  (exported beside RowDataset)
 
 
 def epoch_plan(n: int, seed: int, epoch: int, shuffle: bool = True, augment: bool = True,
@@ -134,3 +135,22 @@ class RowDataset:
                    for k in KEYS}
             rs.build_into(first, n, out)
             yield out
+
+    def grad_iter(self, step: MLPGradStep, batch_size: int, *, epoch: int = 0, seed: int = 0, augment: bool = True,
+                  p_swap: float = 0.5, shuffle: bool = True, drop_last: bool = True) -> Iterator[tuple]:
+        """One epoch as training steps: the plan, the order and the order-token rule of ``epoch_iter``, but instead of
+        materialising a batch, ``step.step(rowset, first, n)`` leaves the batch's gradients in the model's ``.grad`` and
+        ``(n, losses)`` is yielded -- ``losses`` the ``(6,)`` device tensor of ``MLPGradStep.step``. The trainer's loop body
+        is ``optimizer.step()``. Nothing is synchronised. A trailing batch of one row is skipped even without
+        ``drop_last``: a training BatchNorm over one row has no variance, and torch refuses it too."""
+        windows = batch_windows(len(self), batch_size, drop_last)
+        order, mask = epoch_plan(len(self), seed, epoch, shuffle, augment, p_swap)
+        rs = self.rowset
+        rs.set_order(self._positions[order], mask[order])
+        token = rs._order_token = object()
+        for first, n in windows:
+            if n < 2:
+                continue
+            if rs._order_token is not token:
+                raise RuntimeError("another epoch over this row set began before this one ended")
+            yield n, step.step(rs, first, n)

@@ -128,6 +128,55 @@ def check_out_tensors(out: dict, n: int, width: int, height: int, device) -> Non
             raise ValueError(f"{k} is on {t.device}, the row set on {device}")
 
 
+# PyRatMLP's state_dict keys (alpharat/nn/models/mlp.py), in the order of ArMlpTensors (_lib.MLP_TENSORS)
+MLP_PARAM_KEYS = ("trunk.0.weight", "trunk.0.bias", "trunk.1.weight", "trunk.1.bias", "trunk.4.weight", "trunk.4.bias",
+                  "trunk.5.weight", "trunk.5.bias", "policy_p1_head.weight", "policy_p1_head.bias", "policy_p2_head.weight",
+                  "policy_p2_head.bias", "value_head.weight", "value_head.bias")
+MLP_RUNNING_KEYS = ("trunk.1.running_mean", "trunk.1.running_var", "trunk.5.running_mean", "trunk.5.running_var")
+TRAIN_OUT_KEYS = ("losses", "logits_p1", "logits_p2", "value_p1", "value_p2")
+
+
+def mlp_param_shapes(width: int, height: int, hidden_dim: int) -> dict:
+    """The shape of every tensor of ``MLP_PARAM_KEYS`` and ``MLP_RUNNING_KEYS``."""
+    D, H = width * height * 7 + 6, hidden_dim
+    shapes = {"trunk.0.weight": (H, D), "trunk.4.weight": (H, H), "policy_p1_head.weight": (5, H), "policy_p1_head.bias": (5,),
+              "policy_p2_head.weight": (5, H), "policy_p2_head.bias": (5,), "value_head.weight": (2, H), "value_head.bias": (2,)}
+    for k in MLP_PARAM_KEYS + MLP_RUNNING_KEYS:
+        shapes.setdefault(k, (H,))
+    return shapes
+
+
+def check_grad_tensors(params: dict, grads: dict, running, out, n: int, width: int, height: int, hidden_dim: int, device) -> None:
+    """``RowSet.grad_mlp_into``'s conditions on its tensors (``ValueError``), in the manner of ``check_out_tensors``; no
+    device and no library is needed."""
+    import torch
+
+    shapes = mlp_param_shapes(width, height, hidden_dim)
+    out_shapes = dict(losses=(6,), logits_p1=(n, 5), logits_p2=(n, 5), value_p1=(n,), value_p2=(n,))
+    groups = [("params", params, MLP_PARAM_KEYS, shapes, True), ("grads", grads, MLP_PARAM_KEYS, shapes, True)]
+    if running is not None:
+        groups.append(("running", running, MLP_RUNNING_KEYS, shapes, True))
+    if out is not None:
+        groups.append(("out", out, TRAIN_OUT_KEYS, out_shapes, False))
+    for what, d, keys, want, required in groups:
+        for k in keys:
+            t = d.get(k)
+            if t is None:
+                if required:
+                    raise ValueError(f"{what} has no {k!r}")
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what}[{k!r}] is not a torch tensor")
+            if t.dtype != torch.float32:
+                raise ValueError(f"{what}[{k!r}] has dtype {t.dtype}, not torch.float32")
+            if not t.is_contiguous():
+                raise ValueError(f"{what}[{k!r}] is not contiguous")
+            if tuple(t.shape) != tuple(want[k]):
+                raise ValueError(f"{what}[{k!r}] has shape {tuple(t.shape)}, not {tuple(want[k])}")
+            if t.device != device:
+                raise ValueError(f"{what}[{k!r}] is on {t.device}, the row set on {device}")
+
+
 class RowSet:
     """ctypes mirror of ``ArRowSet`` (include/alpharat_hip.h): finished games kept on the device until their training rows
     are built. ``capacity_positions`` is fixed here and allocated once; an append that does not fit raises ``MemoryError``
@@ -216,6 +265,34 @@ class RowSet:
             stream = torch.cuda.current_stream(self.device_index)
         ptrs = _lib.ArTrainRows(*[out[k].data_ptr() for k in KEYS])
         _lib.check(_lib.load().ar_rows_build_device(handle, first, n, C.byref(ptrs), C.c_void_p(stream.cuda_stream)))
+
+    def grad_mlp_into(self, first: int, n: int, hidden_dim: int, params: dict, grads: dict, running, policy_weight: float,
+                      value_weight: float, out, stream=None) -> None:
+        """The loss and the gradients of PyRatMLP in training mode over rows ``first .. first + n`` of the order
+        (``ar_rows_grad_mlp``), on ``stream`` (``None``: torch's current stream of the set's device). Only launches.
+        ``params`` and ``grads``: the fourteen tensors under ``MLP_PARAM_KEYS``; ``grads`` is overwritten. ``running``:
+        the four ``MLP_RUNNING_KEYS``, updated in place, or ``None``. ``out``: any of ``TRAIN_OUT_KEYS`` (losses ``(6,)``,
+        logits ``(n, 5)``, values ``(n,)``), or ``None``. Every tensor is on the set's device, float32, contiguous and of
+        the shape ``(width, height, hidden_dim)`` give, else ``ValueError`` before the library is touched."""
+        import torch
+
+        first, n, hidden_dim = int(first), int(n), int(hidden_dim)
+        if first < 0 or n < 0 or hidden_dim <= 0:
+            raise ValueError("first and n must not be negative, hidden_dim positive")
+        check_grad_tensors(params, grads, running, out, n, self.width, self.height, hidden_dim,
+                           torch.device("cuda", self.device_index))
+        handle = self._handle()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device_index)
+        p = _lib.ArMlpTensors(*[params[k].data_ptr() for k in MLP_PARAM_KEYS])
+        g = _lib.ArMlpTensors(*[grads[k].data_ptr() for k in MLP_PARAM_KEYS])
+        r = _lib.ArMlpBnStats(*[running[k].data_ptr() for k in MLP_RUNNING_KEYS]) if running is not None else None
+        o = (_lib.ArTrainOut(*[out[k].data_ptr() if out.get(k) is not None else None for k in TRAIN_OUT_KEYS])
+             if out is not None else None)
+        _lib.check(_lib.load().ar_rows_grad_mlp(handle, first, n, hidden_dim, C.byref(p), C.byref(g),
+                                                C.byref(r) if r is not None else None, float(policy_weight),
+                                                float(value_weight), C.byref(o) if o is not None else None,
+                                                C.c_void_p(stream.cuda_stream)))
 
     def validate(self, net, rows, chunk_rows: int = 0, return_rows: bool = False):
         """``net`` over the stored positions ``rows``: the sums of the reference's validation pass

@@ -1,0 +1,95 @@
+"""The training step of PyRatMLP over a device-resident ``RowSet``: forward, losses and gradients in one call.
+
+The reference's loop (alpharat/nn/training/loop.py) gathers a batch, runs ``model(obs)`` in training mode,
+``compute_mlp_losses`` and ``loss.backward()``. ``MLPGradStep.step`` does the three for rows ``first .. first + n`` of the
+set's order with ``ar_rows_grad_mlp`` (alpharat_amd/csrc/train_mlp.h): the rows are built from the stored records, and the
+gradients land in tensors this object owns, which it hands to the parameters as their ``.grad``. The optimiser, its
+schedule and the checkpoints stay the trainer's::
+
+    step = MLPGradStep(model, policy_weight=1.0, value_weight=1.0)
+    for n, losses in train_dataset.grad_iter(step, 4096, epoch=epoch, seed=seed):
+        optimizer.step()
+
+Supported: PyRatMLP (``architecture: mlp``) in float32 with ``dropout`` 0.0 -- the architecture's default -- and a hidden
+width that is a multiple of 32, at most 256. LocalValueMLP is refused: its loss has a third term (the ownership head).
+AMP, dropout and the other architectures are not built.
+
+``trunk.0.bias`` and ``trunk.4.bias`` sit in front of a BatchNorm, so their true gradient is zero and what any
+implementation writes there is rounding noise.
+
+torch ships its own copy of the HIP runtime and a process brings up only one: import torch before anything loads
+``libalpharat_hip.so``.
+"""
+from __future__ import annotations
+
+from .shards import MLP_PARAM_KEYS, MLP_RUNNING_KEYS, RowSet
+
+_PREFIX = "_orig_mod."  # torch.compile's wrapper, stripped as weights.py does
+
+
+class MLPGradStep:
+    """``model``: an ``nn.Module`` whose ``state_dict()`` has PyRatMLP's keys (an ``_orig_mod.`` prefix is stripped).
+    ``ValueError`` for a ``Dropout`` with ``p != 0``, an ``ownership_head``, a missing key, or a parameter or BatchNorm
+    buffer that is not float32 or not contiguous. One persistent gradient tensor per parameter is allocated here."""
+
+    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0) -> None:
+        import torch
+
+        self.model = model
+        self.policy_weight, self.value_weight = float(policy_weight), float(value_weight)
+        for m in model.modules():
+            if isinstance(m, torch.nn.Dropout) and m.p != 0:
+                raise ValueError(f"dropout {m.p} is not supported: the step is built for PyRatMLP's default dropout 0.0")
+        named = {k.removeprefix(_PREFIX): v for k, v in model.named_parameters()}
+        buffers = {k.removeprefix(_PREFIX): v for k, v in model.named_buffers()}
+        if any(k.startswith("ownership_head.") for k in list(named) + list(buffers)):
+            raise ValueError("the model has an ownership_head (LocalValueMLP): its loss has a third term that this step "
+                             "does not compute")
+        missing = [k for k in MLP_PARAM_KEYS if k not in named] + [
+            k for k in MLP_RUNNING_KEYS + ("trunk.1.num_batches_tracked", "trunk.5.num_batches_tracked") if k not in buffers]
+        if missing:
+            raise ValueError(f"the model is not a PyRatMLP: its state_dict lacks {', '.join(missing)}")
+        self.params = {k: named[k] for k in MLP_PARAM_KEYS}
+        self.running = {k: buffers[k] for k in MLP_RUNNING_KEYS}
+        self._tracked = (buffers["trunk.1.num_batches_tracked"], buffers["trunk.5.num_batches_tracked"])
+        for k, t in {**self.params, **self.running}.items():
+            if t.dtype != torch.float32:
+                raise ValueError(f"{k} has dtype {t.dtype}: the step is float32 throughout")
+            if not t.is_contiguous():
+                raise ValueError(f"{k} is not contiguous")
+        w0 = self.params["trunk.0.weight"]
+        if w0.dim() != 2:
+            raise ValueError(f"trunk.0.weight has shape {tuple(w0.shape)}")
+        self.hidden_dim, self.obs_dim = int(w0.shape[0]), int(w0.shape[1])
+        self.grads = {k: torch.zeros_like(p) for k, p in self.params.items()}
+
+    def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
+        """Loss and gradients of rows ``first .. first + n`` of ``rowset``'s order, launched on torch's current stream;
+        nothing is synchronised. Every parameter's ``.grad`` is (again) this object's buffer, overwritten -- so
+        ``zero_grad(set_to_none=True)`` between steps is harmless and gradient accumulation is not what this does. With
+        ``model.training`` the running statistics are updated in place and both ``num_batches_tracked`` grow by one.
+        Returns the ``(6,)`` tensor loss_p1, loss_p2, loss_value_p1, loss_value_p2, loss_value, loss; with ``outputs``
+        ``(losses, logits_p1 (n, 5), logits_p2 (n, 5), value_p1 (n,), value_p2 (n,))``, the training-mode outputs."""
+        import torch
+
+        if rowset.width * rowset.height * 7 + 6 != self.obs_dim:
+            raise ValueError(f"the model reads {self.obs_dim} inputs, a {rowset.width}x{rowset.height} row has "
+                             f"{rowset.width * rowset.height * 7 + 6}")
+        device = torch.device("cuda", rowset.device_index)
+        n = int(n)
+        out = dict(losses=torch.empty(6, device=device, dtype=torch.float32))
+        if outputs:
+            out.update(logits_p1=torch.empty((n, 5), device=device), logits_p2=torch.empty((n, 5), device=device),
+                       value_p1=torch.empty(n, device=device), value_p2=torch.empty(n, device=device))
+        training = bool(self.model.training)
+        params = {k: p.data for k, p in self.params.items()}
+        rowset.grad_mlp_into(first, n, self.hidden_dim, params, self.grads, self.running if training else None,
+                             self.policy_weight, self.value_weight, out)
+        for k, p in self.params.items():
+            p.grad = self.grads[k]
+        if training:
+            for t in self._tracked:
+                t.add_(1)
+        if outputs:
+            return out["losses"], out["logits_p1"], out["logits_p2"], out["value_p1"], out["value_p2"]
+        return out["losses"]

@@ -473,6 +473,48 @@ int ar_rows_validate_lv(ArRowSet* set, ArNet* net, const uint64_t* rows, uint64_
                         uint32_t loss_batch_rows, ArValSums* sums, ArOwnSums* own, const ArValRows* rows_out,
                         const ArOwnRows* own_out);
 
+/* ---- training gradients of PyRatMLP over stored rows (nn/models/mlp.py in training mode, the loss of
+ * architectures/mlp/loss.py, loss.backward()) -----------------------------------------------------------------------------
+ * The loss and the gradients of one batch -- rows first .. first + n of the order, with their swap flags, exactly the
+ * rows ar_rows_build_device writes -- computed on the device in f32 and written into the caller's tensors. The
+ * optimiser, the schedule and the checkpoints stay the caller's. Dropout is not applied (the architecture's default 0).
+ * BatchNorm (both layers), over the batch: mu = mean(z), var = mean((z - mu)^2) (two passes), xhat = (z - mu) *
+ * rsqrt(var + 1e-5), y = gamma * xhat + beta, then ReLU. Running statistics, when given: rm = 0.9 rm + 0.1 mu,
+ * rv = 0.9 rv + 0.1 var * n / (n - 1). Heads: l1, l2 the policy logits, v = softplus(o) of the value head (v = o above 20).
+ *   loss_pX       = mean(-sum_k t_k log_softmax(l)_k)       loss_value_pX = mean((v - y)^2)
+ *   loss_value    = 0.5 (loss_value_p1 + loss_value_p2)     loss = policy_weight (loss_p1 + loss_p2) + value_weight loss_value
+ * trunk0_b and trunk4_b sit in front of a BatchNorm, so their true gradient is zero: what is written is the column sum of
+ * the layer's dz, rounding noise, as torch writes it. Sums over the batch use fixed partitions combined in a fixed order,
+ * without atomics: the same request gives the same bytes. */
+typedef struct ArMlpTensors { /* device pointers, f32, C order: PyRatMLP's state_dict tensors */
+    float *trunk0_w, *trunk0_b;       /* [H][D], [H]      D = h*w*7 + 6 */
+    float *bn1_w, *bn1_b;             /* [H]  trunk.1     */
+    float *trunk4_w, *trunk4_b;       /* [H][H], [H]      */
+    float *bn2_w, *bn2_b;             /* [H]  trunk.5     */
+    float *p1_w, *p1_b, *p2_w, *p2_b; /* [5][H], [5]      */
+    float *value_w, *value_b;         /* [2][H], [2]      */
+} ArMlpTensors;
+typedef struct ArMlpBnStats { /* running statistics [H], updated in place */
+    float *mean1, *var1, *mean2, *var2;
+} ArMlpBnStats;
+typedef struct ArTrainOut { /* device memory of the caller's, any may be NULL */
+    float* losses;                /* [6] loss_p1, loss_p2, loss_value_p1, loss_value_p2, loss_value, loss (batch means) */
+    float *logits_p1, *logits_p2; /* [n][5] the training-mode outputs */
+    float *value_p1, *value_p2;   /* [n] */
+} ArTrainOut;
+/* `grads` has the tensors of `params` and is overwritten, not accumulated into. running == NULL: no running statistic is
+ * updated; out == NULL: nothing but the gradients is written. Launched on `stream` (a hipStream_t; NULL: the null stream)
+ * with no synchronisation and no host copy; it allocates only when the set's training workspace must grow (the first
+ * call, or a larger n or hidden_dim; about 30 MB at n = 4096, D = 349, H = 256). ar_rows_order_set, ar_rows_clear and
+ * ar_rows_close wait for a pending step as they wait for pending batches. AR_E_INVALID before any launch, nothing
+ * written: a null set, params or grads; no order set, or first + n beyond it; n < 2 (a training BatchNorm over one row
+ * has no variance) or n > 65536; hidden_dim not a multiple of 32 or above 256; a null tensor in params, grads or
+ * running; any given pointer that is not device memory of the set's device (hipPointerGetAttributes) or not 4-byte
+ * aligned. */
+int ar_rows_grad_mlp(ArRowSet* set, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArMlpTensors* params,
+                     const ArMlpTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
+                     const ArTrainOut* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
