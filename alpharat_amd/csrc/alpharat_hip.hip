@@ -1679,12 +1679,19 @@ SearchCfg to_cfg(const ArSearchConfig& c, uint32_t sims, uint32_t batch) {
     return s;
 }
 
+// The most node counts a budget table holds (16 MiB of device memory): check_cfg refuses wider scaling ranges when the
+// power is not 1.
+enum { COLL_TABLE_MAX = 1 << 22 };
+
 int check_cfg(const SearchCfg& c) {
     if (c.n_sims == 0) return fail(AR_E_INVALID, "simulations must be > 0");
     static_assert(MAX_BATCH_SIZE == 4096, "the message below states the limit");
     if (c.batch_size == 0 || c.batch_size > MAX_BATCH_SIZE) return fail(AR_E_INVALID, "batch_size must be in 1..4096");
     if (c.coll_max > 65536) return fail(AR_E_INVALID, "collision_limit_max must be <= 65536");
     if (c.coll_min > c.coll_max) return fail(AR_E_INVALID, "collision_limit_min must be <= collision_limit_max");
+    static_assert(COLL_TABLE_MAX == 4194304, "the message below states the limit");
+    if (coll_table_size(c) >= (uint32_t)COLL_TABLE_MAX)
+        return fail(AR_E_INVALID, "collision_scaling_power != 1 needs collision_scaling_end - collision_scaling_start <= 4194304");
     if (c.noise_epsilon > 0.0f && !(c.noise_concentration / 5.0f > 1.0f))
         return fail(AR_E_INVALID, "noise_concentration must exceed 5 (Gamma shape >= 1 path only)");
     return AR_OK;
@@ -1790,6 +1797,21 @@ struct DevBuf {
         if (p) hipFree(p);
     }
 };
+// The collision budgets of a configuration whose power is not 1, computed here with the host's powf (the one the
+// reference's budgets come from) and kept on the current device for collisions_left to look up: c.coll_table points into
+// `buf`, which must live as long as kernels run with `c`. A power of 1 needs no table and leaves c.coll_table null.
+static int make_coll_table(SearchCfg& c, DevBuf<uint32_t>& buf) {
+    c.coll_table = nullptr;
+    const uint32_t n = coll_table_size(c);
+    if (n == 0) return AR_OK;
+    std::vector<uint32_t> host(n);
+    for (uint32_t k = 0; k < n; ++k) host[k] = collisions_left(c.coll_start + 1 + k, c);  // (the host's)
+    HIP_TRY(buf.alloc(n));
+    HIP_TRY(hipMemcpy(buf.p, host.data(), 4 * (size_t)n, hipMemcpyHostToDevice));
+    c.coll_table = buf.p;
+    return AR_OK;
+}
+
 template <typename T>
 struct PinBuf {
     T* p = nullptr;
@@ -1889,6 +1911,60 @@ __global__ void __launch_bounds__(ADV_THREADS) k_dbg_advance(NodeStats* recs, No
     if (threadIdx.x == 0) counts[blockIdx.x] = cnt;
 }
 
+// the ziggurat tables every engine copies to its device (zig.p); ar_debug_draws copies the same object
+static const ZigTables g_host_zig = {AR_ZIG_NORM_X_INIT, AR_ZIG_NORM_F_INIT};
+
+// ar_debug_budgets / ar_debug_draws: the scalar routines of dev_search.h and dev_rng.h by themselves, one thread per item,
+// so that what the device's math library and code generation return can be compared with the host's, call by call
+__global__ void k_dbg_budgets(const uint32_t* node_counts, uint32_t n, SearchCfg cfg, uint32_t* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = collisions_left(node_counts[i], cfg);
+}
+
+enum { DBG_DRAW_U64 = 0, DBG_DRAW_BELOW = 1, DBG_DRAW_WEIGHTED5 = 2, DBG_DRAW_NORMAL = 3, DBG_DRAW_GAMMA = 4, DBG_DRAW_DIRICHLET = 5, DBG_DRAW_KINDS = 6 };
+// kind; draws per stream; n: the range of rng_below, the outcome count of dirichlet_mix; w: the weights of rng_weighted5,
+// the prior every dirichlet_mix starts from; shape: of rng_gamma; epsilon, concentration: of dirichlet_mix
+struct DbgDraw {
+    uint32_t kind, count, n;
+    float w[5];
+    double shape;
+    float epsilon, concentration;
+};
+static size_t dbg_draw_bytes(uint32_t kind) { return kind == DBG_DRAW_BELOW || kind == DBG_DRAW_WEIGHTED5 ? 4 : kind == DBG_DRAW_DIRICHLET ? 20 : 8; }
+// stream s: rng_seed(seeds[s]), then d.count draws; draw i of stream s is item s * d.count + i of `out` (u64: rng_u64 and
+// the bits of the f64 draws; u32: rng_below, rng_weighted5 with -1 as 0xFFFFFFFF; five f32: the mixed prior); states:
+// the four words of the stream after its last draw
+__global__ void k_dbg_draws(const uint64_t* seeds, uint32_t n_streams, DbgDraw d, const ZigTables* zt, void* out, uint64_t* states) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_streams) return;
+    Rng r;
+    rng_seed(r, seeds[s]);
+    const size_t first = (size_t)s * d.count;
+    for (uint32_t i = 0; i < d.count; ++i) {
+        const size_t at = first + i;
+        if (d.kind == DBG_DRAW_U64) {
+            ((uint64_t*)out)[at] = rng_u64(r);
+        } else if (d.kind == DBG_DRAW_BELOW) {
+            ((uint32_t*)out)[at] = rng_below(r, d.n);
+        } else if (d.kind == DBG_DRAW_WEIGHTED5) {
+            ((uint32_t*)out)[at] = (uint32_t)rng_weighted5(r, d.w);
+        } else if (d.kind == DBG_DRAW_NORMAL) {
+            ((double*)out)[at] = rng_normal(r, zt);
+        } else if (d.kind == DBG_DRAW_GAMMA) {
+            ((double*)out)[at] = rng_gamma(r, d.shape, zt);
+        } else {
+            float prior[5];
+            for (int k = 0; k < 5; ++k) prior[k] = d.w[k];
+            dirichlet_mix(prior, d.n, d.epsilon, d.concentration, r, zt);
+            for (int k = 0; k < 5; ++k) ((float*)out)[at * 5 + k] = prior[k];
+        }
+    }
+    states[4 * (size_t)s + 0] = r.a;
+    states[4 * (size_t)s + 1] = r.b;
+    states[4 * (size_t)s + 2] = r.c;
+    states[4 * (size_t)s + 3] = r.d;
+}
+
 #if defined(AR_STATS)
 static void* g_dbg_slots;
 static uint32_t g_dbg_S, g_dbg_nw;
@@ -1918,6 +1994,7 @@ struct Engine {
     ArenaHold arena;
     DevBuf<uint8_t> maze;
     DevBuf<ZigTables> zig;
+    DevBuf<uint32_t> coll_table;  // cfg.coll_table
     DevBuf<uint32_t> counts, done_list, stall_list, release_list;
     DevBuf<StallInfo> stall_info;
     DevBuf<GameInit<NW>> init;
@@ -2075,6 +2152,7 @@ struct Engine {
         cfg = c;
         max_turns = mt;
         HIP_TRY(hipSetDevice(dev));
+        if (int rc = make_coll_table(cfg, coll_table)) return rc;
         HIP_TRY(hipStreamCreate(&stream));
         HIP_TRY(hipEventCreate(&ev0));
         HIP_TRY(hipEventCreate(&ev1));
@@ -2154,8 +2232,7 @@ struct Engine {
         HIP_TRY(maze.alloc(maze_bytes.size()));
         HIP_TRY(hipMemcpyAsync(maze.p, maze_bytes.data(), maze_bytes.size(), hipMemcpyHostToDevice, stream));
         HIP_TRY(zig.alloc(1));
-        static const ZigTables host_zig = {AR_ZIG_NORM_X_INIT, AR_ZIG_NORM_F_INIT};
-        HIP_TRY(hipMemcpyAsync(zig.p, &host_zig, sizeof host_zig, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(zig.p, &g_host_zig, sizeof g_host_zig, hipMemcpyHostToDevice, stream));
         HIP_TRY(counts.alloc(8));
         HIP_TRY(release_list.alloc(S));
         HIP_TRY(h_release.alloc(S));
@@ -4631,6 +4708,55 @@ int ar_debug_advance(const void* records, uint64_t n_records, const uint32_t* fi
     HIP_TRY(hipMemcpy(in_place_out, a.p, bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(moved_out, b.p, bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(counts_out, cnt.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    return AR_OK;
+}
+
+// Test entries (not in the public header): the device's scalar arithmetic, item by item.
+// ar_debug_budgets: out[i] = collisions_left(node_counts[i], cfg) as the gathers compute it at the start of a batch.
+int ar_debug_budgets(const ArSearchConfig* cfg, const uint32_t* node_counts, uint32_t n, uint32_t* out) {
+    if (!cfg || !node_counts || !out || n == 0) return fail(AR_E_INVALID, "ar_debug_budgets: null argument");
+    SearchCfg sc = to_cfg(*cfg, 1, 1);
+    if (int rc = check_cfg(sc)) return rc;
+    DevBuf<uint32_t> in, res, table;
+    if (int rc = make_coll_table(sc, table)) return rc;  // as Engine::setup does
+    HIP_TRY(in.alloc(n));
+    HIP_TRY(res.alloc(n));
+    HIP_TRY(hipMemcpy(in.p, node_counts, 4 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_dbg_budgets, dim3((n + 255) / 256), dim3(256), 0, 0, in.p, n, sc, res.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, res.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    return AR_OK;
+}
+
+// ar_debug_draws: `n_streams` random streams, stream s seeded with seeds[s], each making draw->count draws of one kind
+// (DbgDraw and k_dbg_draws above say which, with what parameters and in what format). out: n_streams * count items;
+// states_out: four words per stream, the generator after the stream's last draw.
+int ar_debug_draws(const uint64_t* seeds, uint32_t n_streams, const DbgDraw* draw, void* out, uint64_t* states_out) {
+    if (!seeds || !draw || !out || !states_out || n_streams == 0) return fail(AR_E_INVALID, "ar_debug_draws: null argument");
+    const DbgDraw d = *draw;
+    if (d.kind >= DBG_DRAW_KINDS || d.count == 0 || (uint64_t)n_streams * d.count > (1ull << 26))
+        return fail(AR_E_INVALID, "ar_debug_draws: unknown kind, no draws or more than 2^26 of them");
+    if (d.kind == DBG_DRAW_BELOW && d.n == 0) return fail(AR_E_INVALID, "ar_debug_draws: rng_below needs n >= 1");
+    if (d.kind == DBG_DRAW_GAMMA && !(d.shape >= 1.0 && d.shape <= 1e300))
+        return fail(AR_E_INVALID, "ar_debug_draws: rng_gamma needs a finite shape >= 1");
+    if (d.kind == DBG_DRAW_DIRICHLET && (d.n > 5 || !(d.concentration <= 3e38f)))
+        return fail(AR_E_INVALID, "ar_debug_draws: dirichlet_mix needs n <= 5 and a finite concentration");
+    const size_t bytes = (size_t)n_streams * d.count * dbg_draw_bytes(d.kind);
+    DevBuf<uint64_t> sd, st;
+    DevBuf<unsigned char> res;
+    DevBuf<ZigTables> zig;
+    HIP_TRY(sd.alloc(n_streams));
+    HIP_TRY(st.alloc(4 * (size_t)n_streams));
+    HIP_TRY(res.alloc(bytes));
+    HIP_TRY(zig.alloc(1));
+    HIP_TRY(hipMemcpy(sd.p, seeds, 8 * (size_t)n_streams, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(zig.p, &g_host_zig, sizeof g_host_zig, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_dbg_draws, dim3((n_streams + 63) / 64), dim3(64), 0, 0, sd.p, n_streams, d, zig.p, (void*)res.p, st.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, res.p, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(states_out, st.p, 32 * (size_t)n_streams, hipMemcpyDeviceToHost));
     return AR_OK;
 }
 

@@ -70,6 +70,9 @@ struct SearchCfg {
     float coll_power;
     uint32_t n_sims, batch_size;
     uint32_t alloc_per_round;  // scheduling only: allocation-loop steps one gather round runs (gather_round)
+    // device memory: collisions_left as the host computes it, for every node count the power applies to (coll_table_size
+    // entries); null where coll_power is 1 and on the host
+    const uint32_t* coll_table = nullptr;
 };
 
 enum { SLOT_EMPTY = 0, SLOT_ACTIVE = 1, SLOT_DONE = 2, SLOT_STALL = 3, SLOT_FAILED = 4, SLOT_ADVANCE = 5 };
@@ -296,13 +299,27 @@ AR_HD void make_root(Slot<NW>& s, const Mem<NW>& m) {
     s.node_count = 1;
 }
 
-// search.rs:437-450
+// node counts coll_start + 1 .. coll_end - 1 are the ones the power applies to: entry k of SearchCfg::coll_table is the
+// budget at coll_start + 1 + k
+AR_HD uint32_t coll_table_size(const SearchCfg& c) {
+    return c.coll_power != 1.0f && c.coll_end > c.coll_start ? c.coll_end - c.coll_start - 1 : 0u;
+}
+
+// search.rs:437-450. The reference's budgets are those of a host libm's powf, and the device's powf returns another f32
+// for some ratios (measured: 27 of the 50001 budgets of min 1, max 65536, start 0, end 50000, power 0.5 came out one off).
+// So only the host evaluates the power; the device reads what the host computed (coll_table, which every configuration
+// with a power other than 1 carries: make_coll_table) and has no pow in its code at all.
 AR_HD uint32_t collisions_left(uint32_t node_count, const SearchCfg& c) {
     if (node_count >= c.coll_end) return c.coll_max;
     if (node_count <= c.coll_start) return c.coll_min;
     const float ratio = (float)(node_count - c.coll_start) / (float)(c.coll_end - c.coll_start);
-    // (x^1 = x in every libm; spelled out because the device's pow is a long routine that every game would run)
-    const float scaled = (float)c.coll_min + ((float)c.coll_max - (float)c.coll_min) * (c.coll_power == 1.0f ? ratio : powf(ratio, c.coll_power));
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (c.coll_power != 1.0f) return c.coll_table[node_count - c.coll_start - 1];
+    const float pw = ratio;
+#else
+    const float pw = c.coll_power == 1.0f ? ratio : powf(ratio, c.coll_power);  // (x^1 = x in every libm)
+#endif
+    const float scaled = (float)c.coll_min + ((float)c.coll_max - (float)c.coll_min) * pw;
     const float r = roundf(scaled);
     uint32_t v = r <= 0.0f ? 0u : (r >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)r);
     if (v < c.coll_min) v = c.coll_min;

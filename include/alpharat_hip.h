@@ -40,7 +40,8 @@ typedef struct ArSearchConfig {
     uint32_t collision_limit_max;     /* 256   */
     uint32_t collision_scaling_start; /* 800   */
     uint32_t collision_scaling_end;   /* 50000 */
-    float collision_scaling_power;    /* 1.0   */
+    float collision_scaling_power;    /* 1.0; another power: the host tabulates the budgets, and
+                                         collision_scaling_end - collision_scaling_start may be at most 4194304 */
 } ArSearchConfig;
 
 /* A full PyRat position: what `rust_mcts_search(game: PyRat, ...)` clones out of the engine

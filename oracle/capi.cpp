@@ -377,6 +377,48 @@ double or_rng_normal(uint64_t state[4]) {
     return v;
 }
 
+// Many draws in one call: `n_streams` streams, stream s = SmallRng::seed_from_u64(seeds[s]) followed by d->count draws of
+// one kind. kind 0 next_u64 (u64), 1 gen_range_u32(n) (u32), 2 weighted_index5_sample(w) (i32), 3 StandardNormal (f64),
+// 4 Gamma(shape, 1) (f64), 5 apply_dirichlet_noise(epsilon, concentration) on a half node of n outcomes whose prior is
+// w before every call (five f32: the prior after it). Draw i of stream s is item s * count + i of `out`; states_out gets
+// the four words of each stream after its last draw; visits (optional, kind 3): [tail entries, wedge tests] over all draws.
+struct OrDraw {
+    uint32_t kind, count, n;
+    float w[5];
+    double shape;
+    float epsilon, concentration;
+};
+int or_rng_fill(const uint64_t* seeds, uint32_t n_streams, const OrDraw* d, void* out, uint64_t* states_out, uint64_t visits[2]) {
+    if (d->kind > 5 || (d->kind == 1 && d->n == 0) || (d->kind == 4 && !(d->shape >= 1.0)) || (d->kind == 5 && d->n > 5)) return -1;
+    const GammaLarge gamma = GammaLarge::make(d->kind == 4 ? d->shape : 1.0, 1.0);
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        SmallRng r = SmallRng::seed_from_u64(seeds[s]);
+        const size_t first = (size_t)s * d->count;
+        for (uint32_t i = 0; i < d->count; ++i) {
+            const size_t at = first + i;
+            if (d->kind == 0) {
+                ((uint64_t*)out)[at] = r.next_u64();
+            } else if (d->kind == 1) {
+                ((uint32_t*)out)[at] = r.gen_range_u32(d->n);
+            } else if (d->kind == 2) {
+                ((int32_t*)out)[at] = weighted_index5_sample(d->w, r);
+            } else if (d->kind == 3) {
+                ((double*)out)[at] = sample_standard_normal(r, visits);
+            } else if (d->kind == 4) {
+                ((double*)out)[at] = gamma.sample(r);
+            } else {
+                HalfNode h;
+                h.n_outcomes = (uint8_t)d->n;
+                std::memcpy(h.prior, d->w, 20);
+                if (!apply_dirichlet_noise(h, d->epsilon, d->concentration, r)) return -1;
+                std::memcpy((float*)out + at * 5, h.prior, 20);
+            }
+        }
+        std::memcpy(states_out + 4 * (size_t)s, r.s, 32);
+    }
+    return 0;
+}
+
 // run_search on a persistent tree. rng_state in/out.
 int or_search(void* tree, const void* game, const OrSearchConfig* cfg, uint32_t n_sims, uint32_t batch,
               uint64_t rng_state[4], int backend_kind, float v1, float v2, const void* net, OrSearchResult* out,

@@ -144,8 +144,9 @@ inline int weighted_index5_sample(const float w[5], SmallRng& rng) {
     return idx;
 }
 
-// rand_distr 0.4.3 StandardNormal (f64) by the ziggurat method.
-inline double sample_standard_normal(SmallRng& rng) {
+// rand_distr 0.4.3 StandardNormal (f64) by the ziggurat method. `visits` (optional, for tests that must know what their
+// seeds exercise): [0] counts the draws that enter the tail, [1] the wedge tests.
+inline double sample_standard_normal(SmallRng& rng, uint64_t* visits = nullptr) {
     for (;;) {
         uint64_t bits = rng.next_u64();
         unsigned i = (unsigned)(bits & 0xff);
@@ -157,6 +158,7 @@ inline double sample_standard_normal(SmallRng& rng) {
         double test_x = std::fabs(x);
         if (test_x < ZIG_NORM_X[i + 1]) return x;
         if (i == 0) {
+            if (visits) ++visits[0];
             double xx = 1.0, yy = 0.0;
             while (-2.0 * yy < xx * xx) {
                 double x_ = rng.gen_open01_f64();
@@ -166,6 +168,7 @@ inline double sample_standard_normal(SmallRng& rng) {
             }
             return u < 0.0 ? xx - AR_ZIG_NORM_R : AR_ZIG_NORM_R - xx;
         }
+        if (visits) ++visits[1];
         if (ZIG_NORM_F[i + 1] + (ZIG_NORM_F[i] - ZIG_NORM_F[i + 1]) * rng.gen_f64() < std::exp(-x * x / 2.0))
             return x;
     }

@@ -652,7 +652,29 @@ static void test_selfplay() {
     for (int i = 0; i < 20; ++i) CHECK(sample_action(one, rng) == 2);
 }
 
+// Known answers for the generator itself, from outside this repository.
+static void test_rng_known_answers() {
+    // the xoshiro256++ authors' reference implementation (xoshiro256plusplus.c) from state {1, 2, 3, 4}; the same vector
+    // is the `reference` test of the rand_xoshiro crate
+    SmallRng r;
+    for (int i = 0; i < 4; ++i) r.s[i] = (uint64_t)i + 1;
+    const uint64_t want[10] = {41943041ULL, 58720359ULL, 3588806011781223ULL, 3591011842654386ULL, 9228616714210784205ULL,
+                               9973669472204895162ULL, 14011001112246962877ULL, 12406186145184390807ULL,
+                               15849039046786891736ULL, 10450023813501588000ULL};
+    for (int i = 0; i < 10; ++i) CHECK(r.next_u64() == want[i]);
+    // an all-zero seed is replaced by SplitMix64 from 0, whose first four outputs are published with the algorithm
+    const uint8_t zero[32] = {0};
+    SmallRng z = SmallRng::from_seed(zero);
+    CHECK(z.s[0] == 0xe220a8397b1dcdafULL && z.s[1] == 0x6e789e6aa1b965f4ULL && z.s[2] == 0x06c45d188009454fULL &&
+          z.s[3] == 0xf88bb8a8724c81ecULL);
+    CHECK(z.next_u64() == 5987356902031041503ULL);  // rand_xoshiro: Xoshiro256PlusPlus::seed_from_u64(0), first output
+    // seed_from_u64 never lands there for the seeds in use: PCG32 words, not zeros
+    SmallRng s = SmallRng::seed_from_u64(0);
+    CHECK((s.s[0] | s.s[1] | s.s[2] | s.s[3]) != 0 && s.s[0] != z.s[0]);
+}
+
 int main() {
+    test_rng_known_answers();
     test_node();
     test_tree();
     test_search_units();

@@ -47,6 +47,27 @@ class OrSearchResult(C.Structure):
     ]
 
 
+class OrDraw(C.Structure):
+    """What every stream of rng_fill draws (oracle/capi.cpp or_rng_fill; the product's test entry takes the same record)."""
+    _fields_ = [("kind", C.c_uint32), ("count", C.c_uint32), ("n", C.c_uint32), ("w", C.c_float * 5), ("shape", C.c_double),
+                ("epsilon", C.c_float), ("concentration", C.c_float)]
+
+
+DRAW_U64, DRAW_BELOW, DRAW_WEIGHTED5, DRAW_NORMAL, DRAW_GAMMA, DRAW_DIRICHLET = range(6)
+DRAW_DTYPE = {DRAW_U64: np.uint64, DRAW_BELOW: np.uint32, DRAW_WEIGHTED5: np.int32, DRAW_NORMAL: np.float64,
+              DRAW_GAMMA: np.float64, DRAW_DIRICHLET: np.float32}
+
+
+def make_draw(kind, count, n=0, w=(0, 0, 0, 0, 0), shape=1.0, epsilon=0.0, concentration=0.0) -> OrDraw:
+    return OrDraw(kind, count, n, (C.c_float * 5)(*w), shape, epsilon, concentration)
+
+
+def draw_buffers(n_streams, d: OrDraw):
+    """(draws[n_streams, count(, 5)], states[n_streams, 4]) for one fill of `d`"""
+    shape = (n_streams, d.count, 5) if d.kind == DRAW_DIRICHLET else (n_streams, d.count)
+    return np.zeros(shape, dtype=DRAW_DTYPE[d.kind]), np.zeros((n_streams, 4), dtype=np.uint64)
+
+
 def make_config(**kw) -> OrSearchConfig:
     d = dict(
         c_puct=1.5,
@@ -116,6 +137,7 @@ def lib() -> C.CDLL:
         "or_rng_weighted5": (i32, [vp, vp]),
         "or_rng_gamma": (C.c_double, [vp, C.c_double]),
         "or_rng_normal": (C.c_double, [vp]),
+        "or_rng_fill": (i32, [vp, u32, C.POINTER(OrDraw), vp, vp, vp]),
         "or_search": (
             i32,
             [vp, vp, C.POINTER(OrSearchConfig), u32, u32, vp, i32, C.c_float, C.c_float, vp, C.POINTER(OrSearchResult), vp],
@@ -248,6 +270,17 @@ class Rng:
 
     def normal(self):
         return lib().or_rng_normal(_ptr(self.s))
+
+
+def rng_fill(seeds, d: OrDraw):
+    """Stream s: seed_from_u64(seeds[s]), then d.count draws of d.kind. Returns (draws, states after the last draw,
+    (normal draws that entered the tail, wedge tests))."""
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+    out, states = draw_buffers(len(seeds), d)
+    visits = np.zeros(2, dtype=np.uint64)
+    if lib().or_rng_fill(_ptr(seeds), len(seeds), C.byref(d), _ptr(out), _ptr(states), _ptr(visits)) != 0:
+        raise ValueError("or_rng_fill: parameters outside what the oracle restates")
+    return out, states, (int(visits[0]), int(visits[1]))
 
 
 class Net:

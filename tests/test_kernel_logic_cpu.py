@@ -241,6 +241,47 @@ def test_collisions_left_matches_the_oracle_everywhere(power):
         assert want[start] == lo and want[min(end, 60000)] == hi
 
 
+# ---- search constants away from the default, tuned and strong sets ---------------------------------------------------
+# The CPU twin of test_gpu_offnominal.py: the same 24 sets (tests/_constant_sets.py), the same games (the first two of
+# the device run on each board), through the lane gather with SmartUniform and with the stand-in network, and through the
+# work-queue gather. A set that fails here fails in the logic; one that fails only on the device fails in what the device
+# computes differently from this host.
+def test_constant_sets_cover_the_grid():
+    import _constant_sets as K
+
+    assert len(K.SETS) == len(set(K.SETS)) == 24
+    for col, values in enumerate((K.C_PUCT, K.FPU, K.FORCE_K)):
+        assert {s[col] for s in K.SETS} == set(values)
+    assert {s[3:] for s in K.SETS} == set(K.NOISE)
+    for corner in (K.LOW, K.HIGH):
+        assert {s[3:] for s in K.SETS if s[:3] == corner} == set(K.NOISE)
+
+
+def _constant_set_params():
+    import _constant_sets as K
+
+    return [pytest.param(s, id=i) for s, i in zip(K.SETS, K.IDS)]
+
+
+@pytest.mark.parametrize("s", _constant_set_params())
+def test_constant_sets_whole_games(s):
+    import _constant_sets as K
+
+    cfg = O.make_config(**K.kwargs(s))
+    seen_mud = False
+    for board in ("open", "maze"):
+        for i in range(2):
+            g = K.game(board, i)
+            seen_mud |= bool((g.maze() >= 2).any())
+            seed = K.rng_seed(i)
+            _same_game(O.play_game(g, cfg, K.SIMS, K.BATCH, seed), H.run(g, K.TURNS, cfg, K.SIMS, K.BATCH, seed, eval_mode=0))
+            want = O.play_game(g, cfg, K.SIMS, K.BATCH, seed, backend=4, net=O.CallbackBackend(H.hashed_eval(K.W)))
+            assert want["total_nn_evals"] > 0
+            for mode in (6, 8):
+                _same_game(want, H.run(g, K.TURNS, cfg, K.SIMS, K.BATCH, seed, eval_mode=mode))
+    assert seen_mud
+
+
 # ---- batch sizes above 16 (check_cfg accepts 1..4096) ---------------------------------------------------------------
 # The batch size sets how many entries a batch holds (ProcEntry[batch]), how many leaves go to the evaluator at once and
 # how far an entry's evaluation index runs: an entry packs kind | evaluation index | order key into one word
