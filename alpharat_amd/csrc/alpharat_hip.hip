@@ -713,14 +713,15 @@ __global__ void __launch_bounds__(64) k_backup(Slot<NW>* slots, uint32_t n_slots
     slots[i] = s;
 }
 
-// The backup with sixteen lanes per game (dev_backup16.h): ceil(n / 4) blocks of 64 threads, dynamic LDS = 64 paths
-// of `path_cap` steps. Ends with batch_end; a search that is complete is left in the state (ACTIVE, no batch,
+// The backup with sixteen lanes per game (dev_backup16.h): ceil(n / 4) blocks of 64 threads, dynamic LDS = the notes of
+// 64 paths (BACKUP16_LDS_BYTES; `path_cap` = levels a path may have); four wavefronts per SIMD (128 registers) match the
+// sixteen blocks a CU's LDS takes. Ends with batch_end; a search that is complete is left in the state (ACTIVE, no batch,
 // remaining == 0) for k_finish.
 template <int NW>
-__global__ void __launch_bounds__(64) k_backup16(Slot<NW>* slots, uint32_t n_slots, SearchCfg cfg, Bases B,
+__global__ void __launch_bounds__(64, 4) k_backup16(Slot<NW>* slots, uint32_t n_slots, SearchCfg cfg, Bases B,
                                                  const ZigTables* zt, const EvalOut* ev_queue, uint32_t first,
                                                  uint32_t path_cap) {
-    extern __shared__ PathStep lds_path[];
+    extern __shared__ uint32_t lds_path[];
     const uint32_t w = threadIdx.x & 15u;
     const uint32_t i = first + blockIdx.x * 4u + (threadIdx.x >> 4);
     bool active = i < n_slots && slots[i].status == SLOT_ACTIVE && slots[i].batch_active != 0;
@@ -730,7 +731,7 @@ __global__ void __launch_bounds__(64) k_backup16(Slot<NW>* slots, uint32_t n_slo
     active = active && backup16_wants(S, m, cfg);
     const EvalOut* ev = ev_queue ? ev_queue + S.eval_base : m.ev_local;
     (void)zt;
-    backup16<NW>(active, S, m, cfg, ev, lds_path + (size_t)threadIdx.x * PATH_LDS_STEPS, path_cap, w);
+    backup16<NW>(active, S, m, cfg, ev, lds_path, path_cap, w);
     if (active && w == 0) batch_end(S);
 }
 // the end of a move (selfplay.rs:538-565 up to the tree reuse) for the games whose search k_backup16 completed
@@ -2160,8 +2161,10 @@ struct Engine {
         L = make_layout<NW>(cfg, max_turns);
         static_assert(sizeof(LevelO<NW>) <= (16 + 112 + sizeof(State<NW>) + 15) / 16 * 16, "slot_layout.h sizes the level stack");
         // which backup kernel (results are identical): AR_BACKUP=lane | group; the group kernel keeps 64 paths in LDS
-        // (the deep part of its paths lives in the level-stack scratch: 16 lanes x path_cap steps must fit there)
-        backup16 = (size_t)16 * (L.max_depth + 2) * sizeof(PathStep) <= (size_t)L.max_depth * (16 + 112 + sizeof(State<NW>));
+        // (the deep part of its paths lives in the level-stack scratch, which make_layout sizes for it too)
+        backup16 = true;
+        if (backup16_deep_bytes(L.max_depth) > L.ev_off - L.levels_off)
+            return fail(AR_E_BACKEND, "slot layout: the level stack is smaller than k_backup16's path notes");
         if (const char* e = getenv("AR_BACKUP")) backup16 = backup16 && std::string(e) != "lane";
         gather = choose_gather(need_queue);
         if (gather == GatherKernel::Wide) {
@@ -2432,7 +2435,7 @@ struct Engine {
         }
         if (backup16) {
             const uint32_t path_cap = L.max_depth + 2;
-            hipLaunchKernelGGL(k_backup16<NW>, dim3((n + 3) / 4), dim3(64), (size_t)64 * PATH_LDS_STEPS * sizeof(PathStep),
+            hipLaunchKernelGGL(k_backup16<NW>, dim3((n + 3) / 4), dim3(64), (size_t)BACKUP16_LDS_BYTES,
                                g.stream, slots.p, g.end, cfg, bases(), zig.p, ev, g.first, path_cap);
             hipLaunchKernelGGL(k_finish<NW>, dim3(grid(n)), dim3(64), 0, g.stream, slots.p, g.end, cfg, bases(), g.first, phase);
             // (fresh roots that draw Dirichlet noise were left alone above; k_finish ignores a slot with a batch pending)

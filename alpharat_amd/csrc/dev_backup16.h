@@ -1,41 +1,316 @@
 // The backup (search.rs:1027-1066: populate / finalize the gathered leaves, walk the values up, cancel the
-// collisions) with SIXTEEN LANES PER GAME: lane w of a group walks batch entry w, a wavefront holds four games.
+// collisions) with SIXTEEN LANES PER GAME: lane w of a group takes batch entry w, a wavefront holds four games.
 //
 // The lane-per-game backup (backup_round, dev_search.h) is one dependent memory trip per tree level per entry:
 // ~16 entries x ~10 levels = ~170 trips per batch in sequence, and nothing else to run meanwhile. Entries cannot
 // simply be walked at the same time: paths share their upper part, and a shared node's running means must take the
-// entries' values in batch order (f32 Welford updates do not commute). Here the walks overlap as far as that order
-// allows:
-//   1. every lane follows the parent links of its own entry from the leaf to the root and notes the path in LDS
-//      (node, which outcome pair of it leads down) -- reads only, all entries at once: depth trips instead of 16 x depth;
-//   2. the updates then run as a pipeline: lane w starts late enough that it reaches every depth strictly after lane
-//      w - 1 did (end round E_w = max(E_{w-1} + 1, D_w), D = path length), so two entries never meet at a node in the same
-//      round and always arrive in batch order; a round is: load the node's header and the two edges, apply
-//      finalize_score_update / update_multivisit exactly as backup_round does, store, workgroup-scope fence (the four
-//      games of a block share one wavefront: its L1 is coherent for it);
-//      the leaf itself is level 0 of the path (populate_node + first finalize), so a terminal node that was claimed
-//      twice in one batch is also served in order;
+// entries' values in batch order (f32 Welford updates do not commute). But the value an entry delivers to a node does
+// not depend on any node's statistics: it is q = r + q', q' what the entry delivered one level below and r the static
+// edge reward of the node below (NodeH1::r1/r2); at the leaf it is the evaluator's output, or 0 for a terminal. So
+// every q of every (entry, level) is known once the path is, the nodes are independent of each other, and a node is
+// read once, given all its entries' updates in batch order in registers, and written once:
+//   1. every lane follows the parent links of its own entry from the leaf to the root and notes per level, in LDS,
+//      the step (node, which outcome pair of it leads down) and the pair (q1, q2) the entry delivers there -- reads
+//      only, all entries at once: depth trips. Level 0 is the leaf (populate_node + first finalize), so a terminal
+//      node that was claimed twice in one batch is served in order like any shared node;
+//   2. a node belongs to the lowest lane whose path has it. Two paths that share a node have it at the same depth
+//      from the root and share everything above it, so a lane's own nodes are the levels of its path below the longest
+//      prefix it shares with a lower lane (bk16_claim: LDS reads only). The own levels of lane 0, 1, ... in turn are
+//      the list of the game's distinct nodes; item t of it is served by lane t % 16 -- the shared upper part of the
+//      paths, which all belongs to lane 0, is spread over the group, and a lane has two or three items, not a whole
+//      path. Serving a node: find the entries that have it (sixteen LDS reads at its depth), load the header and the
+//      edges, apply finalize_score_update / update_multivisit of every such entry in entry order, exactly as
+//      backup_round does, store what changed. There is no fence inside the phase;
 //   3. collisions only subtract integers from in-flight counters: lanes take them 16 at a time and walk up with atomic
 //      subtractions, after the updates are done.
-// Same arithmetic, same order per node as backup_round: trees are bit-identical. End-of-batch bookkeeping (batch_end)
+// Levels are numbered from the leaf, so of a path longer than PATH_LDS_STEPS it is the root side that lives in scratch:
+// the lanes' scans at those depths are global loads (cached: sixteen lanes read the same few words). Searches with the
+// shipped constants stay near ten levels; tests/test_gpu_backup_merge.py has paths of forty.
+// A path longer than path_cap (never met: the cap is beyond the turn limit) flags the game with error 6 and drops that
+// entry alone; the other entries and later chunks are served (the pipeline this replaces stopped the lane for good).
+// Same arithmetic, same order per node as backup_round: trees are bit-identical. 1 and 2 are host-callable per lane
+// (bk16_walk, bk16_claim, bk16_apply: lanes meet only through the notes), and tests/hostsim_backup runs them on the CPU with the
+// lanes in ascending and in descending order against the entry-by-entry walk. End-of-batch bookkeeping (batch_end)
 // is done by lane 0; the end of a move (extraction, sampling, record, step: finish_move) is left to k_finish.
 #pragma once
 #include "dev_search.h"
 
-#if defined(__HIPCC__)
 namespace ar {
 
 // one step of a path: node id (26 bits) | outcome pair of THIS node that leads to the level below (p1 3 bits, p2 3 bits)
 typedef uint32_t PathStep;
-enum { PATH_LDS_STEPS = 20 };  // steps kept in LDS per lane; deeper ones go to the game's (idle) level-stack scratch
-__device__ inline PathStep path_pack(uint32_t node, uint32_t o1, uint32_t o2) { return node | (o1 << 26) | (o2 << 29); }
+// levels kept in LDS per lane; deeper ones go to the game's (idle) level-stack scratch. Twelve levels are 9.5 KB a
+// wavefront: sixteen wavefronts a CU, which the 128 registers of the kernel allow too (twenty would be ten)
+enum { PATH_LDS_STEPS = 12 };
+enum { PATH_NODE_MASK = 0x3FFFFFF, PATH_LANES = 16 };
+AR_HD PathStep path_pack(uint32_t node, uint32_t o1, uint32_t o2) { return node | (o1 << 26) | (o2 << 29); }
+
+// a level beyond PATH_LDS_STEPS, in scratch
+struct PathNote {
+    PathStep step;
+    float q1, q2;
+};
+// bytes of level-stack scratch the deep levels of a game's sixteen paths take (path_cap = max_depth + 2 levels each)
+AR_HD size_t backup16_deep_bytes(uint32_t max_depth) {
+    const uint32_t cap = max_depth + 2;
+    return cap > PATH_LDS_STEPS ? (size_t)PATH_LANES * (cap - PATH_LDS_STEPS) * sizeof(PathNote) : 0;
+}
+
+// what a lane says about its entry: path length (0: no entry) | the leaf is evaluated << 18 | where the evaluator put
+// its outputs << 19
+enum { HEAD_LEN_BITS = 18 };
+AR_HD uint32_t head_pack(uint32_t len, uint32_t entry_word) {
+    return len | (proc_kind(entry_word) == PROC_EVAL ? (1u << HEAD_LEN_BITS) | (proc_eval_index(entry_word) << (HEAD_LEN_BITS + 1)) : 0u);
+}
+AR_HD uint32_t head_len(uint32_t h) { return h & ((1u << HEAD_LEN_BITS) - 1u); }
+AR_HD bool head_is_eval(uint32_t h) { return (h >> HEAD_LEN_BITS) & 1u; }
+AR_HD uint32_t head_eval_index(uint32_t h) { return h >> (HEAD_LEN_BITS + 1); }
+static_assert(HEAD_LEN_BITS + 1 + PROC_INDEX_BITS <= 32, "a head word is length | evaluated | evaluation index");
+
+// The notes of one game's sixteen paths. Level l of lane j is step[l * stride + j] (likewise q1, q2) below
+// PATH_LDS_STEPS and deep[j * deep_cap + l - PATH_LDS_STEPS] from there on; level 0 is the leaf.
+struct PathNotes {
+    PathStep* step;
+    float* q1;
+    float* q2;
+    uint32_t* head;  // [16]
+    uint32_t* cut;   // [16] first level (from the root) no lower lane has: bk16_claim
+    PathNote* deep;
+    uint32_t stride, deep_cap;
+};
+AR_HD PathStep note_step(const PathNotes& P, uint32_t j, uint32_t l) {
+    return l < PATH_LDS_STEPS ? P.step[l * P.stride + j] : P.deep[(size_t)j * P.deep_cap + (l - PATH_LDS_STEPS)].step;
+}
+AR_HD void note_get(const PathNotes& P, uint32_t j, uint32_t l, PathStep& s, float& q1, float& q2) {
+    if (l < PATH_LDS_STEPS) {
+        s = P.step[l * P.stride + j];
+        q1 = P.q1[l * P.stride + j];
+        q2 = P.q2[l * P.stride + j];
+    } else {
+        const PathNote n = P.deep[(size_t)j * P.deep_cap + (l - PATH_LDS_STEPS)];
+        s = n.step;
+        q1 = n.q1;
+        q2 = n.q2;
+    }
+}
+AR_HD void note_put(const PathNotes& P, uint32_t j, uint32_t l, PathStep s, float q1, float q2) {
+    if (l < PATH_LDS_STEPS) {
+        P.step[l * P.stride + j] = s;
+        P.q1[l * P.stride + j] = q1;
+        P.q2[l * P.stride + j] = q2;
+    } else {
+        PathNote n;
+        n.step = s;
+        n.q1 = q1;
+        n.q2 = q2;
+        P.deep[(size_t)j * P.deep_cap + (l - PATH_LDS_STEPS)] = n;
+    }
+}
+
+// ---- 1. lane w notes the path of its entry (leaf `leaf`, entry word `entry_word`; `mine` = the lane has an entry).
+// Returns the error code (6: the path is longer than path_cap; the entry then takes no part in the backup).
+AR_HD uint32_t bk16_walk(const PathNotes& P, uint32_t w, bool mine, uint32_t leaf, uint32_t entry_word,
+                         const NodeStats* stats, const EvalOut* ev, uint32_t path_cap) {
+    uint32_t D = 0, err = 0;
+    if (mine) {
+        // what the leaf takes: the evaluator's values, or zeros (its read does not wait for the walk)
+        float q1 = 0.0f, q2 = 0.0f;
+        if (proc_kind(entry_word) == PROC_EVAL) {
+            const EvalOut& o = ev[proc_eval_index(entry_word)];
+            q1 = o.v1;
+            q2 = o.v2;
+        }
+        uint32_t cur = leaf, po = 0;
+        while (true) {
+            if (D >= path_cap) {
+                err = 6;
+                D = 0;
+                break;
+            }
+            const NodeH1 h = stats[cur].h1;
+            const uint32_t meta = stats[cur].h2.meta;
+            note_put(P, w, D, path_pack(cur, po & 7u, po >> 3), q1, q2);
+            D += 1;
+            // one level up (backup_round B_LEVEL): the edge rewards of the level below plus the value carried up
+            q1 = h.r1 + q1;
+            q2 = h.r2 + q2;
+            po = meta_po(meta, 0) | (meta_po(meta, 1) << 3);
+            cur = h.parent;
+            if (cur == NIL) break;
+        }
+    }
+    P.head[w] = head_pack(D, entry_word);
+    return err;
+}
+
+// ---- 2. a node in the registers of the lane that serves it
+struct OwnedNode {
+    uint32_t same;  // lanes whose path has the node (at the same depth from the root, all of them)
+    uint32_t node;
+    NodeH0 h0;
+    Edge e[2][5];  // loaded where an entry changes them (not for a node that is only a terminal leaf here)
+};
+// what populate_node needs of an evaluated leaf
+struct LeafEval {
+    uint32_t omap[2];
+    float p1[5], p2[5];
+};
+AR_HD LeafEval leaf_eval(const NodeStats& N, const EvalOut& o) {
+    LeafEval r;
+    const NodeH2 c = N.h2;
+    r.omap[0] = c.omap[0];
+    r.omap[1] = c.omap[1];
+    for (int i = 0; i < 5; ++i) {
+        r.p1[i] = o.p1[i];
+        r.p2[i] = o.p2[i];
+    }
+    return r;
+}
+
+// the three fields of edge `a` an update changes, as ORs over masked elements (sel5u, dev_search.h)
+AR_HD Edge edge_pick(const Edge* e, uint32_t a) {
+    uint32_t q = 0, v = 0, n = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 5; ++i) {
+        q |= (a == i) ? f32_to_bits(e[i].q) : 0u;
+        v |= (a == i) ? e[i].visits : 0u;
+        n |= (a == i) ? e[i].nif : 0u;
+    }
+    Edge r;
+    r.prior = 0.0f;
+    r.q = bits_to_f32(q);
+    r.visits = v;
+    r.nif = n;
+    return r;
+}
+AR_HD void edge_place(Edge* e, uint32_t a, const Edge& r) {
+#pragma unroll
+    for (uint32_t i = 0; i < 5; ++i) {
+        e[i].q = (a == i) ? r.q : e[i].q;
+        e[i].visits = (a == i) ? r.visits : e[i].visits;
+        e[i].nif = (a == i) ? r.nif : e[i].nif;
+    }
+}
+
+// The node gets the update of every entry that has it, in entry order, and is stored. Returns the number of updates.
+// `k` = the node's depth from the root, `le` = what lane `first_eval`'s evaluated leaf needs, if the node is one.
+AR_HD uint32_t bk16_settle(const PathNotes& P, uint32_t first_eval, uint32_t k, NodeStats* stats, const EvalOut* ev,
+                           const LeafEval& le0, OwnedNode& n) {
+    NodeStats& N = stats[n.node];
+    uint32_t nv = 0, dirty = 0;  // bit pl * 5 + i: edge record to store
+    for (uint32_t left = n.same; left; left &= left - 1u) {
+        const uint32_t j = (uint32_t)lowest_bit(left), hj = P.head[j], l = head_len(hj) - 1 - k;
+        PathStep ps;
+        float q1, q2;
+        note_get(P, j, l, ps, q1, q2);
+        if (l == 0) {
+            // the gathered leaf: populate_node (tree.rs:156-173) + first finalize (backup_round B_ENTRY)
+            if (head_is_eval(hj)) {
+                LeafEval le = le0;
+                if (j != first_eval) le = leaf_eval(N, ev[head_eval_index(hj)]);  // (an evaluated leaf has one entry: not met)
+                float red1[5], red2[5];
+                reduce_prior(le.omap[0], le.p1, red1);
+                reduce_prior(le.omap[1], le.p2, red2);
+                for (int i = 0; i < 5; ++i) {
+                    n.e[0][i].prior = red1[i];
+                    n.e[1][i].prior = red2[i];
+                }
+                dirty = 0x3FFu;
+            }
+            finalize_h0(n.h0, q1, q2, 1);
+        } else {
+            // one ancestor (backup_round B_LEVEL, search.rs:834-851)
+            const uint32_t a1 = (ps >> 26) & 7u, a2 = ps >> 29;
+            Edge e1 = edge_pick(n.e[0], a1), e2 = edge_pick(n.e[1], a2);
+            finalize_h0(n.h0, q1, q2, 1);
+            edge_update(e1, q1, 1);
+            edge_update(e2, q2, 1);
+            edge_place(n.e[0], a1, e1);
+            edge_place(n.e[1], a2, e2);
+            dirty |= (1u << a1) | (32u << a2);
+        }
+        nv += 1;
+    }
+    N.h0 = n.h0;
+    for (int pl = 0; pl < 2; ++pl)
+        for (int i = 0; i < 5; ++i)
+            if ((dirty >> (pl * 5 + i)) & 1u) N.e[pl][i] = n.e[pl][i];
+    return nv;
+}
+
+// ---- 2a. lane w finds the levels of its path that are its own: those no lower lane has. Two paths that share a node
+// share everything above it, so these are the depths from `cut` on, cut = the longest prefix shared with a lower lane.
+AR_HD void bk16_claim(const PathNotes& P, uint32_t w) {
+    const uint32_t D = head_len(P.head[w]);
+    uint32_t c = 0;
+    for (uint32_t j = 0; j < w && c < D;) {
+        const uint32_t Dj = head_len(P.head[j]);
+        if (Dj > c && ((note_step(P, j, Dj - 1 - c) ^ note_step(P, w, D - 1 - c)) & PATH_NODE_MASK) == 0)
+            c += 1;  // lane j has the node at depth c too
+        else
+            j += 1;
+    }
+    P.cut[w] = c;
+}
+
+// ---- 2b. The game's distinct nodes are lane 0's own levels, then lane 1's, ...: item t of that list is served by
+// lane t % 16, whoever's path it is on, so the long shared prefix of lane 0 is spread over the group. A lane takes its
+// items one after the other: who has the node (sixteen LDS reads), load, every entry's update in entry order, store.
+// Every lane's notes and cuts must be complete. Returns the number of (entry, level) updates the lane applied.
+AR_HD uint32_t bk16_apply(const PathNotes& P, uint32_t x, NodeStats* stats, const EvalOut* ev) {
+    uint32_t nv = 0;
+    for (uint32_t t = x;; t += PATH_LANES) {
+        // item t: level k (from the root) of lane w's path
+        uint32_t off = 0, w = PATH_LANES, k = 0, Dw = 0;
+#pragma unroll 4
+        for (uint32_t j = 0; j < PATH_LANES; ++j) {
+            const uint32_t Dj = head_len(P.head[j]), cj = P.cut[j];
+            if (w == PATH_LANES && t < off + (Dj - cj)) {
+                w = j;
+                k = cj + (t - off);
+                Dw = Dj;
+            }
+            off += Dj - cj;
+        }
+        if (w == PATH_LANES) break;
+        OwnedNode n;
+        n.node = note_step(P, w, Dw - 1 - k) & PATH_NODE_MASK;
+        uint32_t same = 0, terminal_leaves = 0, first_eval = PATH_LANES;
+#pragma unroll 4
+        for (uint32_t j = 0; j < PATH_LANES; ++j) {
+            const uint32_t hj = P.head[j], Dj = head_len(hj);
+            if (Dj > k && (note_step(P, j, Dj - 1 - k) & PATH_NODE_MASK) == n.node) {
+                same |= 1u << j;
+                if (Dj - 1 == k) {
+                    if (!head_is_eval(hj)) terminal_leaves |= 1u << j;
+                    else if (first_eval == PATH_LANES) first_eval = j;
+                }
+            }
+        }
+        n.same = same;
+        NodeStats& N = stats[n.node];
+        n.h0 = N.h0;
+        if (same != terminal_leaves)
+            for (int pl = 0; pl < 2; ++pl)
+                for (int i = 0; i < 5; ++i) n.e[pl][i] = N.e[pl][i];
+        LeafEval le = {};
+        if (first_eval != PATH_LANES) le = leaf_eval(N, ev[head_eval_index(P.head[first_eval])]);
+        nv += bk16_settle(P, first_eval, k, stats, ev, le, n);
+    }
+    return nv;
+}
+
+}  // namespace ar
+
+#if defined(__HIPCC__)
+namespace ar {
 
 __device__ inline uint32_t grp_pick(uint32_t v, uint32_t w) {  // value of group lane `w` (16 lanes per game)
     return (uint32_t)__shfl((int)v, (int)((threadIdx.x & 48u) | w), 64);
 }
+// LDS of a wavefront: step, q1, q2 [PATH_LDS_STEPS][64], one head word and one cut per lane
+enum { BACKUP16_LDS_BYTES = (3 * PATH_LDS_STEPS + 2) * 64 * 4 };
 
-// One game's batch. `path` = this lane's LDS path buffer [path_cap]; all 16 lanes of the group call this together
-// (idle groups call it with active = false and only take part in the wave-wide loops' votes).
 // A batch that evaluates the ROOT (a fresh tree's first batch: one entry) draws Dirichlet noise (search.rs:1036-1050,
 // the Gamma sampler is a hundred registers of code): such games are left to the lane-per-game kernel, which the host
 // launches behind this one for whatever still has a batch to back up.
@@ -46,27 +321,36 @@ __device__ inline bool backup16_wants(const Slot<NW>& S, const Mem<NW>& m, const
     return !(S.n_proc >= 1 && pe.node == S.root && proc_kind(pe.kind) == PROC_EVAL);
 }
 
+// One game's batch. `lds` = the wavefront's BACKUP16_LDS_BYTES; all 16 lanes of the group call this together (idle
+// groups call it with active = false and only take part in the wave-wide loops' votes and barriers).
 template <int NW>
 __device__ inline void backup16(bool active, Slot<NW>& S, const Mem<NW>& m, const SearchCfg& cfg, const EvalOut* ev,
-                                PathStep* lds_path, uint32_t path_cap, uint32_t w) {
+                                uint32_t* lds, uint32_t path_cap, uint32_t w) {
+    (void)cfg;
     const uint32_t n_proc = active ? S.n_proc : 0u, n_coll = active ? S.n_coll : 0u;
-    // steps beyond the LDS part: lane w's slice of the level-stack scratch (not in use between gather and gather)
-    PathStep* deep_path = (PathStep*)m.levels + (size_t)w * path_cap;
-    auto path_at = [&](uint32_t d) -> PathStep& { return d < PATH_LDS_STEPS ? lds_path[d] : deep_path[d - PATH_LDS_STEPS]; };
+    PathNotes P;
+    {
+        const uint32_t g0 = threadIdx.x & 48u;  // the game's first lane
+        P.step = lds + g0;
+        P.q1 = (float*)(lds + PATH_LDS_STEPS * 64 + g0);
+        P.q2 = (float*)(lds + 2 * PATH_LDS_STEPS * 64 + g0);
+        P.head = lds + 3 * PATH_LDS_STEPS * 64 + g0;
+        P.cut = lds + (3 * PATH_LDS_STEPS + 1) * 64 + g0;
+        P.deep = (PathNote*)m.levels;  // (not in use between gather and gather)
+        P.stride = 64;
+        P.deep_cap = path_cap > PATH_LDS_STEPS ? path_cap - PATH_LDS_STEPS : 0u;
+    }
     uint32_t err = 0;
     uint32_t nv = 0;  // node records updated (the lane kernel's nv_backup)
-    // eval index of entry e = number of EVAL entries before it: prefix over the proc list (kinds are read by all)
     for (uint32_t base = 0; __any(base < n_proc); base += 16) {
         const uint32_t e = base + w;
         const bool mine = e < n_proc;
-        // ---- 1. the path of entry e
-        uint32_t kind = PROC_TERMINAL, D = 0, leaf = NIL, ev_idx = 0;
+        ProcEntry pe;
+        pe.node = NIL;
+        pe.kind = proc_none();
         {
             // lane w takes the w-th entry in backup order: rank by key among the chunk's entries (a chunk of the
             // depth-first gathers' entries is in order already; the work-queue gather writes at most 16, in arrival order)
-            ProcEntry pe;
-            pe.node = NIL;
-            pe.kind = proc_none();
             if (mine) pe = m.proc[e];
             uint32_t rank = 0;
             for (uint32_t j = 0; j < 16; ++j) {
@@ -77,102 +361,17 @@ __device__ inline void backup16(bool active, Slot<NW>& S, const Mem<NW>& m, cons
             for (uint32_t j = 0; j < 16; ++j) src = grp_pick(rank, j) == w ? j : src;
             pe.node = grp_pick(pe.node, src);
             pe.kind = grp_pick(pe.kind, src);
-            if (mine) {  // (entries without a batch entry sort last: lanes >= n_proc - base get those)
-                kind = proc_kind(pe.kind);
-                leaf = pe.node;
-                ev_idx = proc_eval_index(pe.kind);  // where the evaluator put this leaf's outputs
-            }
+            // (entries without a batch entry sort last: lanes >= n_proc - base get those)
         }
-        {
-            uint32_t cur = leaf, po = 0;
-            bool walking = mine;
-            while (__any(walking)) {
-                if (walking) {
-                    if (D >= path_cap) {
-                        err = 6;
-                        walking = false;
-                    } else {
-                        const uint32_t parent = m.stats[cur].h1.parent;
-                        const uint32_t meta = m.stats[cur].h2.meta;
-                        path_at(D) = path_pack(cur, po & 7u, po >> 3);
-                        D += 1;
-                        po = meta_po(meta, 0) | (meta_po(meta, 1) << 3);
-                        cur = parent;
-                        if (cur == NIL) walking = false;
-                    }
-                }
-            }
-        }
-        // ---- 2. the schedule: E_w = max(E_{w-1} + 1, D_w) over the lanes that have an entry, in lane order
-        uint32_t E = 0, t0 = 0;
-        {
-            uint32_t prev = 0;
-            for (uint32_t j = 0; j < 16; ++j) {
-                const uint32_t Dj = grp_pick(D, j);
-                uint32_t Ej = prev;
-                if (Dj > 0) {
-                    Ej = prev + 1 > Dj ? prev + 1 : Dj;
-                    prev = Ej;
-                }
-                if (j == w) {
-                    E = Ej;
-                    t0 = Ej - Dj;
-                }
-            }
-            (void)E;
-        }
-        // ---- the pipeline: at round r lane w works on path[r - t0] while t0 <= r < t0 + D
-        float v1 = 0.0f, v2 = 0.0f, cr1 = 0.0f, cr2 = 0.0f;  // value carried up, edge rewards of the level below
-        for (uint32_t r = 0; __any(mine && r < t0 + D); ++r) {
-            if (mine && r >= t0 && r < t0 + D && err == 0) {
-                const uint32_t lvl = r - t0;
-                const PathStep ps = path_at(lvl);
-                NodeStats& N = m.stats[ps & 0x3FFFFFFu];
-                NodeH0 a = N.h0;
-                const NodeH1 h = N.h1;
-                if (lvl == 0) {
-                    // the gathered leaf: populate_node (tree.rs:156-173) + first finalize (backup_round B_ENTRY)
-                    float g1 = 0.0f, g2 = 0.0f;
-                    if (kind == PROC_EVAL) {
-                        const NodeH2 c = N.h2;
-                        const EvalOut o = ev[ev_idx];
-                        float red1[5], red2[5];
-                        reduce_prior(c.omap[0], o.p1, red1);
-                        reduce_prior(c.omap[1], o.p2, red2);
-                        for (int k = 0; k < 5; ++k) {
-                            N.e[0][k].prior = red1[k];
-                            N.e[1][k].prior = red2[k];
-                        }
-                        g1 = o.v1;
-                        g2 = o.v2;
-                    }
-                    finalize_h0(a, g1, g2, 1);
-                    N.h0 = a;
-                    v1 = g1;
-                    v2 = g2;
-                } else {
-                    // one ancestor (backup_round B_LEVEL, search.rs:834-851)
-                    const uint32_t a1 = (ps >> 26) & 7u, a2 = ps >> 29;
-                    Edge e1 = N.e[0][a1], e2 = N.e[1][a2];
-                    const float q1 = cr1 + v1, q2 = cr2 + v2;
-                    finalize_h0(a, q1, q2, 1);
-                    edge_update(e1, q1, 1);
-                    edge_update(e2, q2, 1);
-                    N.h0 = a;
-                    N.e[0][a1] = e1;
-                    N.e[1][a2] = e2;
-                    v1 = q1;
-                    v2 = q2;
-                }
-                cr1 = h.r1;
-                cr2 = h.r2;
-                nv += 1;
-            }
-            // the next round's lanes read what this round's lanes wrote (one wavefront, one L1: a workgroup-scope
-            // release / acquire is a wait for the stores, not a cache write-back)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        }
+        // ---- 1. the path of entry e, noted for all
+        err |= bk16_walk(P, w, mine, pe.node, pe.kind, m.stats, ev, path_cap);
+        __syncthreads();  // (one wavefront: a wait for the notes, those in scratch included)
+        // ---- 2. every node once: the lowest lane that has it lists it, the list is dealt round the group
+        bk16_claim(P, w);
+        __syncthreads();
+        nv += bk16_apply(P, w, m.stats, ev);
+        // a later chunk reads what this one stored, and phase 3's atomics hit words the stores wrote
+        __syncthreads();
     }
     // ---- 3. collisions (search.rs:860-889): integer subtractions, any order, atomics where paths meet
     for (uint32_t base = 0; __any(base < n_coll); base += 16) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <stddef.h>
 
+#include "dev_backup16.h"
 #include "dev_search.h"
 
 namespace ar {
@@ -30,7 +31,10 @@ inline SlotLayout make_layout(const SearchCfg& cfg, uint32_t max_turns) {
     const size_t level_bytes = sizeof(Level<NW>) > level_o ? sizeof(Level<NW>) : level_o;
     // (the work-queue gather, dev_gatherw.h, keeps up to sixteen spilled position records here instead: State + 16 bytes each)
     const size_t spill_bytes = 16 * align_up(sizeof(State<NW>) + 16, 8);
-    const size_t levels_total = level_bytes * L.max_depth > spill_bytes ? level_bytes * L.max_depth : spill_bytes;
+    size_t levels_total = level_bytes * L.max_depth > spill_bytes ? level_bytes * L.max_depth : spill_bytes;
+    // (between two gathers the sixteen-lane backup notes the deep levels of its paths here: more than the stack needs only
+    // above 60 levels)
+    if (levels_total < backup16_deep_bytes(L.max_depth)) levels_total = backup16_deep_bytes(L.max_depth);
     off = align_up(off + levels_total, 64);
     L.ev_off = off;
     off = align_up(off + sizeof(EvalOut) * cfg.batch_size, 64);
