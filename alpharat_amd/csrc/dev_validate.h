@@ -36,10 +36,12 @@ AR_HD void val_policy_terms(const float* l, const float* t, float& ce, float& en
         e[k] = expf(l[k] - m);
         s += e[k];
     }
-    const float lse = m + logf(s);
+    const float ls = logf(s);
     float c = 0.0f, hp = 0.0f, ht = 0.0f;
     for (int k = 0; k < 5; ++k) {
-        const float lp = l[k] - lse;  // log_softmax
+        // log_softmax as (l - max) - log(sum), the order torch takes: l - (max + log(sum)) rounds the sum at the size of the
+        // logits, which at |l| of 100 is 4e-6 on a term that is itself -log(sum), near 0 for the largest logit
+        const float lp = (l[k] - m) - ls;
         c += t[k] * lp;
         hp += (e[k] / s) * lp;
         const float tc = t[k] > 1e-8f ? t[k] : 1e-8f;

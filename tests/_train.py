@@ -78,6 +78,19 @@ def shape_case(board_name: str, H: int, n: int, seed: int) -> dict:
     return make_case(board_name, random_mlp(w, h, H, seed), order, swap)
 
 
+# the ``value`` family's head (tests/_saturated_nets.py) on its PyRatMLP: pre-softplus outputs on both sides of 20, above 89
+# and below -90, so the step's softplus and its derivative take the linear branch, the threshold and the underflowing one
+VALUE_BOARD, VALUE_NET, VALUE_ROWS, VALUE_SEED = "5x5 open", "mlp_5x5_h32", 33, 1
+
+
+def value_family_case() -> dict:
+    import _saturated_nets as S
+
+    _, plain = board(VALUE_BOARD)
+    order, swap = repeated_order(len(plain["value_p1"]), VALUE_ROWS, VALUE_SEED)
+    return make_case(VALUE_BOARD, S.family(VALUE_NET, "value"), order, swap)
+
+
 def window_cases() -> list:
     """the whole order's case (rows, swap, network) and one case per window"""
     whole = shape_case(WINDOW_BOARD, WINDOW_H, WINDOW_ROWS, WINDOW_SEED)

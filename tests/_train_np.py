@@ -81,7 +81,8 @@ def step(case: dict) -> dict:
     # backward
     dl1 = pw / n * (np.exp(ls1) * t1.sum(axis=1, keepdims=True) - t1)
     dl2 = pw / n * (np.exp(ls2) * t2.sum(axis=1, keepdims=True) - t2)
-    sig = np.where(o > 20.0, 1.0, 1.0 / (1.0 + np.exp(-o)))
+    with np.errstate(over="ignore"):  # exp(-o) is inf below -709, and the sigmoid there 0, as it should be
+        sig = np.where(o > 20.0, 1.0, 1.0 / (1.0 + np.exp(-o)))
     do = vw / n * (v - np.stack([v1t, v2t], axis=1)) * sig
     g = {}
     for name, d in (("policy_p1_head", dl1), ("policy_p2_head", dl2), ("value_head", do)):

@@ -28,7 +28,10 @@ SEED = 5
 
 RANDOM_NETS = ("random_mlp_h64", "random_mlp_h40", "random_symmetric_h64")  # k_mlp_mfma, k_mlp, k_symmetric_mfma2 / k_symmetric
 CASES = [(board, net) for net in RANDOM_NETS for board in BOARDS] + [
-    ("7x5", "nets/cnn_gpool_7x5_c16"), ("7x5", "nets_katago/katago_7x5_c32"), ("7x7", "nets/mlp_7x7_h256")]
+    ("7x5", "nets/cnn_gpool_7x5_c16"), ("7x5", "nets_katago/katago_7x5_c32"), ("7x7", "nets/mlp_7x7_h256"),
+    # logit spreads above 104 and pre-softplus values from -90 to 200 (tests/_saturated_nets.py): the cross-entropy has to
+    # come from the log-softmax, not from log(p) of a p that underflowed
+    ("5x5 open", "saturated_mlp_5x5_h32")]
 CASE_IDS = [f"{net.split('/')[-1]}-on-{board.replace(' ', '_')}" for board, net in CASES]
 
 
@@ -43,7 +46,15 @@ def network(name: str, w: int, h: int, tmp_dir=None):
     """(blob path or None without tmp_dir, forward(obs) -> dict of float64 logits_p1, logits_p2, value_p1, value_p2)"""
     from alpharat_amd.weights import read_blob, write_blob
 
-    if name.startswith("random_"):
+    if name.startswith("saturated_"):
+        import _saturated_nets as S
+
+        arch, bw, bh, _ = S.ARCHS[name[len("saturated_"):]]
+        assert (arch, bw, bh) == ("mlp", w, h), name
+        t = S.family(name[len("saturated_"):], "policy+value")
+        blob = write_blob(Path(tmp_dir) / f"{name}.arnet", arch, w, h, t) if tmp_dir is not None else None
+        fwd = lambda obs: _mlp_np.mlp_forward(t, obs)  # noqa: E731
+    elif name.startswith("random_"):
         kind, H = name[len("random_"):].split("_h")
         t = (random_mlp if kind == "mlp" else random_symmetric)(w, h, int(H), SEED)
         blob = write_blob(Path(tmp_dir) / f"{name}_{w}x{h}.arnet", kind, w, h, t) if tmp_dir is not None else None

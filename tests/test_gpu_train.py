@@ -105,6 +105,13 @@ def test_shapes(sets, shape):
     _check_case(sets(shape[0]), TR.shape_case(*shape), TR.SHAPE_IDS[TR.SHAPES.index(shape)])
 
 
+def test_value_family_head(sets):
+    """pre-softplus outputs within 0.5 of 20 on both sides, above 89 and below -90 (tests/test_train_np.py asserts that
+    of the float64 step): the softplus of dev_train.h and its derivative on every branch, under the measured bound"""
+    case = TR.value_family_case()
+    _check_case(sets(case["board"]), case, "value family")
+
+
 # ---- 3. windows of one order; swapped rows ----------------------------------------------------------------------------------
 def test_windows_of_one_order(sets):
     whole, windows = TR.window_cases()

@@ -65,6 +65,15 @@ def test_relu_guard_shapes(shape):
     assert N.relu_margin(TR.shape_case(*shape)) >= TR.MARGIN
 
 
+def test_relu_guard_value_family():
+    case = TR.value_family_case()
+    res = N.step(case)
+    assert N.relu_margin(case, res) >= TR.MARGIN
+    v = np.concatenate([res["value_p1"], res["value_p2"]])  # softplus(o) is o to 2e-9 from o = 20 on
+    assert ((v > 19.5) & (v < 20)).any() and ((v > 20) & (v < 20.5)).any()  # both sides of softplus's threshold
+    assert (v > 89).any() and (v < 1e-30).any() and ((v > 1e-3) & (v < 10)).any()
+
+
 def test_relu_guard_windows_and_swaps():
     _, windows = TR.window_cases()
     for (first, n), case in zip(TR.WINDOWS, windows):
