@@ -218,6 +218,19 @@ class ArTrainOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("losses", "logits_p1", "logits_p2", "value_p1", "value_p2")]
 
 
+SYM_TENSORS = ("se0_w", "se0_b", "se1_w", "se1_b", "pe0_w", "pe0_b", "pe1_w", "pe1_b", "trunk0_w", "trunk0_b", "bn1_w", "bn1_b",
+               "trunk4_w", "trunk4_b", "bn2_w", "bn2_b", "policy_w", "policy_b", "value_w", "value_b")
+
+
+class ArSymTensors(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in SYM_TENSORS]
+
+
+class ArSymBnStats(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("se_mean", "se_var", "pe_mean", "pe_var", "bn1_mean", "bn1_var", "bn2_mean",
+                                          "bn2_var")]
+
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -266,6 +279,9 @@ EXPORTS = {
     "ar_rows_grad_mlp": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArMlpTensors),
                                    C.POINTER(ArMlpTensors), C.POINTER(ArMlpBnStats), C.c_float, C.c_float,
                                    C.POINTER(ArTrainOut), C.c_void_p]),
+    "ar_rows_grad_symmetric": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArSymTensors),
+                                         C.POINTER(ArSymTensors), C.POINTER(ArSymBnStats), C.c_float, C.c_float,
+                                         C.POINTER(ArTrainOut), C.c_void_p]),
 }
 
 _lib = None

@@ -38,6 +38,7 @@
 #include "dev_rows.h"
 #include "dev_validate.h"
 #include "train_mlp.h"
+#include "train_sym.h"
 #include "host_games.h"
 #include "zig_norm_tables.inc"
 
@@ -3462,6 +3463,310 @@ int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const A
     return AR_OK;
 }
 
+// ar_rows_grad_symmetric: the loss and the gradients of SymmetricMLP over rows first .. first + n of the order (train_sym.h
+// lists the chain), under the rules of rows_grad_mlp: everything checked before the first launch, the set's one workspace
+// grown after waiting for what may still use the old one, ev_batch behind the last launch. P1's and P2's rows are stacked:
+// an array of [2n] rows holds P1's n, then P2's.
+static const char* const kSymTensorNames[20] = {"se0_w",    "se0_b",    "se1_w",  "se1_b",  "pe0_w",    "pe0_b",    "pe1_w",
+                                                "pe1_b",    "trunk0_w", "trunk0_b", "bn1_w", "bn1_b",    "trunk4_w", "trunk4_b",
+                                                "bn2_w",    "bn2_b",    "policy_w", "policy_b", "value_w", "value_b"};
+template <int NW>
+int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const ArSymTensors& p, const ArSymTensors& g,
+                        const ArSymBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream) {
+    if (!R.has_order) return fail(AR_E_INVALID, "the row set has no order: ar_rows_order_set comes first");
+    if (first > R.ord_n || n64 > R.ord_n - first)
+        return fail(AR_E_INVALID, "rows " + std::to_string(first) + " + " + std::to_string(n64) + " go beyond the order of " +
+                                      std::to_string(R.ord_n));
+    if (n64 < 2) return fail(AR_E_INVALID, "a training BatchNorm needs at least two rows");
+    if (n64 > (uint64_t)TRAIN_MAX_ROWS) return fail(AR_E_INVALID, "at most 65536 rows a step");
+    if (H == 0 || H % 32 != 0 || H > 256)
+        return fail(AR_E_INVALID, "hidden_dim must be a multiple of 32, at most 256 (got " + std::to_string(H) + ")");
+    static_assert(sizeof(ArSymTensors) == 20 * sizeof(float*), "twenty pointers");
+    static_assert(sizeof(ArSymBnStats) == 8 * sizeof(float*), "eight pointers");
+    float* const* pp = (float* const*)&p;
+    float* const* gp = (float* const*)&g;
+    for (int i = 0; i < 20; ++i) {
+        if (!pp[i] || !gp[i]) return fail(AR_E_INVALID, std::string("null tensor: ") + kSymTensorNames[i]);
+        if (int rc = rows_check_device_ptr(R, pp[i], 4, kSymTensorNames[i])) return rc;
+        if (int rc = rows_check_device_ptr(R, gp[i], 4, kSymTensorNames[i])) return rc;
+    }
+    if (run) {
+        float* const* rs = (float* const*)run;
+        for (int i = 0; i < 8; ++i) {
+            if (!rs[i]) return fail(AR_E_INVALID, "null running statistic");
+            if (int rc = rows_check_device_ptr(R, rs[i], 4, "running statistic")) return rc;
+        }
+    }
+    if (out) {
+        float* const os[5] = {out->losses, out->logits_p1, out->logits_p2, out->value_p1, out->value_p2};
+        for (float* q : os)
+            if (q)
+                if (int rc = rows_check_device_ptr(R, q, 4, "output")) return rc;
+    }
+    const int n = (int)n64, n2 = 2 * n, hw = (int)R.hw, D = (int)rows_obs_dim(R.hw), Hi = (int)H, H2 = 2 * Hi;
+    const int Ds = sym_shared_dim(hw), Dp = sym_player_dim(hw);
+    // fixed partitions: of a BatchNorm call's n rows for the column sums; of the n or 2n rows a product is reduced over
+    TrainCols tc;
+    tc.n = n;
+    tc.H = Hi;
+    tc.P = std::min<int>(TRAIN_MAX_PARTS, (n + 63) / 64);
+    tc.rpp = (n + tc.P - 1) / tc.P;
+    tc.P = (n + tc.rpp - 1) / tc.rpp;
+    struct Split { int S, kps; };
+    auto split_of = [](int rows) {
+        Split s;
+        s.S = std::min<int>(TRAIN_MAX_SPLITS, (rows + 255) / 256);
+        s.kps = ((rows + s.S - 1) / s.S + TG_KC - 1) / TG_KC * TG_KC;
+        s.S = (rows + s.kps - 1) / s.kps;
+        return s;
+    };
+    const Split sp1 = split_of(n), sp2 = split_of(n2);
+    const int head_blocks = (n + TRAIN_HEAD_ROWS - 1) / TRAIN_HEAD_ROWS;
+    // the workspace: offsets into one allocation, every array 256-byte aligned
+    size_t total = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t nH = (size_t)n * H * 4;
+    const size_t o_x = take((size_t)n * D * 4), o_t1 = take((size_t)n * 20), o_t2 = take((size_t)n * 20), o_y1 = take((size_t)n * 4),
+                 o_y2 = take((size_t)n * 4), o_a1 = take(n), o_a2 = take(n), o_co = take((size_t)n * R.hw),
+                 o_xs = take((size_t)n * Ds * 4), o_xp = take((size_t)n2 * Dp * 4), o_zs = take(nH), o_as = take(nH),
+                 o_zp = take(2 * nH), o_ap = take(2 * nH), o_cat = take(4 * nH), o_zt0 = take(2 * nH), o_at0 = take(2 * nH),
+                 o_zt4 = take(2 * nH), o_at4 = take(2 * nH), o_d12 = take((size_t)n2 * 48), o_dt4 = take(2 * nH),
+                 o_dt0 = take(2 * nH), o_dcat = take(4 * nH), o_dp = take(2 * nH), o_ds = take(nH),
+                 o_parts = take((size_t)6 * TRAIN_MAX_PARTS * H * 8), o_mean = take((size_t)7 * H * 8), o_rstd = take((size_t)7 * H * 4),
+                 o_wpart = take((size_t)sp2.S * H * std::max(std::max(Ds, Dp), H2) * 4),
+                 o_bpart = take((size_t)sp2.S * H * 4), o_lpart = take((size_t)head_blocks * 32), o_loss = take(6 * 4),
+                 o_bnscr = take((size_t)2 * H * 4);
+    int before = 0;
+    HIP_TRY(hipGetDevice(&before));  // the caller's framework keeps its own current device
+    if (before != R.device) HIP_TRY(hipSetDevice(R.device));
+    if (total > R.train_ws_bytes) {
+        hipError_t e = R.wait_batches();  // a pending step may still use the old workspace
+        if (e == hipSuccess) e = regrow(R.train_ws, total);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            R.train_ws_bytes = 0;
+            if (before != R.device) (void)hipSetDevice(before);
+            return fail(AR_E_NOMEM, "not enough device memory for a training workspace of " + std::to_string(total) + " bytes");
+        }
+        R.train_ws_bytes = total;
+    }
+    uint8_t* ws = R.train_ws.p;
+    auto F = [&](size_t at) { return (float*)(ws + at); };
+    float *X = F(o_x), *Xs = F(o_xs), *Xp = F(o_xp), *Zs = F(o_zs), *As = F(o_as), *Zp = F(o_zp), *Ap = F(o_ap), *Cat = F(o_cat),
+          *Zt0 = F(o_zt0), *At0 = F(o_at0), *Zt4 = F(o_zt4), *At4 = F(o_at4), *D12 = F(o_d12), *dT4 = F(o_dt4), *dT0 = F(o_dt0),
+          *dCat = F(o_dcat), *dP = F(o_dp), *dS = F(o_ds), *rstds = F(o_rstd), *wpart = F(o_wpart), *bpart = F(o_bpart),
+          *bnscr = F(o_bnscr);
+    double *parts = (double*)(ws + o_parts), *means = (double*)(ws + o_mean);
+    auto part = [&](int i) { return parts + (size_t)i * TRAIN_MAX_PARTS * H; };
+    const size_t half = (size_t)n * H;  // P2's rows of a [2n][H] array
+    hipError_t err = hipSuccess;
+    // the workspace is shared by every step of this set: a step on another stream starts behind the last one
+    if (R.has_batch) err = hipStreamWaitEvent(stream, R.ev_batch, 0);
+    auto launched = [&]() {
+        if (err == hipSuccess) err = hipGetLastError();
+    };
+    auto blocks = [](size_t count) { return dim3((unsigned)((count + 255) / 256)); };
+    RowOut ro;
+    ro.observation = X;
+    ro.policy_p1 = F(o_t1);
+    ro.policy_p2 = F(o_t2);
+    ro.value_p1 = F(o_y1);
+    ro.value_p2 = F(o_y2);
+    ro.action_p1 = (int8_t*)(ws + o_a1);
+    ro.action_p2 = (int8_t*)(ws + o_a2);
+    ro.cheese_outcomes = (int8_t*)(ws + o_co);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(k_rows_batch<NW>, dim3((n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(ROWS_PER_BLOCK * ROWS_LANES), 0,
+                           stream, (const PosRec<NW>*)R.recs.p, (const uint32_t*)R.pos_game.p, (const RowGame*)R.games.p,
+                           (const uint8_t*)R.mazes.p, (const uint8_t*)R.outcomes.p, (const uint64_t*)R.ord_rows.p,
+                           (const uint8_t*)R.ord_swap.p, first, (uint64_t)0, (uint32_t)n, ro);
+        hipLaunchKernelGGL(k_sym_split, blocks((size_t)n * (Ds + 2 * Dp)), dim3(256), 0, stream, (const float*)X, Xs, Xp, n, hw);
+        launched();
+    }
+    // C[M][N] = sum_k A(m, k) B(k, n)
+    auto gemm = [&](const float* a, long sam, long sak, int a_kfast, const float* b, long sbk, long sbn, int b_kfast, float* c, int M,
+                    int N, int K, const float* bias, int splits, int k_per_split, float* colsum) {
+        if (err != hipSuccess) return;
+        TrainGemm t;
+        t.a = a;
+        t.b = b;
+        t.bias = bias;
+        t.c = c;
+        t.colsum = colsum;
+        t.M = M;
+        t.N = N;
+        t.K = K;
+        t.k_per_split = k_per_split;
+        t.ldc = N;
+        t.sam = sam;
+        t.sak = sak;
+        t.sbk = sbk;
+        t.sbn = sbn;
+        t.c_split = (size_t)M * N;
+        t.a_kfast = a_kfast;
+        t.b_kfast = b_kfast;
+        hipLaunchKernelGGL(k_train_gemm, dim3((N + TG_TILE - 1) / TG_TILE, (M + TG_TILE - 1) / TG_TILE, splits), dim3(TG_THREADS), 0,
+                           stream, t);
+        launched();
+    };
+    // Z[rows][H] = In[rows][K] W[H][K]^T + b
+    auto linear = [&](const float* in, int rows, int K, const float* w, const float* b, float* z) {
+        gemm(in, K, 1, 1, w, 1, K, 1, z, rows, Hi, K, b, 1, K, nullptr);
+    };
+    // dW[H][N] = d[rows][H]^T In[rows][N] and db = colsum(d), per row range, then the ranges in order
+    auto grad_w = [&](const float* d, const float* in, int rows, int N, const Split& sp, float* w, float* b) {
+        gemm(d, 1, Hi, 0, in, N, 1, 0, wpart, Hi, N, rows, nullptr, sp.S, sp.kps, bpart);
+        if (err != hipSuccess) return;
+        TrainReduce t;
+        t.wpart = wpart;
+        t.bpart = bpart;
+        t.S = sp.S;
+        t.M = Hi;
+        t.N = N;
+        t.w[0] = w, t.w[1] = nullptr, t.w[2] = nullptr;
+        t.b[0] = b, t.b[1] = nullptr, t.b[2] = nullptr;
+        t.rows[0] = Hi, t.rows[1] = 0, t.rows[2] = 0;
+        hipLaunchKernelGGL(k_train_reduce, blocks((size_t)Hi * N + Hi), dim3(256), 0, stream, t);
+        launched();
+    };
+    const dim3 cgrid((H + 63) / 64, tc.P);
+    // one BatchNorm call (0: shared; 1, 2: player_encoder.1 of P1, P2; 3, 4: trunk.1; 5, 6: trunk.5) over n rows at z
+    auto bn_forward = [&](int call, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
+        if (err != hipSuccess) return;
+        TrainColArgs a;
+        memset(&a, 0, sizeof a);
+        a.z = z;
+        a.part0 = part(0);
+        hipLaunchKernelGGL(k_train_colsum<TC_SUM>, cgrid, dim3(256), 0, stream, tc, a);
+        a.sum_in = part(0);
+        a.part0 = part(1);
+        hipLaunchKernelGGL(k_train_colsum<TC_SQ>, cgrid, dim3(256), 0, stream, tc, a);
+        hipLaunchKernelGGL(k_train_bn_apply, cgrid, dim3(256), 0, stream, tc, z, (const double*)part(0), (const double*)part(1),
+                           gamma, beta, act, means + (size_t)call * H, rstds + (size_t)call * H, rm, rv);
+        launched();
+    };
+    // a module called for both players: P1's call, then P2's on top of it
+    auto bn_forward2 = [&](int call, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
+        bn_forward(call, z, gamma, beta, act, rm, rv);
+        bn_forward(call + 1, z + half, gamma, beta, act + half, rm, rv);
+    };
+    // dz in place of d for one call; its column sums stay in part(2 + 2 * slot), part(3 + 2 * slot)
+    auto bn_backward = [&](int call, int slot, bool head, const float* z, const float* act, float* d, const float* d12,
+                           const float* gamma, float* dgamma, float* dbeta) {
+        if (err != hipSuccess) return;
+        double *p0 = part(2 + 2 * slot), *p1 = part(3 + 2 * slot);
+        const double* mu = means + (size_t)call * H;
+        const float* rstd = rstds + (size_t)call * H;
+        if (head) {
+            SymDHead a;
+            a.z = z;
+            a.act = act;
+            a.d = d;
+            a.d12 = d12;
+            a.w_p = p.policy_w;
+            a.w_v = p.value_w;
+            a.mu = mu;
+            a.rstd = rstd;
+            a.part0 = p0;
+            a.part1 = p1;
+            hipLaunchKernelGGL(k_sym_dhead, cgrid, dim3(256), 0, stream, tc, a);
+        } else {
+            TrainColArgs a;
+            memset(&a, 0, sizeof a);
+            a.z = z;
+            a.act = act;
+            a.d = d;
+            a.mu = mu;
+            a.rstd = rstd;
+            a.part0 = p0;
+            a.part1 = p1;
+            hipLaunchKernelGGL(k_train_colsum<TC_DTRUNK>, cgrid, dim3(256), 0, stream, tc, a);
+        }
+        hipLaunchKernelGGL(k_train_bn_bwd, cgrid, dim3(256), 0, stream, tc, z, d, (const double*)p0, (const double*)p1, mu, rstd,
+                           gamma, dgamma, dbeta);
+        launched();
+    };
+    // both calls of a shared module; the module's two gradients from both calls' column sums (k_train_bn_bwd's own go to bnscr)
+    auto bn_backward2 = [&](int call, bool head, const float* z, const float* act, float* d, const float* gamma, float* dgamma,
+                            float* dbeta) {
+        bn_backward(call, 0, head, z, act, d, D12, gamma, bnscr, bnscr + H);
+        bn_backward(call + 1, 1, head, z + half, act + half, d + half, D12 + (size_t)n * 12, gamma, bnscr, bnscr + H);
+        if (err != hipSuccess) return;
+        hipLaunchKernelGGL(k_sym_bn_grad, dim3((H + 255) / 256), dim3(256), 0, stream, tc.P, Hi, (const double*)part(2),
+                           (const double*)part(3), (const double*)part(4), (const double*)part(5), dgamma, dbeta);
+        launched();
+    };
+    float* const* rs = (float* const*)run;  // se mean, var; pe; trunk.1; trunk.5
+    auto rstat = [&](int i) { return run ? rs[i] : (float*)nullptr; };
+    // forward
+    linear(Xs, n, Ds, p.se0_w, p.se0_b, Zs);
+    bn_forward(0, Zs, p.se1_w, p.se1_b, As, rstat(0), rstat(1));
+    linear(Xp, n2, Dp, p.pe0_w, p.pe0_b, Zp);
+    bn_forward2(1, Zp, p.pe1_w, p.pe1_b, Ap, rstat(2), rstat(3));
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(k_sym_cat, blocks((size_t)4 * n * H), dim3(256), 0, stream, (const float*)As, (const float*)Ap, Cat, n, Hi);
+        launched();
+    }
+    linear(Cat, n2, H2, p.trunk0_w, p.trunk0_b, Zt0);
+    bn_forward2(3, Zt0, p.bn1_w, p.bn1_b, At0, rstat(4), rstat(5));
+    linear(At0, n2, Hi, p.trunk4_w, p.trunk4_b, Zt4);
+    bn_forward2(5, Zt4, p.bn2_w, p.bn2_b, At4, rstat(6), rstat(7));
+    if (err == hipSuccess) {
+        SymHeads t;
+        t.h = At4;
+        t.w_p = p.policy_w, t.b_p = p.policy_b, t.w_v = p.value_w, t.b_v = p.value_b;
+        t.t1 = ro.policy_p1, t.t2 = ro.policy_p2, t.y1 = ro.value_p1, t.y2 = ro.value_p2;
+        t.d12 = D12;
+        t.loss_part = (double*)(ws + o_lpart);
+        t.logits_p1 = out ? out->logits_p1 : nullptr;
+        t.logits_p2 = out ? out->logits_p2 : nullptr;
+        t.value_p1 = out ? out->value_p1 : nullptr;
+        t.value_p2 = out ? out->value_p2 : nullptr;
+        t.n = n;
+        t.H = Hi;
+        t.pw_n = pw / (float)n;
+        t.vw_n = vw / (float)n;
+        hipLaunchKernelGGL(k_sym_heads, dim3(head_blocks), dim3(256), (size_t)12 * H * 4, stream, t);
+        hipLaunchKernelGGL(k_train_loss_sum, dim3(1), dim3(256), 0, stream, (const double*)(ws + o_lpart), (uint32_t)head_blocks,
+                           (uint32_t)n, pw, vw, F(o_loss), out ? out->losses : nullptr);
+        launched();
+    }
+    // backward: the heads
+    gemm(D12, 1, 12, 0, At4, Hi, 1, 0, wpart, 12, Hi, n2, nullptr, sp2.S, sp2.kps, bpart);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(k_sym_head_reduce, blocks((size_t)12 * H + 6), dim3(256), 0, stream, (const float*)wpart,
+                           (const float*)bpart, sp2.S, Hi, g.policy_w, g.policy_b, g.value_w, g.value_b);
+        launched();
+    }
+    // the trunk
+    bn_backward2(5, true, Zt4, At4, dT4, p.bn2_w, g.bn2_w, g.bn2_b);
+    grad_w(dT4, At0, n2, Hi, sp2, g.trunk4_w, g.trunk4_b);
+    gemm(dT4, Hi, 1, 1, p.trunk4_w, Hi, 1, 0, dT0, n2, Hi, Hi, nullptr, 1, Hi, nullptr);
+    bn_backward2(3, false, Zt0, At0, dT0, p.bn1_w, g.bn1_w, g.bn1_b);
+    grad_w(dT0, Cat, n2, H2, sp2, g.trunk0_w, g.trunk0_b);
+    gemm(dT0, Hi, 1, 1, p.trunk0_w, H2, 1, 0, dCat, n2, H2, Hi, nullptr, 1, Hi, nullptr);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(k_sym_uncat, blocks((size_t)2 * n * H), dim3(256), 0, stream, (const float*)dCat, dS, dP, n, Hi);
+        launched();
+    }
+    // the encoders
+    bn_backward2(1, false, Zp, Ap, dP, p.pe1_w, g.pe1_w, g.pe1_b);
+    grad_w(dP, Xp, n2, Dp, sp2, g.pe0_w, g.pe0_b);
+    bn_backward(0, 0, false, Zs, As, dS, nullptr, p.se1_w, g.se1_w, g.se1_b);
+    grad_w(dS, Xs, n, Ds, sp1, g.se0_w, g.se0_b);
+    if (err == hipSuccess) {
+        err = hipEventRecord(R.ev_batch, stream);
+        R.has_batch = true;
+    }
+    if (before != R.device) (void)hipSetDevice(before);
+    HIP_TRY(err);
+    return AR_OK;
+}
+
 // ar_rows_validate: the request in chunks of `chunk` rows -- requests from the stored records (k_val_requests), the
 // evaluator with its logits output (net_launch), the terms of every row summed per block (k_val_terms) and added to the
 // running total (k_val_sum) -- all on the null stream; blocks until the sums are on the host. No observation, no target
@@ -5000,6 +5305,16 @@ int ar_rows_grad_mlp(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_di
                                                out, (hipStream_t)stream)
                             : rows_grad_mlp<4>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight, value_weight,
                                                out, (hipStream_t)stream);
+}
+
+int ar_rows_grad_symmetric(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArSymTensors* params,
+                           const ArSymTensors* grads, const ArSymBnStats* running, float policy_weight, float value_weight,
+                           const ArTrainOut* out, void* stream) {
+    if (!s || !s->impl || !params || !grads) return fail(AR_E_INVALID, "null argument");
+    return s->impl->nw == 1 ? rows_grad_symmetric<1>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight,
+                                                     value_weight, out, (hipStream_t)stream)
+                            : rows_grad_symmetric<4>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight,
+                                                     value_weight, out, (hipStream_t)stream);
 }
 
 int ar_rows_clear(ArRowSet* s) {

@@ -146,16 +146,45 @@ def mlp_param_shapes(width: int, height: int, hidden_dim: int) -> dict:
     return shapes
 
 
-def check_grad_tensors(params: dict, grads: dict, running, out, n: int, width: int, height: int, hidden_dim: int, device) -> None:
+# SymmetricMLP's parameters (alpharat/nn/models/symmetric.py) in torch's named_parameters() order, which is the order of
+# ArSymTensors (_lib.SYM_TENSORS); its running statistics in the order of ArSymBnStats
+SYM_PARAM_KEYS = ("shared_encoder.0.weight", "shared_encoder.0.bias", "shared_encoder.1.weight", "shared_encoder.1.bias",
+                  "player_encoder.0.weight", "player_encoder.0.bias", "player_encoder.1.weight", "player_encoder.1.bias",
+                  "trunk.0.weight", "trunk.0.bias", "trunk.1.weight", "trunk.1.bias", "trunk.4.weight", "trunk.4.bias",
+                  "trunk.5.weight", "trunk.5.bias", "policy_head.weight", "policy_head.bias", "value_head.weight",
+                  "value_head.bias")
+SYM_BN_MODULES = ("shared_encoder.1", "player_encoder.1", "trunk.1", "trunk.5")
+SYM_RUNNING_KEYS = tuple(f"{bn}.{s}" for bn in SYM_BN_MODULES for s in ("running_mean", "running_var"))
+
+
+def sym_param_shapes(width: int, height: int, hidden_dim: int) -> dict:
+    """The shape of every tensor of ``SYM_PARAM_KEYS`` and ``SYM_RUNNING_KEYS``."""
+    hw, H = width * height, hidden_dim
+    shapes = {"shared_encoder.0.weight": (H, 5 * hw + 1), "player_encoder.0.weight": (H, hw + 2), "trunk.0.weight": (H, 2 * H),
+              "trunk.4.weight": (H, H), "policy_head.weight": (5, 2 * H), "policy_head.bias": (5,), "value_head.weight": (1, 2 * H),
+              "value_head.bias": (1,)}
+    for k in SYM_PARAM_KEYS + SYM_RUNNING_KEYS:
+        shapes.setdefault(k, (H,))
+    return shapes
+
+
+def check_grad_tensors(params: dict, grads: dict, running, out, n: int, width: int, height: int, hidden_dim: int, device,
+                       architecture: str = "mlp") -> None:
     """``RowSet.grad_mlp_into``'s conditions on its tensors (``ValueError``), in the manner of ``check_out_tensors``; no
-    device and no library is needed."""
+    device and no library is needed. ``architecture="symmetric"``: ``RowSet.grad_symmetric_into``'s, over
+    ``SYM_PARAM_KEYS`` and ``SYM_RUNNING_KEYS``."""
     import torch
 
-    shapes = mlp_param_shapes(width, height, hidden_dim)
+    if architecture == "mlp":
+        param_keys, running_keys, shapes = MLP_PARAM_KEYS, MLP_RUNNING_KEYS, mlp_param_shapes(width, height, hidden_dim)
+    elif architecture == "symmetric":
+        param_keys, running_keys, shapes = SYM_PARAM_KEYS, SYM_RUNNING_KEYS, sym_param_shapes(width, height, hidden_dim)
+    else:
+        raise ValueError(f"no training step for architecture {architecture!r}")
     out_shapes = dict(losses=(6,), logits_p1=(n, 5), logits_p2=(n, 5), value_p1=(n,), value_p2=(n,))
-    groups = [("params", params, MLP_PARAM_KEYS, shapes, True), ("grads", grads, MLP_PARAM_KEYS, shapes, True)]
+    groups = [("params", params, param_keys, shapes, True), ("grads", grads, param_keys, shapes, True)]
     if running is not None:
-        groups.append(("running", running, MLP_RUNNING_KEYS, shapes, True))
+        groups.append(("running", running, running_keys, shapes, True))
     if out is not None:
         groups.append(("out", out, TRAIN_OUT_KEYS, out_shapes, False))
     for what, d, keys, want, required in groups:
@@ -293,6 +322,31 @@ class RowSet:
                                                 C.byref(r) if r is not None else None, float(policy_weight),
                                                 float(value_weight), C.byref(o) if o is not None else None,
                                                 C.c_void_p(stream.cuda_stream)))
+
+    def grad_symmetric_into(self, first: int, n: int, hidden_dim: int, params: dict, grads: dict, running, policy_weight: float,
+                            value_weight: float, out, stream=None) -> None:
+        """``grad_mlp_into`` for SymmetricMLP (``ar_rows_grad_symmetric``): ``params`` and ``grads`` are the twenty tensors
+        under ``SYM_PARAM_KEYS``, ``running`` the eight ``SYM_RUNNING_KEYS`` or ``None``, of the shapes
+        ``sym_param_shapes(width, height, hidden_dim)`` gives; everything else as there."""
+        import torch
+
+        first, n, hidden_dim = int(first), int(n), int(hidden_dim)
+        if first < 0 or n < 0 or hidden_dim <= 0:
+            raise ValueError("first and n must not be negative, hidden_dim positive")
+        check_grad_tensors(params, grads, running, out, n, self.width, self.height, hidden_dim,
+                           torch.device("cuda", self.device_index), architecture="symmetric")
+        handle = self._handle()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device_index)
+        p = _lib.ArSymTensors(*[params[k].data_ptr() for k in SYM_PARAM_KEYS])
+        g = _lib.ArSymTensors(*[grads[k].data_ptr() for k in SYM_PARAM_KEYS])
+        r = _lib.ArSymBnStats(*[running[k].data_ptr() for k in SYM_RUNNING_KEYS]) if running is not None else None
+        o = (_lib.ArTrainOut(*[out[k].data_ptr() if out.get(k) is not None else None for k in TRAIN_OUT_KEYS])
+             if out is not None else None)
+        _lib.check(_lib.load().ar_rows_grad_symmetric(handle, first, n, hidden_dim, C.byref(p), C.byref(g),
+                                                      C.byref(r) if r is not None else None, float(policy_weight),
+                                                      float(value_weight), C.byref(o) if o is not None else None,
+                                                      C.c_void_p(stream.cuda_stream)))
 
     def validate(self, net, rows, chunk_rows: int = 0, return_rows: bool = False):
         """``net`` over the stored positions ``rows``: the sums of the reference's validation pass

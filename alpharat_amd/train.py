@@ -1,4 +1,4 @@
-"""The training step of PyRatMLP over a device-resident ``RowSet``: forward, losses and gradients in one call.
+"""The training step of PyRatMLP or SymmetricMLP over a device-resident ``RowSet``: forward, losses and gradients in one call.
 
 The reference's loop (alpharat/nn/training/loop.py) gathers a batch, runs ``model(obs)`` in training mode,
 ``compute_mlp_losses`` and ``loss.backward()``. ``MLPGradStep.step`` does the three for rows ``first .. first + n`` of the
@@ -10,19 +10,23 @@ schedule and the checkpoints stay the trainer's::
     for n, losses in train_dataset.grad_iter(step, 4096, epoch=epoch, seed=seed):
         optimizer.step()
 
-Supported: PyRatMLP (``architecture: mlp``) in float32 with ``dropout`` 0.0 -- the architecture's default -- and a hidden
-width that is a multiple of 32, at most 256. LocalValueMLP is refused: its loss has a third term (the ownership head).
-AMP, dropout and the other architectures are not built.
+Supported: PyRatMLP (``architecture: mlp``, ``MLPGradStep``) and SymmetricMLP (``architecture: symmetric``,
+``SymmetricGradStep`` over ``ar_rows_grad_symmetric``, alpharat_amd/csrc/train_sym.h; same loop, same contract) in float32
+with ``dropout`` 0.0 -- the architectures' default -- and a hidden width that is a multiple of 32, at most 256.
+LocalValueMLP is refused: its loss has a third term (the ownership head). AMP, dropout and the other architectures are not
+built. (The reference's configs/model/symmetric.yaml sets ``dropout: 0.1``: a model built from it is refused until that is
+0.0.)
 
-``trunk.0.bias`` and ``trunk.4.bias`` sit in front of a BatchNorm, so their true gradient is zero and what any
-implementation writes there is rounding noise.
+``trunk.0.bias`` and ``trunk.4.bias`` -- and SymmetricMLP's ``shared_encoder.0.bias`` and ``player_encoder.0.bias`` -- sit
+in front of a BatchNorm, so their true gradient is zero and what any implementation writes there is rounding noise
+(INTEGRATION.md).
 
 torch ships its own copy of the HIP runtime and a process brings up only one: import torch before anything loads
 ``libalpharat_hip.so``.
 """
 from __future__ import annotations
 
-from .shards import MLP_PARAM_KEYS, MLP_RUNNING_KEYS, RowSet
+from .shards import MLP_PARAM_KEYS, MLP_RUNNING_KEYS, SYM_BN_MODULES, SYM_PARAM_KEYS, SYM_RUNNING_KEYS, RowSet
 
 _PREFIX = "_orig_mod."  # torch.compile's wrapper, stripped as weights.py does
 
@@ -90,6 +94,74 @@ class MLPGradStep:
         if training:
             for t in self._tracked:
                 t.add_(1)
+        if outputs:
+            return out["losses"], out["logits_p1"], out["logits_p2"], out["value_p1"], out["value_p2"]
+        return out["losses"]
+
+
+class SymmetricGradStep:
+    """``MLPGradStep`` for SymmetricMLP: ``model`` is an ``nn.Module`` whose ``state_dict()`` has SymmetricMLP's keys (an
+    ``_orig_mod.`` prefix is stripped). ``ValueError`` for a ``Dropout`` with ``p != 0``, a missing key (a PyRatMLP lacks
+    the encoders and ``policy_head``), or a parameter or BatchNorm buffer that is not float32 or not contiguous. One
+    persistent gradient tensor per parameter is allocated here."""
+
+    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0) -> None:
+        import torch
+
+        self.model = model
+        self.policy_weight, self.value_weight = float(policy_weight), float(value_weight)
+        for m in model.modules():
+            if isinstance(m, torch.nn.Dropout) and m.p != 0:
+                raise ValueError(f"dropout {m.p} is not supported: the step is built for SymmetricMLP's default dropout 0.0")
+        named = {k.removeprefix(_PREFIX): v for k, v in model.named_parameters()}
+        buffers = {k.removeprefix(_PREFIX): v for k, v in model.named_buffers()}
+        tracked = tuple(f"{bn}.num_batches_tracked" for bn in SYM_BN_MODULES)
+        missing = [k for k in SYM_PARAM_KEYS if k not in named] + [k for k in SYM_RUNNING_KEYS + tracked if k not in buffers]
+        if missing:
+            raise ValueError(f"the model is not a SymmetricMLP: its state_dict lacks {', '.join(missing)}")
+        self.params = {k: named[k] for k in SYM_PARAM_KEYS}
+        self.running = {k: buffers[k] for k in SYM_RUNNING_KEYS}
+        # shared_encoder.1 sees a batch once, the other three modules once per player
+        self._tracked = tuple((buffers[k], 1 if k.startswith("shared_encoder.") else 2) for k in tracked)
+        for k, t in {**self.params, **self.running}.items():
+            if t.dtype != torch.float32:
+                raise ValueError(f"{k} has dtype {t.dtype}: the step is float32 throughout")
+            if not t.is_contiguous():
+                raise ValueError(f"{k} is not contiguous")
+        w4, ws, wp = (self.params[k] for k in ("trunk.4.weight", "shared_encoder.0.weight", "player_encoder.0.weight"))
+        for k, w in (("trunk.4.weight", w4), ("shared_encoder.0.weight", ws), ("player_encoder.0.weight", wp)):
+            if w.dim() != 2:
+                raise ValueError(f"{k} has shape {tuple(w.shape)}")
+        self.hidden_dim, self.shared_dim, self.player_dim = int(w4.shape[0]), int(ws.shape[1]), int(wp.shape[1])
+        self.grads = {k: torch.zeros_like(p) for k, p in self.params.items()}
+
+    def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
+        """``MLPGradStep.step`` under the same contract: launched on torch's current stream, nothing synchronised, every
+        parameter's ``.grad`` is (again) this object's buffer, overwritten. The batch's statistics are always used; with
+        ``model.training`` the running statistics are updated in place (P1's call, then P2's) and
+        ``num_batches_tracked`` grows by one for ``shared_encoder.1`` and by two for the other three modules. Returns the
+        ``(6,)`` losses, with ``outputs`` also the four training-mode outputs."""
+        import torch
+
+        hw = rowset.width * rowset.height
+        if (5 * hw + 1, hw + 2) != (self.shared_dim, self.player_dim):
+            raise ValueError(f"the model's encoders read {self.shared_dim} and {self.player_dim} inputs, a "
+                             f"{rowset.width}x{rowset.height} board gives {5 * hw + 1} and {hw + 2}")
+        device = torch.device("cuda", rowset.device_index)
+        n = int(n)
+        out = dict(losses=torch.empty(6, device=device, dtype=torch.float32))
+        if outputs:
+            out.update(logits_p1=torch.empty((n, 5), device=device), logits_p2=torch.empty((n, 5), device=device),
+                       value_p1=torch.empty(n, device=device), value_p2=torch.empty(n, device=device))
+        training = bool(self.model.training)
+        params = {k: p.data for k, p in self.params.items()}
+        rowset.grad_symmetric_into(first, n, self.hidden_dim, params, self.grads, self.running if training else None,
+                                   self.policy_weight, self.value_weight, out)
+        for k, p in self.params.items():
+            p.grad = self.grads[k]
+        if training:
+            for t, calls in self._tracked:
+                t.add_(calls)
         if outputs:
             return out["losses"], out["logits_p1"], out["logits_p2"], out["value_p1"], out["value_p2"]
         return out["losses"]

@@ -516,6 +516,40 @@ int ar_rows_grad_mlp(ArRowSet* set, uint64_t first, uint64_t n, uint32_t hidden_
                      const ArMlpTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
                      const ArTrainOut* out, void* stream);
 
+/* ---- training gradients of SymmetricMLP over stored rows (nn/models/symmetric.py in training mode, the loss of
+ * architectures/symmetric/loss.py, loss.backward()) -----------------------------------------------------------------------
+ * ar_rows_grad_mlp for the second architecture: the same rows, the same loss (no third term), the same BatchNorm
+ * arithmetic, ArTrainOut, streams, workspace (the two steps share the set's one workspace and wait for each other) and
+ * refusals. With hw = h*w the inputs are columns of the flat row: shared_raw = [0, 4hw) + [6hw, 7hw) + scalar 1,
+ * p1_raw = [4hw, 5hw) + scalars 2, 4, p2_raw = [5hw, 6hw) + scalars 3, 5. shared = se(shared_raw), p_i = pe(p_i_raw),
+ * h_i = trunk(cat(shared, p_i)), agg = h_1 + h_2, logits_i = policy(cat(h_i, agg)), value_i = softplus(value(cat(h_i, agg))).
+ * Seven BatchNorm applications over four modules: se1 sees the batch once; pe1, bn1 (trunk.1) and bn2 (trunk.5) are called
+ * for P1's rows and then for P2's, each call with its own batch mean and variance, never pooled. Running statistics, when
+ * given: P1's call updates first, P2's on top of it, rm = 0.9 (0.9 rm + 0.1 mu_1) + 0.1 mu_2, each variance with its own
+ * n / (n - 1). The gradient of a shared tensor is the sum of its two calls' contributions, P1's before P2's. se0_b, pe0_b,
+ * trunk0_b and trunk4_b sit in front of a BatchNorm: what is written there is the column sum of dz, rounding noise. */
+typedef struct ArSymTensors { /* device pointers, f32, C order: SymmetricMLP's parameters in named_parameters() order */
+    float *se0_w, *se0_b;       /* [H][5hw + 1], [H]   shared_encoder.0 */
+    float *se1_w, *se1_b;       /* [H]                 shared_encoder.1 */
+    float *pe0_w, *pe0_b;       /* [H][hw + 2], [H]    player_encoder.0 */
+    float *pe1_w, *pe1_b;       /* [H]                 player_encoder.1 */
+    float *trunk0_w, *trunk0_b; /* [H][2H], [H]        */
+    float *bn1_w, *bn1_b;       /* [H]  trunk.1        */
+    float *trunk4_w, *trunk4_b; /* [H][H], [H]         */
+    float *bn2_w, *bn2_b;       /* [H]  trunk.5        */
+    float *policy_w, *policy_b; /* [5][2H], [5]        */
+    float *value_w, *value_b;   /* [1][2H], [1]        */
+} ArSymTensors;
+typedef struct ArSymBnStats { /* running statistics [H], updated in place */
+    float *se_mean, *se_var, *pe_mean, *pe_var, *bn1_mean, *bn1_var, *bn2_mean, *bn2_var;
+} ArSymBnStats;
+/* As ar_rows_grad_mlp in every other respect: `grads` overwritten; running and out may be NULL; launched on `stream` with
+ * no synchronisation; the workspace is about 151 MB at n = 4096, 7x7, H = 256 and about 2.2 GB at the cap of 65536 rows;
+ * AR_E_INVALID before any launch, nothing written, for the same list (here twenty tensors, eight running statistics). */
+int ar_rows_grad_symmetric(ArRowSet* set, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArSymTensors* params,
+                           const ArSymTensors* grads, const ArSymBnStats* running, float policy_weight, float value_weight,
+                           const ArTrainOut* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
