@@ -3233,106 +3233,129 @@ static hipError_t regrow(DevBuf<T>& b, size_t count) {
     return b.alloc(count);
 }
 
-// ar_rows_grad_mlp: the loss and the gradients of PyRatMLP over rows first .. first + n of the order (train_mlp.h), on the
-// caller's stream. Everything is checked before the first launch; it then only launches, and allocates only when the
-// workspace must grow (after waiting for what may still use the old one). ev_batch sits behind the last launch, so
-// whatever waits for pending batches waits for a pending step too.
+// What the training steps of a row set share (ar_rows_grad_mlp, ar_rows_grad_symmetric): the refusals, the workspace, the
+// stream rule and the launches that both chains are made of. One rule for the workspace and the stream, stated here only:
+// a set has one workspace, grown to the largest request; a step waits on ev_batch before it touches it, so a step on
+// another stream starts behind the last one; growth first waits for the pending batches, which may still use the old
+// block; and ev_batch is recorded behind the step's last launch, so whatever waits for pending batches waits for a
+// pending step too. Everything is checked before the first launch; a step then only launches, and allocates only to grow.
+// `err` is sticky: after the first failure every member returns without launching, and end() reports it.
 static const char* const kMlpTensorNames[14] = {"trunk0_w", "trunk0_b", "bn1_w",  "bn1_b",  "trunk4_w", "trunk4_b", "bn2_w",
                                                 "bn2_b",    "p1_w",     "p1_b",   "p2_w",   "p2_b",     "value_w",  "value_b"};
-template <int NW>
-int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const ArMlpTensors& p, const ArMlpTensors& g,
-                  const ArMlpBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream) {
-    if (!R.has_order) return fail(AR_E_INVALID, "the row set has no order: ar_rows_order_set comes first");
-    if (first > R.ord_n || n64 > R.ord_n - first)
-        return fail(AR_E_INVALID, "rows " + std::to_string(first) + " + " + std::to_string(n64) + " go beyond the order of " +
-                                      std::to_string(R.ord_n));
-    if (n64 < 2) return fail(AR_E_INVALID, "a training BatchNorm needs at least two rows");
-    if (n64 > (uint64_t)TRAIN_MAX_ROWS) return fail(AR_E_INVALID, "at most 65536 rows a step");
-    if (H == 0 || H % 32 != 0 || H > 256)
-        return fail(AR_E_INVALID, "hidden_dim must be a multiple of 32, at most 256 (got " + std::to_string(H) + ")");
-    static_assert(sizeof(ArMlpTensors) == 14 * sizeof(float*), "fourteen pointers");
-    float* const* pp = (float* const*)&p;
-    float* const* gp = (float* const*)&g;
-    for (int i = 0; i < 14; ++i) {
-        if (!pp[i] || !gp[i]) return fail(AR_E_INVALID, std::string("null tensor: ") + kMlpTensorNames[i]);
-        if (int rc = rows_check_device_ptr(R, pp[i], 4, kMlpTensorNames[i])) return rc;
-        if (int rc = rows_check_device_ptr(R, gp[i], 4, kMlpTensorNames[i])) return rc;
-    }
-    if (run) {
-        float* const rs[4] = {run->mean1, run->var1, run->mean2, run->var2};
-        for (float* q : rs) {
-            if (!q) return fail(AR_E_INVALID, "null running statistic");
-            if (int rc = rows_check_device_ptr(R, q, 4, "running statistic")) return rc;
+static const char* const kSymTensorNames[20] = {"se0_w",    "se0_b",    "se1_w",  "se1_b",  "pe0_w",    "pe0_b",    "pe1_w",
+                                                "pe1_b",    "trunk0_w", "trunk0_b", "bn1_w", "bn1_b",    "trunk4_w", "trunk4_b",
+                                                "bn2_w",    "bn2_b",    "policy_w", "policy_b", "value_w", "value_b"};
+struct TrainStep {
+    RowStore& R;
+    hipStream_t stream;
+    int n = 0, H = 0, head_blocks = 0;
+    TrainCols tc{};
+    size_t total = 0;     // bytes of workspace taken so far
+    size_t o_rows[8]{};   // the row targets: x, t1, t2, y1, y2, a1, a2, co
+    size_t o_lpart = 0, o_loss = 0;
+    uint8_t* ws = nullptr;
+    float *wpart = nullptr, *bpart = nullptr;  // grad_w's partial products and column sums: the driver sizes and sets them
+    RowOut ro{};
+    hipError_t err = hipSuccess;
+    int before = 0;  // the caller's framework keeps its own current device
+
+    // the refusals; `params`, `grads`: `count` pointers named by `names`; `running`: n_running pointers (0: none given)
+    int check(uint64_t first, uint64_t n64, uint32_t H_, const char* const* names, float* const* params, float* const* grads,
+              int count, float* const* running, int n_running, const ArTrainOut* out) {
+        if (!R.has_order) return fail(AR_E_INVALID, "the row set has no order: ar_rows_order_set comes first");
+        if (first > R.ord_n || n64 > R.ord_n - first)
+            return fail(AR_E_INVALID, "rows " + std::to_string(first) + " + " + std::to_string(n64) + " go beyond the order of " +
+                                          std::to_string(R.ord_n));
+        if (n64 < 2) return fail(AR_E_INVALID, "a training BatchNorm needs at least two rows");
+        if (n64 > (uint64_t)TRAIN_MAX_ROWS) return fail(AR_E_INVALID, "at most 65536 rows a step");
+        if (H_ == 0 || H_ % 32 != 0 || H_ > 256)
+            return fail(AR_E_INVALID, "hidden_dim must be a multiple of 32, at most 256 (got " + std::to_string(H_) + ")");
+        for (int i = 0; i < count; ++i) {
+            if (!params[i] || !grads[i]) return fail(AR_E_INVALID, std::string("null tensor: ") + names[i]);
+            if (int rc = rows_check_device_ptr(R, params[i], 4, names[i])) return rc;
+            if (int rc = rows_check_device_ptr(R, grads[i], 4, names[i])) return rc;
         }
+        for (int i = 0; i < n_running; ++i) {
+            if (!running[i]) return fail(AR_E_INVALID, "null running statistic");
+            if (int rc = rows_check_device_ptr(R, running[i], 4, "running statistic")) return rc;
+        }
+        if (out) {
+            float* const os[5] = {out->losses, out->logits_p1, out->logits_p2, out->value_p1, out->value_p2};
+            for (float* q : os)
+                if (q)
+                    if (int rc = rows_check_device_ptr(R, q, 4, "output")) return rc;
+        }
+        n = (int)n64;
+        H = (int)H_;
+        tc = train_cols(n, H);
+        head_blocks = (n + TRAIN_HEAD_ROWS - 1) / TRAIN_HEAD_ROWS;
+        return AR_OK;
     }
-    if (out) {
-        float* const os[5] = {out->losses, out->logits_p1, out->logits_p2, out->value_p1, out->value_p2};
-        for (float* q : os)
-            if (q)
-                if (int rc = rows_check_device_ptr(R, q, 4, "output")) return rc;
-    }
-    const int n = (int)n64, D = (int)rows_obs_dim(R.hw), Hi = (int)H;
-    // fixed partitions: of the rows for the column sums, of the batch for the products reduced over it
-    TrainCols tc;
-    tc.n = n;
-    tc.H = Hi;
-    tc.P = std::min<int>(TRAIN_MAX_PARTS, (n + 63) / 64);
-    tc.rpp = (n + tc.P - 1) / tc.P;
-    tc.P = (n + tc.rpp - 1) / tc.rpp;
-    int S = std::min<int>(TRAIN_MAX_SPLITS, (n + 255) / 256);
-    const int kps = ((n + S - 1) / S + TG_KC - 1) / TG_KC * TG_KC;
-    S = (n + kps - 1) / kps;
-    const int head_blocks = (n + TRAIN_HEAD_ROWS - 1) / TRAIN_HEAD_ROWS;
+
     // the workspace: offsets into one allocation, every array 256-byte aligned
-    size_t total = 0;
-    auto take = [&](size_t bytes) {
+    size_t take(size_t bytes) {
         const size_t at = total;
         total += (bytes + 255) & ~(size_t)255;
         return at;
-    };
-    const size_t nH = (size_t)n * H * 4;
-    const size_t o_x = take((size_t)n * D * 4), o_t1 = take((size_t)n * 20), o_t2 = take((size_t)n * 20), o_y1 = take((size_t)n * 4),
-                 o_y2 = take((size_t)n * 4), o_a1 = take(n), o_a2 = take(n), o_co = take((size_t)n * R.hw), o_z1 = take(nH),
-                 o_act1 = take(nH), o_z2 = take(nH), o_act2 = take(nH), o_dout = take((size_t)n * 48), o_dz2 = take(nH),
-                 o_dz1 = take(nH), o_parts = take((size_t)6 * TRAIN_MAX_PARTS * H * 8), o_mean = take((size_t)2 * H * 8), o_rstd = take((size_t)2 * H * 4),
-                 o_wpart = take((size_t)S * H * std::max(D, Hi) * 4), o_bpart = take((size_t)S * H * 4),
-                 o_lpart = take((size_t)head_blocks * 32), o_loss = take(6 * 4);
-    int before = 0;
-    HIP_TRY(hipGetDevice(&before));  // the caller's framework keeps its own current device
-    if (before != R.device) HIP_TRY(hipSetDevice(R.device));
-    if (total > R.train_ws_bytes) {
-        hipError_t e = R.wait_batches();  // a pending step may still use the old workspace
-        if (e == hipSuccess) e = regrow(R.train_ws, total);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            R.train_ws_bytes = 0;
-            if (before != R.device) (void)hipSetDevice(before);
-            return fail(AR_E_NOMEM, "not enough device memory for a training workspace of " + std::to_string(total) + " bytes");
-        }
-        R.train_ws_bytes = total;
     }
-    uint8_t* ws = R.train_ws.p;
-    auto F = [&](size_t at) { return (float*)(ws + at); };
-    float *X = F(o_x), *Z1 = F(o_z1), *A1 = F(o_act1), *Z2 = F(o_z2), *A2 = F(o_act2), *dOut = F(o_dout), *dZ2 = F(o_dz2),
-          *dZ1 = F(o_dz1), *rstds = F(o_rstd), *wpart = F(o_wpart), *bpart = F(o_bpart);
-    double *parts = (double*)(ws + o_parts), *means = (double*)(ws + o_mean);
-    auto part = [&](int i) { return parts + (size_t)i * TRAIN_MAX_PARTS * H; };
-    hipError_t err = hipSuccess;
-    // the workspace is shared by every step of this set: a step on another stream starts behind the last one
-    if (R.has_batch) err = hipStreamWaitEvent(stream, R.ev_batch, 0);
-    auto launched = [&]() {
+    void take_rows() {
+        const size_t N = (size_t)n, bytes[8] = {N * rows_obs_dim(R.hw) * 4, N * 20, N * 20, N * 4, N * 4, N, N, N * R.hw};
+        for (int i = 0; i < 8; ++i) o_rows[i] = take(bytes[i]);
+    }
+    void take_losses() {
+        o_lpart = take((size_t)head_blocks * 32);
+        o_loss = take(6 * 4);
+    }
+    float* f(size_t at) const { return (float*)(ws + at); }
+    double* d(size_t at) const { return (double*)(ws + at); }
+
+    // the set's device current, `total` bytes of workspace behind `ws`, the stream behind the last batch or step
+    int begin() {
+        HIP_TRY(hipGetDevice(&before));
+        if (before != R.device) HIP_TRY(hipSetDevice(R.device));
+        if (total > R.train_ws_bytes) {
+            hipError_t e = R.wait_batches();
+            if (e == hipSuccess) e = regrow(R.train_ws, total);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                R.train_ws_bytes = 0;
+                if (before != R.device) (void)hipSetDevice(before);
+                return fail(AR_E_NOMEM, "not enough device memory for a training workspace of " + std::to_string(total) + " bytes");
+            }
+            R.train_ws_bytes = total;
+        }
+        ws = R.train_ws.p;
+        if (R.has_batch) err = hipStreamWaitEvent(stream, R.ev_batch, 0);
+        return AR_OK;
+    }
+    bool ok() const { return err == hipSuccess; }
+    void launched() {
         if (err == hipSuccess) err = hipGetLastError();
-    };
-    RowOut ro;
-    ro.observation = X;
-    ro.policy_p1 = F(o_t1);
-    ro.policy_p2 = F(o_t2);
-    ro.value_p1 = F(o_y1);
-    ro.value_p2 = F(o_y2);
-    ro.action_p1 = (int8_t*)(ws + o_a1);
-    ro.action_p2 = (int8_t*)(ws + o_a2);
-    ro.cheese_outcomes = (int8_t*)(ws + o_co);
-    if (err == hipSuccess) {
+    }
+    int end() {
+        if (err == hipSuccess) {
+            err = hipEventRecord(R.ev_batch, stream);
+            R.has_batch = true;
+        }
+        if (before != R.device) (void)hipSetDevice(before);
+        HIP_TRY(err);
+        return AR_OK;
+    }
+    static dim3 blocks(size_t count) { return dim3((unsigned)((count + 255) / 256)); }
+    dim3 cgrid() const { return dim3((H + 63) / 64, tc.P); }
+
+    // X and the targets of the window, by the row routine the batches use
+    template <int NW>
+    void rows(uint64_t first) {
+        ro.observation = f(o_rows[0]);
+        ro.policy_p1 = f(o_rows[1]);
+        ro.policy_p2 = f(o_rows[2]);
+        ro.value_p1 = f(o_rows[3]);
+        ro.value_p2 = f(o_rows[4]);
+        ro.action_p1 = (int8_t*)(ws + o_rows[5]);
+        ro.action_p2 = (int8_t*)(ws + o_rows[6]);
+        ro.cheese_outcomes = (int8_t*)(ws + o_rows[7]);
+        if (err != hipSuccess) return;
         hipLaunchKernelGGL(k_rows_batch<NW>, dim3((n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(ROWS_PER_BLOCK * ROWS_LANES), 0,
                            stream, (const PosRec<NW>*)R.recs.p, (const uint32_t*)R.pos_game.p, (const RowGame*)R.games.p,
                            (const uint8_t*)R.mazes.p, (const uint8_t*)R.outcomes.p, (const uint64_t*)R.ord_rows.p,
@@ -3340,8 +3363,8 @@ int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const A
         launched();
     }
     // C[M][N] = sum_k A(m, k) B(k, n)
-    auto gemm = [&](const float* a, long sam, long sak, int a_kfast, const float* b, long sbk, long sbn, int b_kfast, float* c, int M,
-                    int N, int K, const float* bias, int splits, int k_per_split, float* colsum) {
+    void gemm(const float* a, long sam, long sak, int a_kfast, const float* b, long sbk, long sbn, int b_kfast, float* c, int M,
+              int N, int K, const float* bias, int splits, int k_per_split, float* colsum) {
         if (err != hipSuccess) return;
         TrainGemm t;
         t.a = a;
@@ -3364,76 +3387,143 @@ int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const A
         hipLaunchKernelGGL(k_train_gemm, dim3((N + TG_TILE - 1) / TG_TILE, (M + TG_TILE - 1) / TG_TILE, splits), dim3(TG_THREADS), 0,
                            stream, t);
         launched();
+    }
+    // Z[rows][H] = In[rows][K] W[H][K]^T + b
+    void linear(const float* in, int rows, int K, const float* w, const float* b, float* z) {
+        gemm(in, K, 1, 1, w, 1, K, 1, z, rows, H, K, b, 1, K, nullptr);
+    }
+    // dIn[rows][N] = d[rows][H] W[H][N]
+    void grad_in(const float* d, int rows, const float* w, int N, float* din) {
+        gemm(d, H, 1, 1, w, N, 1, 0, din, rows, N, H, nullptr, 1, H, nullptr);
+    }
+    // dW[M][N] = d[rows][M]^T In[rows][N] and db = colsum(d): per row range of `sp`, then the ranges added in order into up
+    // to three destinations, consecutive segments of dW's rows (the MLP's three heads; one segment otherwise)
+    struct Seg {
+        float *w, *b;
+        int rows;
     };
-    // dW = dOut^T In and db = colsum(dOut) over the batch: per row range, then the ranges in order
-    auto grad_w = [&](const float* d, int M, const float* in, int N, float* w0, float* b0, int r0, float* w1, float* b1, int r1,
-                      float* w2, float* b2, int r2) {
-        gemm(d, 1, M, 0, in, N, 1, 0, wpart, M, N, n, nullptr, S, kps, bpart);
+    void grad_w(const float* d, int M, const float* in, int N, int rows, TrainSplit sp, Seg s0, Seg s1 = {nullptr, nullptr, 0},
+                Seg s2 = {nullptr, nullptr, 0}) {
+        gemm(d, 1, M, 0, in, N, 1, 0, wpart, M, N, rows, nullptr, sp.S, sp.kps, bpart);
         if (err != hipSuccess) return;
         TrainReduce t;
         t.wpart = wpart;
         t.bpart = bpart;
-        t.S = S;
+        t.S = sp.S;
         t.M = M;
         t.N = N;
-        t.w[0] = w0, t.w[1] = w1, t.w[2] = w2;
-        t.b[0] = b0, t.b[1] = b1, t.b[2] = b2;
-        t.rows[0] = r0, t.rows[1] = r1, t.rows[2] = r2;
-        const size_t count = (size_t)M * N + M;
-        hipLaunchKernelGGL(k_train_reduce, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, t);
+        t.w[0] = s0.w, t.w[1] = s1.w, t.w[2] = s2.w;
+        t.b[0] = s0.b, t.b[1] = s1.b, t.b[2] = s2.b;
+        t.rows[0] = s0.rows, t.rows[1] = s1.rows, t.rows[2] = s2.rows;
+        hipLaunchKernelGGL(k_train_reduce, blocks((size_t)M * N + M), dim3(256), 0, stream, t);
         launched();
-    };
-    const dim3 cgrid((H + 63) / 64, tc.P);
-    // z -> relu(bn(z)) with the batch's statistics (two passes over z), layer 0 / 1
-    auto bn_forward = [&](int layer, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
+    }
+    // act = relu(bn(z)) over n rows at z with the batch's statistics (two passes over z); mu and rstd kept for the backward
+    void bn_forward(const float* z, const float* gamma, const float* beta, float* act, double* mu, float* rstd, float* run_mean,
+                    float* run_var, double* part_sum, double* part_sq) {
         if (err != hipSuccess) return;
         TrainColArgs a;
         memset(&a, 0, sizeof a);
         a.z = z;
-        a.part0 = part(2 * layer);
-        hipLaunchKernelGGL(k_train_colsum<TC_SUM>, cgrid, dim3(256), 0, stream, tc, a);
-        a.sum_in = part(2 * layer);
-        a.part0 = part(2 * layer + 1);
-        hipLaunchKernelGGL(k_train_colsum<TC_SQ>, cgrid, dim3(256), 0, stream, tc, a);
-        hipLaunchKernelGGL(k_train_bn_apply, cgrid, dim3(256), 0, stream, tc, z, (const double*)part(2 * layer),
-                           (const double*)part(2 * layer + 1), gamma, beta, act, means + (size_t)layer * H,
-                           rstds + (size_t)layer * H, rm, rv);
+        a.part0 = part_sum;
+        hipLaunchKernelGGL(k_train_colsum<TC_SUM>, cgrid(), dim3(256), 0, stream, tc, a);
+        a.sum_in = part_sum;
+        a.part0 = part_sq;
+        hipLaunchKernelGGL(k_train_colsum<TC_SQ>, cgrid(), dim3(256), 0, stream, tc, a);
+        hipLaunchKernelGGL(k_train_bn_apply, cgrid(), dim3(256), 0, stream, tc, z, (const double*)part_sum, (const double*)part_sq,
+                           gamma, beta, act, mu, rstd, run_mean, run_var);
         launched();
-    };
-    auto bn_backward = [&](int layer, bool head, const float* z, const float* act, float* d, const float* gamma, float* dgamma,
-                           float* dbeta) {
-        if (err != hipSuccess) return;
+    }
+    // the backward of one BatchNorm call: a column kernel leaves the masked dy in a.d and its two column sums in a.part0,
+    // a.part1 (bn_backward_trunk: from dA already in a.d; a head's own kernel is its driver's), then bn_bwd puts dz there
+    static TrainColArgs backward_args(const float* z, const float* act, float* d, const double* mu, const float* rstd,
+                                      double* part0, double* part1) {
         TrainColArgs a;
         memset(&a, 0, sizeof a);
         a.z = z;
         a.act = act;
         a.d = d;
+        a.mu = mu;
+        a.rstd = rstd;
+        a.part0 = part0;
+        a.part1 = part1;
+        return a;
+    }
+    void bn_bwd(const float* z, float* d, const double* part0, const double* part1, const double* mu, const float* rstd,
+                const float* gamma, float* dgamma, float* dbeta) {
+        hipLaunchKernelGGL(k_train_bn_bwd, cgrid(), dim3(256), 0, stream, tc, z, d, part0, part1, mu, rstd, gamma, dgamma, dbeta);
+        launched();
+    }
+    void bn_backward_trunk(const TrainColArgs& a, const float* gamma, float* dgamma, float* dbeta) {
+        if (err != hipSuccess) return;
+        hipLaunchKernelGGL(k_train_colsum<TC_DTRUNK>, cgrid(), dim3(256), 0, stream, tc, a);
+        bn_bwd(a.z, a.d, a.part0, a.part1, a.mu, a.rstd, gamma, dgamma, dbeta);
+    }
+    // the six losses from the heads' partial sums (called behind the driver's heads launch)
+    void loss_sum(float pw, float vw, const ArTrainOut* out) {
+        hipLaunchKernelGGL(k_train_loss_sum, dim3(1), dim3(256), 0, stream, (const double*)d(o_lpart), (uint32_t)head_blocks,
+                           (uint32_t)n, pw, vw, f(o_loss), out ? out->losses : nullptr);
+        launched();
+    }
+};
+
+// ar_rows_grad_mlp: the loss and the gradients of PyRatMLP over rows first .. first + n of the order, on the caller's
+// stream: train_mlp.h's chain, under TrainStep's rules.
+template <int NW>
+int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const ArMlpTensors& p, const ArMlpTensors& g,
+                  const ArMlpBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream) {
+    static_assert(sizeof(ArMlpTensors) == 14 * sizeof(float*), "fourteen pointers");
+    static_assert(sizeof(ArMlpBnStats) == 4 * sizeof(float*), "four pointers");
+    TrainStep T{R, stream};
+    if (int rc = T.check(first, n64, H, kMlpTensorNames, (float* const*)&p, (float* const*)&g, 14, (float* const*)run, run ? 4 : 0, out))
+        return rc;
+    const int n = T.n, D = (int)rows_obs_dim(R.hw), Hi = T.H;
+    const TrainSplit sp = train_split(n);
+    const size_t nH = (size_t)n * H * 4;
+    T.take_rows();
+    const size_t o_z1 = T.take(nH), o_act1 = T.take(nH), o_z2 = T.take(nH), o_act2 = T.take(nH), o_dout = T.take((size_t)n * 48),
+                 o_dz2 = T.take(nH), o_dz1 = T.take(nH), o_parts = T.take((size_t)6 * TRAIN_MAX_PARTS * H * 8),
+                 o_mean = T.take((size_t)2 * H * 8), o_rstd = T.take((size_t)2 * H * 4),
+                 o_wpart = T.take((size_t)sp.S * H * std::max(D, Hi) * 4), o_bpart = T.take((size_t)sp.S * H * 4);
+    T.take_losses();
+    if (int rc = T.begin()) return rc;
+    float *Z1 = T.f(o_z1), *A1 = T.f(o_act1), *Z2 = T.f(o_z2), *A2 = T.f(o_act2), *dOut = T.f(o_dout), *dZ2 = T.f(o_dz2),
+          *dZ1 = T.f(o_dz1), *rstds = T.f(o_rstd);
+    double *parts = T.d(o_parts), *means = T.d(o_mean);
+    T.wpart = T.f(o_wpart);
+    T.bpart = T.f(o_bpart);
+    auto part = [&](int i) { return parts + (size_t)i * TRAIN_MAX_PARTS * H; };
+    // z -> relu(bn(z)), layer 0 / 1
+    auto bn_forward = [&](int layer, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
+        T.bn_forward(z, gamma, beta, act, means + (size_t)layer * H, rstds + (size_t)layer * H, rm, rv, part(2 * layer),
+                     part(2 * layer + 1));
+    };
+    auto bn_backward = [&](int layer, bool head, const float* z, const float* act, float* d, const float* gamma, float* dgamma,
+                           float* dbeta) {
+        if (!T.ok()) return;
+        TrainColArgs a = TrainStep::backward_args(z, act, d, means + (size_t)layer * H, rstds + (size_t)layer * H, part(4), part(5));
         a.dout = dOut;
         a.w_p1 = p.p1_w;
         a.w_p2 = p.p2_w;
         a.w_v = p.value_w;
-        a.mu = means + (size_t)layer * H;
-        a.rstd = rstds + (size_t)layer * H;
-        a.part0 = part(4);
-        a.part1 = part(5);
-        if (head) hipLaunchKernelGGL(k_train_colsum<TC_DHEAD>, cgrid, dim3(256), 0, stream, tc, a);
-        else hipLaunchKernelGGL(k_train_colsum<TC_DTRUNK>, cgrid, dim3(256), 0, stream, tc, a);
-        hipLaunchKernelGGL(k_train_bn_bwd, cgrid, dim3(256), 0, stream, tc, z, d, (const double*)part(4), (const double*)part(5),
-                           a.mu, a.rstd, gamma, dgamma, dbeta);
-        launched();
+        if (!head) return T.bn_backward_trunk(a, gamma, dgamma, dbeta);
+        hipLaunchKernelGGL(k_train_colsum<TC_DHEAD>, T.cgrid(), dim3(256), 0, stream, T.tc, a);
+        T.bn_bwd(z, d, part(4), part(5), a.mu, a.rstd, gamma, dgamma, dbeta);
     };
+    const float* X = T.f(T.o_rows[0]);
+    T.rows<NW>(first);
     // forward
-    gemm(X, D, 1, 1, p.trunk0_w, 1, D, 1, Z1, n, Hi, D, p.trunk0_b, 1, D, nullptr);
+    T.linear(X, n, D, p.trunk0_w, p.trunk0_b, Z1);
     bn_forward(0, Z1, p.bn1_w, p.bn1_b, A1, run ? run->mean1 : nullptr, run ? run->var1 : nullptr);
-    gemm(A1, Hi, 1, 1, p.trunk4_w, 1, Hi, 1, Z2, n, Hi, Hi, p.trunk4_b, 1, Hi, nullptr);
+    T.linear(A1, n, Hi, p.trunk4_w, p.trunk4_b, Z2);
     bn_forward(1, Z2, p.bn2_w, p.bn2_b, A2, run ? run->mean2 : nullptr, run ? run->var2 : nullptr);
-    if (err == hipSuccess) {
+    if (T.ok()) {
         TrainHeads t;
         t.act = A2;
         t.w_p1 = p.p1_w, t.b_p1 = p.p1_b, t.w_p2 = p.p2_w, t.b_p2 = p.p2_b, t.w_v = p.value_w, t.b_v = p.value_b;
-        t.t1 = ro.policy_p1, t.t2 = ro.policy_p2, t.y1 = ro.value_p1, t.y2 = ro.value_p2;
+        t.t1 = T.ro.policy_p1, t.t2 = T.ro.policy_p2, t.y1 = T.ro.value_p1, t.y2 = T.ro.value_p2;
         t.dout = dOut;
-        t.loss_part = (double*)(ws + o_lpart);
+        t.loss_part = T.d(T.o_lpart);
         t.logits_p1 = out ? out->logits_p1 : nullptr;
         t.logits_p2 = out ? out->logits_p2 : nullptr;
         t.value_p1 = out ? out->value_p1 : nullptr;
@@ -3442,212 +3532,57 @@ int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const A
         t.H = Hi;
         t.pw_n = pw / (float)n;
         t.vw_n = vw / (float)n;
-        hipLaunchKernelGGL(k_train_heads, dim3(head_blocks), dim3(256), (size_t)12 * H * 4, stream, t);
-        hipLaunchKernelGGL(k_train_loss_sum, dim3(1), dim3(256), 0, stream, (const double*)(ws + o_lpart), (uint32_t)head_blocks,
-                           (uint32_t)n, pw, vw, F(o_loss), out ? out->losses : nullptr);
-        launched();
+        hipLaunchKernelGGL(k_train_heads, dim3(T.head_blocks), dim3(256), (size_t)12 * H * 4, stream, t);
+        T.loss_sum(pw, vw, out);
     }
     // backward
-    grad_w(dOut, 12, A2, Hi, g.p1_w, g.p1_b, 5, g.p2_w, g.p2_b, 5, g.value_w, g.value_b, 2);
+    T.grad_w(dOut, 12, A2, Hi, n, sp, {g.p1_w, g.p1_b, 5}, {g.p2_w, g.p2_b, 5}, {g.value_w, g.value_b, 2});
     bn_backward(1, true, Z2, A2, dZ2, p.bn2_w, g.bn2_w, g.bn2_b);
-    grad_w(dZ2, Hi, A1, Hi, g.trunk4_w, g.trunk4_b, Hi, nullptr, nullptr, 0, nullptr, nullptr, 0);
-    gemm(dZ2, Hi, 1, 1, p.trunk4_w, Hi, 1, 0, dZ1, n, Hi, Hi, nullptr, 1, Hi, nullptr);
+    T.grad_w(dZ2, Hi, A1, Hi, n, sp, {g.trunk4_w, g.trunk4_b, Hi});
+    T.grad_in(dZ2, n, p.trunk4_w, Hi, dZ1);
     bn_backward(0, false, Z1, A1, dZ1, p.bn1_w, g.bn1_w, g.bn1_b);
-    grad_w(dZ1, Hi, X, D, g.trunk0_w, g.trunk0_b, Hi, nullptr, nullptr, 0, nullptr, nullptr, 0);
-    if (err == hipSuccess) {
-        err = hipEventRecord(R.ev_batch, stream);
-        R.has_batch = true;
-    }
-    if (before != R.device) (void)hipSetDevice(before);
-    HIP_TRY(err);
-    return AR_OK;
+    T.grad_w(dZ1, Hi, X, D, n, sp, {g.trunk0_w, g.trunk0_b, Hi});
+    return T.end();
 }
 
-// ar_rows_grad_symmetric: the loss and the gradients of SymmetricMLP over rows first .. first + n of the order (train_sym.h
-// lists the chain), under the rules of rows_grad_mlp: everything checked before the first launch, the set's one workspace
-// grown after waiting for what may still use the old one, ev_batch behind the last launch. P1's and P2's rows are stacked:
-// an array of [2n] rows holds P1's n, then P2's.
-static const char* const kSymTensorNames[20] = {"se0_w",    "se0_b",    "se1_w",  "se1_b",  "pe0_w",    "pe0_b",    "pe1_w",
-                                                "pe1_b",    "trunk0_w", "trunk0_b", "bn1_w", "bn1_b",    "trunk4_w", "trunk4_b",
-                                                "bn2_w",    "bn2_b",    "policy_w", "policy_b", "value_w", "value_b"};
+// ar_rows_grad_symmetric: the loss and the gradients of SymmetricMLP over rows first .. first + n of the order, on the
+// caller's stream: train_sym.h's chain, under TrainStep's rules. P1's and P2's rows are stacked: an array of [2n] rows holds
+// P1's n, then P2's.
 template <int NW>
 int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const ArSymTensors& p, const ArSymTensors& g,
                         const ArSymBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream) {
-    if (!R.has_order) return fail(AR_E_INVALID, "the row set has no order: ar_rows_order_set comes first");
-    if (first > R.ord_n || n64 > R.ord_n - first)
-        return fail(AR_E_INVALID, "rows " + std::to_string(first) + " + " + std::to_string(n64) + " go beyond the order of " +
-                                      std::to_string(R.ord_n));
-    if (n64 < 2) return fail(AR_E_INVALID, "a training BatchNorm needs at least two rows");
-    if (n64 > (uint64_t)TRAIN_MAX_ROWS) return fail(AR_E_INVALID, "at most 65536 rows a step");
-    if (H == 0 || H % 32 != 0 || H > 256)
-        return fail(AR_E_INVALID, "hidden_dim must be a multiple of 32, at most 256 (got " + std::to_string(H) + ")");
     static_assert(sizeof(ArSymTensors) == 20 * sizeof(float*), "twenty pointers");
     static_assert(sizeof(ArSymBnStats) == 8 * sizeof(float*), "eight pointers");
-    float* const* pp = (float* const*)&p;
-    float* const* gp = (float* const*)&g;
-    for (int i = 0; i < 20; ++i) {
-        if (!pp[i] || !gp[i]) return fail(AR_E_INVALID, std::string("null tensor: ") + kSymTensorNames[i]);
-        if (int rc = rows_check_device_ptr(R, pp[i], 4, kSymTensorNames[i])) return rc;
-        if (int rc = rows_check_device_ptr(R, gp[i], 4, kSymTensorNames[i])) return rc;
-    }
-    if (run) {
-        float* const* rs = (float* const*)run;
-        for (int i = 0; i < 8; ++i) {
-            if (!rs[i]) return fail(AR_E_INVALID, "null running statistic");
-            if (int rc = rows_check_device_ptr(R, rs[i], 4, "running statistic")) return rc;
-        }
-    }
-    if (out) {
-        float* const os[5] = {out->losses, out->logits_p1, out->logits_p2, out->value_p1, out->value_p2};
-        for (float* q : os)
-            if (q)
-                if (int rc = rows_check_device_ptr(R, q, 4, "output")) return rc;
-    }
-    const int n = (int)n64, n2 = 2 * n, hw = (int)R.hw, D = (int)rows_obs_dim(R.hw), Hi = (int)H, H2 = 2 * Hi;
+    float* const* rs = (float* const*)run;  // se mean, var; pe; trunk.1; trunk.5
+    TrainStep T{R, stream};
+    if (int rc = T.check(first, n64, H, kSymTensorNames, (float* const*)&p, (float* const*)&g, 20, rs, run ? 8 : 0, out)) return rc;
+    const int n = T.n, n2 = 2 * n, hw = (int)R.hw, Hi = T.H, H2 = 2 * Hi;
     const int Ds = sym_shared_dim(hw), Dp = sym_player_dim(hw);
-    // fixed partitions: of a BatchNorm call's n rows for the column sums; of the n or 2n rows a product is reduced over
-    TrainCols tc;
-    tc.n = n;
-    tc.H = Hi;
-    tc.P = std::min<int>(TRAIN_MAX_PARTS, (n + 63) / 64);
-    tc.rpp = (n + tc.P - 1) / tc.P;
-    tc.P = (n + tc.rpp - 1) / tc.rpp;
-    struct Split { int S, kps; };
-    auto split_of = [](int rows) {
-        Split s;
-        s.S = std::min<int>(TRAIN_MAX_SPLITS, (rows + 255) / 256);
-        s.kps = ((rows + s.S - 1) / s.S + TG_KC - 1) / TG_KC * TG_KC;
-        s.S = (rows + s.kps - 1) / s.kps;
-        return s;
-    };
-    const Split sp1 = split_of(n), sp2 = split_of(n2);
-    const int head_blocks = (n + TRAIN_HEAD_ROWS - 1) / TRAIN_HEAD_ROWS;
-    // the workspace: offsets into one allocation, every array 256-byte aligned
-    size_t total = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    // a product is reduced over the n rows of the shared encoder or the 2n of everything else
+    const TrainSplit sp1 = train_split(n), sp2 = train_split(n2);
     const size_t nH = (size_t)n * H * 4;
-    const size_t o_x = take((size_t)n * D * 4), o_t1 = take((size_t)n * 20), o_t2 = take((size_t)n * 20), o_y1 = take((size_t)n * 4),
-                 o_y2 = take((size_t)n * 4), o_a1 = take(n), o_a2 = take(n), o_co = take((size_t)n * R.hw),
-                 o_xs = take((size_t)n * Ds * 4), o_xp = take((size_t)n2 * Dp * 4), o_zs = take(nH), o_as = take(nH),
-                 o_zp = take(2 * nH), o_ap = take(2 * nH), o_cat = take(4 * nH), o_zt0 = take(2 * nH), o_at0 = take(2 * nH),
-                 o_zt4 = take(2 * nH), o_at4 = take(2 * nH), o_d12 = take((size_t)n2 * 48), o_dt4 = take(2 * nH),
-                 o_dt0 = take(2 * nH), o_dcat = take(4 * nH), o_dp = take(2 * nH), o_ds = take(nH),
-                 o_parts = take((size_t)6 * TRAIN_MAX_PARTS * H * 8), o_mean = take((size_t)7 * H * 8), o_rstd = take((size_t)7 * H * 4),
-                 o_wpart = take((size_t)sp2.S * H * std::max(std::max(Ds, Dp), H2) * 4),
-                 o_bpart = take((size_t)sp2.S * H * 4), o_lpart = take((size_t)head_blocks * 32), o_loss = take(6 * 4),
-                 o_bnscr = take((size_t)2 * H * 4);
-    int before = 0;
-    HIP_TRY(hipGetDevice(&before));  // the caller's framework keeps its own current device
-    if (before != R.device) HIP_TRY(hipSetDevice(R.device));
-    if (total > R.train_ws_bytes) {
-        hipError_t e = R.wait_batches();  // a pending step may still use the old workspace
-        if (e == hipSuccess) e = regrow(R.train_ws, total);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            R.train_ws_bytes = 0;
-            if (before != R.device) (void)hipSetDevice(before);
-            return fail(AR_E_NOMEM, "not enough device memory for a training workspace of " + std::to_string(total) + " bytes");
-        }
-        R.train_ws_bytes = total;
-    }
-    uint8_t* ws = R.train_ws.p;
-    auto F = [&](size_t at) { return (float*)(ws + at); };
-    float *X = F(o_x), *Xs = F(o_xs), *Xp = F(o_xp), *Zs = F(o_zs), *As = F(o_as), *Zp = F(o_zp), *Ap = F(o_ap), *Cat = F(o_cat),
-          *Zt0 = F(o_zt0), *At0 = F(o_at0), *Zt4 = F(o_zt4), *At4 = F(o_at4), *D12 = F(o_d12), *dT4 = F(o_dt4), *dT0 = F(o_dt0),
-          *dCat = F(o_dcat), *dP = F(o_dp), *dS = F(o_ds), *rstds = F(o_rstd), *wpart = F(o_wpart), *bpart = F(o_bpart),
-          *bnscr = F(o_bnscr);
-    double *parts = (double*)(ws + o_parts), *means = (double*)(ws + o_mean);
+    T.take_rows();
+    const size_t o_xs = T.take((size_t)n * Ds * 4), o_xp = T.take((size_t)n2 * Dp * 4), o_zs = T.take(nH), o_as = T.take(nH),
+                 o_zp = T.take(2 * nH), o_ap = T.take(2 * nH), o_cat = T.take(4 * nH), o_zt0 = T.take(2 * nH),
+                 o_at0 = T.take(2 * nH), o_zt4 = T.take(2 * nH), o_at4 = T.take(2 * nH), o_d12 = T.take((size_t)n2 * 48),
+                 o_dt4 = T.take(2 * nH), o_dt0 = T.take(2 * nH), o_dcat = T.take(4 * nH), o_dp = T.take(2 * nH), o_ds = T.take(nH),
+                 o_parts = T.take((size_t)6 * TRAIN_MAX_PARTS * H * 8), o_mean = T.take((size_t)7 * H * 8),
+                 o_rstd = T.take((size_t)7 * H * 4), o_wpart = T.take((size_t)sp2.S * H * std::max(std::max(Ds, Dp), H2) * 4),
+                 o_bpart = T.take((size_t)sp2.S * H * 4);
+    T.take_losses();
+    const size_t o_bnscr = T.take((size_t)2 * H * 4);
+    if (int rc = T.begin()) return rc;
+    float *Xs = T.f(o_xs), *Xp = T.f(o_xp), *Zs = T.f(o_zs), *As = T.f(o_as), *Zp = T.f(o_zp), *Ap = T.f(o_ap), *Cat = T.f(o_cat),
+          *Zt0 = T.f(o_zt0), *At0 = T.f(o_at0), *Zt4 = T.f(o_zt4), *At4 = T.f(o_at4), *D12 = T.f(o_d12), *dT4 = T.f(o_dt4),
+          *dT0 = T.f(o_dt0), *dCat = T.f(o_dcat), *dP = T.f(o_dp), *dS = T.f(o_ds), *rstds = T.f(o_rstd), *bnscr = T.f(o_bnscr);
+    double *parts = T.d(o_parts), *means = T.d(o_mean);
+    T.wpart = T.f(o_wpart);
+    T.bpart = T.f(o_bpart);
     auto part = [&](int i) { return parts + (size_t)i * TRAIN_MAX_PARTS * H; };
     const size_t half = (size_t)n * H;  // P2's rows of a [2n][H] array
-    hipError_t err = hipSuccess;
-    // the workspace is shared by every step of this set: a step on another stream starts behind the last one
-    if (R.has_batch) err = hipStreamWaitEvent(stream, R.ev_batch, 0);
-    auto launched = [&]() {
-        if (err == hipSuccess) err = hipGetLastError();
-    };
-    auto blocks = [](size_t count) { return dim3((unsigned)((count + 255) / 256)); };
-    RowOut ro;
-    ro.observation = X;
-    ro.policy_p1 = F(o_t1);
-    ro.policy_p2 = F(o_t2);
-    ro.value_p1 = F(o_y1);
-    ro.value_p2 = F(o_y2);
-    ro.action_p1 = (int8_t*)(ws + o_a1);
-    ro.action_p2 = (int8_t*)(ws + o_a2);
-    ro.cheese_outcomes = (int8_t*)(ws + o_co);
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(k_rows_batch<NW>, dim3((n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(ROWS_PER_BLOCK * ROWS_LANES), 0,
-                           stream, (const PosRec<NW>*)R.recs.p, (const uint32_t*)R.pos_game.p, (const RowGame*)R.games.p,
-                           (const uint8_t*)R.mazes.p, (const uint8_t*)R.outcomes.p, (const uint64_t*)R.ord_rows.p,
-                           (const uint8_t*)R.ord_swap.p, first, (uint64_t)0, (uint32_t)n, ro);
-        hipLaunchKernelGGL(k_sym_split, blocks((size_t)n * (Ds + 2 * Dp)), dim3(256), 0, stream, (const float*)X, Xs, Xp, n, hw);
-        launched();
-    }
-    // C[M][N] = sum_k A(m, k) B(k, n)
-    auto gemm = [&](const float* a, long sam, long sak, int a_kfast, const float* b, long sbk, long sbn, int b_kfast, float* c, int M,
-                    int N, int K, const float* bias, int splits, int k_per_split, float* colsum) {
-        if (err != hipSuccess) return;
-        TrainGemm t;
-        t.a = a;
-        t.b = b;
-        t.bias = bias;
-        t.c = c;
-        t.colsum = colsum;
-        t.M = M;
-        t.N = N;
-        t.K = K;
-        t.k_per_split = k_per_split;
-        t.ldc = N;
-        t.sam = sam;
-        t.sak = sak;
-        t.sbk = sbk;
-        t.sbn = sbn;
-        t.c_split = (size_t)M * N;
-        t.a_kfast = a_kfast;
-        t.b_kfast = b_kfast;
-        hipLaunchKernelGGL(k_train_gemm, dim3((N + TG_TILE - 1) / TG_TILE, (M + TG_TILE - 1) / TG_TILE, splits), dim3(TG_THREADS), 0,
-                           stream, t);
-        launched();
-    };
-    // Z[rows][H] = In[rows][K] W[H][K]^T + b
-    auto linear = [&](const float* in, int rows, int K, const float* w, const float* b, float* z) {
-        gemm(in, K, 1, 1, w, 1, K, 1, z, rows, Hi, K, b, 1, K, nullptr);
-    };
-    // dW[H][N] = d[rows][H]^T In[rows][N] and db = colsum(d), per row range, then the ranges in order
-    auto grad_w = [&](const float* d, const float* in, int rows, int N, const Split& sp, float* w, float* b) {
-        gemm(d, 1, Hi, 0, in, N, 1, 0, wpart, Hi, N, rows, nullptr, sp.S, sp.kps, bpart);
-        if (err != hipSuccess) return;
-        TrainReduce t;
-        t.wpart = wpart;
-        t.bpart = bpart;
-        t.S = sp.S;
-        t.M = Hi;
-        t.N = N;
-        t.w[0] = w, t.w[1] = nullptr, t.w[2] = nullptr;
-        t.b[0] = b, t.b[1] = nullptr, t.b[2] = nullptr;
-        t.rows[0] = Hi, t.rows[1] = 0, t.rows[2] = 0;
-        hipLaunchKernelGGL(k_train_reduce, blocks((size_t)Hi * N + Hi), dim3(256), 0, stream, t);
-        launched();
-    };
-    const dim3 cgrid((H + 63) / 64, tc.P);
     // one BatchNorm call (0: shared; 1, 2: player_encoder.1 of P1, P2; 3, 4: trunk.1; 5, 6: trunk.5) over n rows at z
     auto bn_forward = [&](int call, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
-        if (err != hipSuccess) return;
-        TrainColArgs a;
-        memset(&a, 0, sizeof a);
-        a.z = z;
-        a.part0 = part(0);
-        hipLaunchKernelGGL(k_train_colsum<TC_SUM>, cgrid, dim3(256), 0, stream, tc, a);
-        a.sum_in = part(0);
-        a.part0 = part(1);
-        hipLaunchKernelGGL(k_train_colsum<TC_SQ>, cgrid, dim3(256), 0, stream, tc, a);
-        hipLaunchKernelGGL(k_train_bn_apply, cgrid, dim3(256), 0, stream, tc, z, (const double*)part(0), (const double*)part(1),
-                           gamma, beta, act, means + (size_t)call * H, rstds + (size_t)call * H, rm, rv);
-        launched();
+        T.bn_forward(z, gamma, beta, act, means + (size_t)call * H, rstds + (size_t)call * H, rm, rv, part(0), part(1));
     };
     // a module called for both players: P1's call, then P2's on top of it
     auto bn_forward2 = [&](int call, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
@@ -3657,71 +3592,62 @@ int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, c
     // dz in place of d for one call; its column sums stay in part(2 + 2 * slot), part(3 + 2 * slot)
     auto bn_backward = [&](int call, int slot, bool head, const float* z, const float* act, float* d, const float* d12,
                            const float* gamma, float* dgamma, float* dbeta) {
-        if (err != hipSuccess) return;
+        if (!T.ok()) return;
         double *p0 = part(2 + 2 * slot), *p1 = part(3 + 2 * slot);
         const double* mu = means + (size_t)call * H;
         const float* rstd = rstds + (size_t)call * H;
-        if (head) {
-            SymDHead a;
-            a.z = z;
-            a.act = act;
-            a.d = d;
-            a.d12 = d12;
-            a.w_p = p.policy_w;
-            a.w_v = p.value_w;
-            a.mu = mu;
-            a.rstd = rstd;
-            a.part0 = p0;
-            a.part1 = p1;
-            hipLaunchKernelGGL(k_sym_dhead, cgrid, dim3(256), 0, stream, tc, a);
-        } else {
-            TrainColArgs a;
-            memset(&a, 0, sizeof a);
-            a.z = z;
-            a.act = act;
-            a.d = d;
-            a.mu = mu;
-            a.rstd = rstd;
-            a.part0 = p0;
-            a.part1 = p1;
-            hipLaunchKernelGGL(k_train_colsum<TC_DTRUNK>, cgrid, dim3(256), 0, stream, tc, a);
-        }
-        hipLaunchKernelGGL(k_train_bn_bwd, cgrid, dim3(256), 0, stream, tc, z, d, (const double*)p0, (const double*)p1, mu, rstd,
-                           gamma, dgamma, dbeta);
-        launched();
+        if (!head) return T.bn_backward_trunk(TrainStep::backward_args(z, act, d, mu, rstd, p0, p1), gamma, dgamma, dbeta);
+        SymDHead a;
+        a.z = z;
+        a.act = act;
+        a.d = d;
+        a.d12 = d12;
+        a.w_p = p.policy_w;
+        a.w_v = p.value_w;
+        a.mu = mu;
+        a.rstd = rstd;
+        a.part0 = p0;
+        a.part1 = p1;
+        hipLaunchKernelGGL(k_sym_dhead, T.cgrid(), dim3(256), 0, stream, T.tc, a);
+        T.bn_bwd(z, d, p0, p1, mu, rstd, gamma, dgamma, dbeta);
     };
     // both calls of a shared module; the module's two gradients from both calls' column sums (k_train_bn_bwd's own go to bnscr)
     auto bn_backward2 = [&](int call, bool head, const float* z, const float* act, float* d, const float* gamma, float* dgamma,
                             float* dbeta) {
         bn_backward(call, 0, head, z, act, d, D12, gamma, bnscr, bnscr + H);
         bn_backward(call + 1, 1, head, z + half, act + half, d + half, D12 + (size_t)n * 12, gamma, bnscr, bnscr + H);
-        if (err != hipSuccess) return;
-        hipLaunchKernelGGL(k_sym_bn_grad, dim3((H + 255) / 256), dim3(256), 0, stream, tc.P, Hi, (const double*)part(2),
+        if (!T.ok()) return;
+        hipLaunchKernelGGL(k_sym_bn_grad, dim3((H + 255) / 256), dim3(256), 0, stream, T.tc.P, Hi, (const double*)part(2),
                            (const double*)part(3), (const double*)part(4), (const double*)part(5), dgamma, dbeta);
-        launched();
+        T.launched();
     };
-    float* const* rs = (float* const*)run;  // se mean, var; pe; trunk.1; trunk.5
     auto rstat = [&](int i) { return run ? rs[i] : (float*)nullptr; };
-    // forward
-    linear(Xs, n, Ds, p.se0_w, p.se0_b, Zs);
-    bn_forward(0, Zs, p.se1_w, p.se1_b, As, rstat(0), rstat(1));
-    linear(Xp, n2, Dp, p.pe0_w, p.pe0_b, Zp);
-    bn_forward2(1, Zp, p.pe1_w, p.pe1_b, Ap, rstat(2), rstat(3));
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(k_sym_cat, blocks((size_t)4 * n * H), dim3(256), 0, stream, (const float*)As, (const float*)Ap, Cat, n, Hi);
-        launched();
+    T.rows<NW>(first);
+    if (T.ok()) {
+        hipLaunchKernelGGL(k_sym_split, T.blocks((size_t)n * (Ds + 2 * Dp)), dim3(256), 0, stream, (const float*)T.ro.observation, Xs,
+                           Xp, n, hw);
+        T.launched();
     }
-    linear(Cat, n2, H2, p.trunk0_w, p.trunk0_b, Zt0);
+    // forward
+    T.linear(Xs, n, Ds, p.se0_w, p.se0_b, Zs);
+    bn_forward(0, Zs, p.se1_w, p.se1_b, As, rstat(0), rstat(1));
+    T.linear(Xp, n2, Dp, p.pe0_w, p.pe0_b, Zp);
+    bn_forward2(1, Zp, p.pe1_w, p.pe1_b, Ap, rstat(2), rstat(3));
+    if (T.ok()) {
+        hipLaunchKernelGGL(k_sym_cat, T.blocks((size_t)4 * n * H), dim3(256), 0, stream, (const float*)As, (const float*)Ap, Cat, n, Hi);
+        T.launched();
+    }
+    T.linear(Cat, n2, H2, p.trunk0_w, p.trunk0_b, Zt0);
     bn_forward2(3, Zt0, p.bn1_w, p.bn1_b, At0, rstat(4), rstat(5));
-    linear(At0, n2, Hi, p.trunk4_w, p.trunk4_b, Zt4);
+    T.linear(At0, n2, Hi, p.trunk4_w, p.trunk4_b, Zt4);
     bn_forward2(5, Zt4, p.bn2_w, p.bn2_b, At4, rstat(6), rstat(7));
-    if (err == hipSuccess) {
+    if (T.ok()) {
         SymHeads t;
         t.h = At4;
         t.w_p = p.policy_w, t.b_p = p.policy_b, t.w_v = p.value_w, t.b_v = p.value_b;
-        t.t1 = ro.policy_p1, t.t2 = ro.policy_p2, t.y1 = ro.value_p1, t.y2 = ro.value_p2;
+        t.t1 = T.ro.policy_p1, t.t2 = T.ro.policy_p2, t.y1 = T.ro.value_p1, t.y2 = T.ro.value_p2;
         t.d12 = D12;
-        t.loss_part = (double*)(ws + o_lpart);
+        t.loss_part = T.d(T.o_lpart);
         t.logits_p1 = out ? out->logits_p1 : nullptr;
         t.logits_p2 = out ? out->logits_p2 : nullptr;
         t.value_p1 = out ? out->value_p1 : nullptr;
@@ -3730,41 +3656,33 @@ int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, c
         t.H = Hi;
         t.pw_n = pw / (float)n;
         t.vw_n = vw / (float)n;
-        hipLaunchKernelGGL(k_sym_heads, dim3(head_blocks), dim3(256), (size_t)12 * H * 4, stream, t);
-        hipLaunchKernelGGL(k_train_loss_sum, dim3(1), dim3(256), 0, stream, (const double*)(ws + o_lpart), (uint32_t)head_blocks,
-                           (uint32_t)n, pw, vw, F(o_loss), out ? out->losses : nullptr);
-        launched();
+        hipLaunchKernelGGL(k_sym_heads, dim3(T.head_blocks), dim3(256), (size_t)12 * H * 4, stream, t);
+        T.loss_sum(pw, vw, out);
     }
     // backward: the heads
-    gemm(D12, 1, 12, 0, At4, Hi, 1, 0, wpart, 12, Hi, n2, nullptr, sp2.S, sp2.kps, bpart);
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(k_sym_head_reduce, blocks((size_t)12 * H + 6), dim3(256), 0, stream, (const float*)wpart,
-                           (const float*)bpart, sp2.S, Hi, g.policy_w, g.policy_b, g.value_w, g.value_b);
-        launched();
+    T.gemm(D12, 1, 12, 0, At4, Hi, 1, 0, T.wpart, 12, Hi, n2, nullptr, sp2.S, sp2.kps, T.bpart);
+    if (T.ok()) {
+        hipLaunchKernelGGL(k_sym_head_reduce, T.blocks((size_t)12 * H + 6), dim3(256), 0, stream, (const float*)T.wpart,
+                           (const float*)T.bpart, sp2.S, Hi, g.policy_w, g.policy_b, g.value_w, g.value_b);
+        T.launched();
     }
     // the trunk
     bn_backward2(5, true, Zt4, At4, dT4, p.bn2_w, g.bn2_w, g.bn2_b);
-    grad_w(dT4, At0, n2, Hi, sp2, g.trunk4_w, g.trunk4_b);
-    gemm(dT4, Hi, 1, 1, p.trunk4_w, Hi, 1, 0, dT0, n2, Hi, Hi, nullptr, 1, Hi, nullptr);
+    T.grad_w(dT4, Hi, At0, Hi, n2, sp2, {g.trunk4_w, g.trunk4_b, Hi});
+    T.grad_in(dT4, n2, p.trunk4_w, Hi, dT0);
     bn_backward2(3, false, Zt0, At0, dT0, p.bn1_w, g.bn1_w, g.bn1_b);
-    grad_w(dT0, Cat, n2, H2, sp2, g.trunk0_w, g.trunk0_b);
-    gemm(dT0, Hi, 1, 1, p.trunk0_w, H2, 1, 0, dCat, n2, H2, Hi, nullptr, 1, Hi, nullptr);
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(k_sym_uncat, blocks((size_t)2 * n * H), dim3(256), 0, stream, (const float*)dCat, dS, dP, n, Hi);
-        launched();
+    T.grad_w(dT0, Hi, Cat, H2, n2, sp2, {g.trunk0_w, g.trunk0_b, Hi});
+    T.grad_in(dT0, n2, p.trunk0_w, H2, dCat);
+    if (T.ok()) {
+        hipLaunchKernelGGL(k_sym_uncat, T.blocks((size_t)2 * n * H), dim3(256), 0, stream, (const float*)dCat, dS, dP, n, Hi);
+        T.launched();
     }
     // the encoders
     bn_backward2(1, false, Zp, Ap, dP, p.pe1_w, g.pe1_w, g.pe1_b);
-    grad_w(dP, Xp, n2, Dp, sp2, g.pe0_w, g.pe0_b);
+    T.grad_w(dP, Hi, Xp, Dp, n2, sp2, {g.pe0_w, g.pe0_b, Hi});
     bn_backward(0, 0, false, Zs, As, dS, nullptr, p.se1_w, g.se1_w, g.se1_b);
-    grad_w(dS, Xs, n, Ds, sp1, g.se0_w, g.se0_b);
-    if (err == hipSuccess) {
-        err = hipEventRecord(R.ev_batch, stream);
-        R.has_batch = true;
-    }
-    if (before != R.device) (void)hipSetDevice(before);
-    HIP_TRY(err);
-    return AR_OK;
+    T.grad_w(dS, Hi, Xs, Ds, n, sp1, {g.se0_w, g.se0_b, Hi});
+    return T.end();
 }
 
 // ar_rows_validate: the request in chunks of `chunk` rows -- requests from the stored records (k_val_requests), the

@@ -87,4 +87,34 @@ AR_HD TrainHeadTerms train_head_terms(const float* out, const float* t1, const f
     return h;
 }
 
+// The two fixed partitions of a step. They set the order of every sum over the batch, and with it every byte of the
+// gradients: a function of the row count alone, never of the device or the launch.
+enum { TG_KC = 16, TRAIN_MAX_PARTS = 32, TRAIN_MAX_SPLITS = 32 };
+
+// of a BatchNorm call's n rows for the column kernels: P consecutive parts of rpp rows, the last one maybe shorter
+struct TrainCols {
+    int n, H, P, rpp;
+};
+inline TrainCols train_cols(int n, int H) {
+    TrainCols t;
+    t.n = n;
+    t.H = H;
+    t.P = (n + 63) / 64 < TRAIN_MAX_PARTS ? (n + 63) / 64 : TRAIN_MAX_PARTS;
+    t.rpp = (n + t.P - 1) / t.P;
+    t.P = (n + t.rpp - 1) / t.rpp;
+    return t;
+}
+
+// of the rows a product is reduced over (k_train_gemm's blockIdx.z): S ranges of kps rows, kps a multiple of the k chunk
+struct TrainSplit {
+    int S, kps;
+};
+inline TrainSplit train_split(int rows) {
+    TrainSplit s;
+    s.S = (rows + 255) / 256 < TRAIN_MAX_SPLITS ? (rows + 255) / 256 : TRAIN_MAX_SPLITS;
+    s.kps = ((rows + s.S - 1) / s.S + TG_KC - 1) / TG_KC * TG_KC;
+    s.S = (rows + s.kps - 1) / s.kps;
+    return s;
+}
+
 }  // namespace ar

@@ -2,7 +2,8 @@
 // row set's order: the forward, the losses of alpharat/nn/architectures/mlp/loss.py and what loss.backward() leaves in
 // the fourteen .grad tensors, f32 throughout. The per-element arithmetic is dev_train.h; this file holds the kernels.
 //
-// The chain of one step (rows_grad_mlp in alpharat_hip.hip), every launch on the caller's stream:
+// The chain of one step, every launch on the caller's stream. rows_grad_mlp in alpharat_hip.hip is this listing as calls;
+// the checks, the workspace, the stream rule and the launches themselves are TrainStep's, shared with train_sym.h:
 //   k_rows_batch                X and the targets of the window, by the row routine the batches use (dev_rows.h)
 //   k_train_gemm                Z1 = X W0^T + b0
 //   k_train_colsum<SUM, SQ>     column sums of Z1, then of (Z1 - mu)^2: the centred two-pass variance
@@ -31,8 +32,9 @@
 // k range, so every tail costs no branch in the inner loop. A product that reduces over the batch is split over fixed
 // ranges of rows (blockIdx.z); every range writes its own partial C and k_train_reduce adds them in range order in double.
 //
-// Determinism: no atomics anywhere. Every sum over the batch is taken over a partition that depends only on (n, H, D),
-// each part in a fixed order, the parts combined in index order: the same request gives the same bytes.
+// Determinism: no atomics anywhere. Every sum over the batch is taken over a partition that depends only on (n, H, D)
+// (train_cols and train_split, dev_train.h), each part in a fixed order, the parts combined in index order: the same
+// request gives the same bytes.
 #pragma once
 #include "dev_rows.h"
 #include "dev_train.h"
@@ -41,8 +43,7 @@ namespace ar {
 
 typedef float tr_f32x16 __attribute__((ext_vector_type(16)));
 
-enum { TG_TILE = 64, TG_KC = 16, TG_LD = TG_TILE + 1, TG_THREADS = 256, TRAIN_MAX_PARTS = 32, TRAIN_MAX_SPLITS = 32,
-       TRAIN_HEAD_ROWS = 64, TRAIN_MAX_ROWS = 65536 };
+enum { TG_TILE = 64, TG_LD = TG_TILE + 1, TG_THREADS = 256, TRAIN_HEAD_ROWS = 64, TRAIN_MAX_ROWS = 65536 };  // TG_KC: dev_train.h
 
 // C[m][n] = sum_{k in the block's range} A(m, k) B(k, n) (+ bias[n]); A(m, k) = a[m * sam + k * sak], B(k, n) =
 // b[k * sbk + n * sbn]. blockIdx.z takes k from z * k_per_split and writes C at c + z * c_split. a_kfast / b_kfast: the
@@ -141,11 +142,8 @@ __global__ void __launch_bounds__(256) k_train_reduce(TrainReduce t) {
     else t.b[seg][row] = (float)s;
 }
 
-// A layer's [n][H] arrays for the column kernels: grid (ceil(H / 64), P); block (p) takes rows p * rpp .. of 64 columns
-// with four rows in flight (thread = column + 64 * (row & 3)).
-struct TrainCols {
-    int n, H, P, rpp;
-};
+// A layer's [n][H] arrays for the column kernels (TrainCols, dev_train.h): grid (ceil(H / 64), P); block (p) takes rows
+// p * rpp .. of 64 columns with four rows in flight (thread = column + 64 * (row & 3)).
 __device__ inline double train_col_total(const double* part, int P, int H, int col) {
     double s = 0.0;
     for (int p = 0; p < P; ++p) s += part[(size_t)p * H + col];

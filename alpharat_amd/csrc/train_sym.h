@@ -8,8 +8,9 @@
 // one batch-reduced product over 2n rows with its ordered reduction. BatchNorm never pools the two: the column kernels run on
 // each half with a pointer offset, each call with its own statistics, P1's call updating the running statistics before P2's.
 //
-// The chain of one step (rows_grad_symmetric in alpharat_hip.hip), every launch on the caller's stream; "bn" is
-// k_train_colsum<SUM>, k_train_colsum<SQ>, k_train_bn_apply; "bn'" is k_train_colsum<DTRUNK>, k_train_bn_bwd:
+// The chain of one step, every launch on the caller's stream: rows_grad_symmetric in alpharat_hip.hip is this listing as
+// calls on the TrainStep it shares with train_mlp.h's driver. "bn" is k_train_colsum<SUM>, k_train_colsum<SQ>,
+// k_train_bn_apply (TrainStep::bn_forward); "bn'" is k_train_colsum<DTRUNK>, k_train_bn_bwd (bn_backward_trunk):
 //    1  k_rows_batch                X and the targets of the window (dev_rows.h)
 //    2  k_sym_split                 shared_raw [n], p_raw [2n]
 //    3  k_train_gemm, bn            shared = relu(bn(shared_raw Ws^T + bs))                                        [n]    4

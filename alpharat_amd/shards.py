@@ -168,6 +168,15 @@ def sym_param_shapes(width: int, height: int, hidden_dim: int) -> dict:
     return shapes
 
 
+# What a training step is made of, per architecture: the key tuples and shapes that check_grad_tensors holds the caller's
+# tensors to, and the two ctypes structs and the symbol that RowSet._grad_into hands them to.
+_GRAD_STEPS = {
+    "mlp": (MLP_PARAM_KEYS, MLP_RUNNING_KEYS, mlp_param_shapes, _lib.ArMlpTensors, _lib.ArMlpBnStats, "ar_rows_grad_mlp"),
+    "symmetric": (SYM_PARAM_KEYS, SYM_RUNNING_KEYS, sym_param_shapes, _lib.ArSymTensors, _lib.ArSymBnStats,
+                  "ar_rows_grad_symmetric"),
+}
+
+
 def check_grad_tensors(params: dict, grads: dict, running, out, n: int, width: int, height: int, hidden_dim: int, device,
                        architecture: str = "mlp") -> None:
     """``RowSet.grad_mlp_into``'s conditions on its tensors (``ValueError``), in the manner of ``check_out_tensors``; no
@@ -175,12 +184,10 @@ def check_grad_tensors(params: dict, grads: dict, running, out, n: int, width: i
     ``SYM_PARAM_KEYS`` and ``SYM_RUNNING_KEYS``."""
     import torch
 
-    if architecture == "mlp":
-        param_keys, running_keys, shapes = MLP_PARAM_KEYS, MLP_RUNNING_KEYS, mlp_param_shapes(width, height, hidden_dim)
-    elif architecture == "symmetric":
-        param_keys, running_keys, shapes = SYM_PARAM_KEYS, SYM_RUNNING_KEYS, sym_param_shapes(width, height, hidden_dim)
-    else:
+    if architecture not in _GRAD_STEPS:
         raise ValueError(f"no training step for architecture {architecture!r}")
+    param_keys, running_keys, shapes_of = _GRAD_STEPS[architecture][:3]
+    shapes = shapes_of(width, height, hidden_dim)
     out_shapes = dict(losses=(6,), logits_p1=(n, 5), logits_p2=(n, 5), value_p1=(n,), value_p2=(n,))
     groups = [("params", params, param_keys, shapes, True), ("grads", grads, param_keys, shapes, True)]
     if running is not None:
@@ -303,50 +310,37 @@ class RowSet:
         the four ``MLP_RUNNING_KEYS``, updated in place, or ``None``. ``out``: any of ``TRAIN_OUT_KEYS`` (losses ``(6,)``,
         logits ``(n, 5)``, values ``(n,)``), or ``None``. Every tensor is on the set's device, float32, contiguous and of
         the shape ``(width, height, hidden_dim)`` give, else ``ValueError`` before the library is touched."""
-        import torch
-
-        first, n, hidden_dim = int(first), int(n), int(hidden_dim)
-        if first < 0 or n < 0 or hidden_dim <= 0:
-            raise ValueError("first and n must not be negative, hidden_dim positive")
-        check_grad_tensors(params, grads, running, out, n, self.width, self.height, hidden_dim,
-                           torch.device("cuda", self.device_index))
-        handle = self._handle()
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device_index)
-        p = _lib.ArMlpTensors(*[params[k].data_ptr() for k in MLP_PARAM_KEYS])
-        g = _lib.ArMlpTensors(*[grads[k].data_ptr() for k in MLP_PARAM_KEYS])
-        r = _lib.ArMlpBnStats(*[running[k].data_ptr() for k in MLP_RUNNING_KEYS]) if running is not None else None
-        o = (_lib.ArTrainOut(*[out[k].data_ptr() if out.get(k) is not None else None for k in TRAIN_OUT_KEYS])
-             if out is not None else None)
-        _lib.check(_lib.load().ar_rows_grad_mlp(handle, first, n, hidden_dim, C.byref(p), C.byref(g),
-                                                C.byref(r) if r is not None else None, float(policy_weight),
-                                                float(value_weight), C.byref(o) if o is not None else None,
-                                                C.c_void_p(stream.cuda_stream)))
+        self._grad_into("mlp", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream)
 
     def grad_symmetric_into(self, first: int, n: int, hidden_dim: int, params: dict, grads: dict, running, policy_weight: float,
                             value_weight: float, out, stream=None) -> None:
         """``grad_mlp_into`` for SymmetricMLP (``ar_rows_grad_symmetric``): ``params`` and ``grads`` are the twenty tensors
         under ``SYM_PARAM_KEYS``, ``running`` the eight ``SYM_RUNNING_KEYS`` or ``None``, of the shapes
         ``sym_param_shapes(width, height, hidden_dim)`` gives; everything else as there."""
+        self._grad_into("symmetric", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream)
+
+    def _grad_into(self, architecture: str, first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out,
+                   stream) -> None:
         import torch
 
         first, n, hidden_dim = int(first), int(n), int(hidden_dim)
         if first < 0 or n < 0 or hidden_dim <= 0:
             raise ValueError("first and n must not be negative, hidden_dim positive")
         check_grad_tensors(params, grads, running, out, n, self.width, self.height, hidden_dim,
-                           torch.device("cuda", self.device_index), architecture="symmetric")
+                           torch.device("cuda", self.device_index), architecture=architecture)
+        param_keys, running_keys, _, Tensors, BnStats, symbol = _GRAD_STEPS[architecture]
         handle = self._handle()
         if stream is None:
             stream = torch.cuda.current_stream(self.device_index)
-        p = _lib.ArSymTensors(*[params[k].data_ptr() for k in SYM_PARAM_KEYS])
-        g = _lib.ArSymTensors(*[grads[k].data_ptr() for k in SYM_PARAM_KEYS])
-        r = _lib.ArSymBnStats(*[running[k].data_ptr() for k in SYM_RUNNING_KEYS]) if running is not None else None
+        p = Tensors(*[params[k].data_ptr() for k in param_keys])
+        g = Tensors(*[grads[k].data_ptr() for k in param_keys])
+        r = BnStats(*[running[k].data_ptr() for k in running_keys]) if running is not None else None
         o = (_lib.ArTrainOut(*[out[k].data_ptr() if out.get(k) is not None else None for k in TRAIN_OUT_KEYS])
              if out is not None else None)
-        _lib.check(_lib.load().ar_rows_grad_symmetric(handle, first, n, hidden_dim, C.byref(p), C.byref(g),
-                                                      C.byref(r) if r is not None else None, float(policy_weight),
-                                                      float(value_weight), C.byref(o) if o is not None else None,
-                                                      C.c_void_p(stream.cuda_stream)))
+        _lib.check(getattr(_lib.load(), symbol)(handle, first, n, hidden_dim, C.byref(p), C.byref(g),
+                                                C.byref(r) if r is not None else None, float(policy_weight),
+                                                float(value_weight), C.byref(o) if o is not None else None,
+                                                C.c_void_p(stream.cuda_stream)))
 
     def validate(self, net, rows, chunk_rows: int = 0, return_rows: bool = False):
         """``net`` over the stored positions ``rows``: the sums of the reference's validation pass

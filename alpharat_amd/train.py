@@ -31,10 +31,13 @@ from .shards import MLP_PARAM_KEYS, MLP_RUNNING_KEYS, SYM_BN_MODULES, SYM_PARAM_
 _PREFIX = "_orig_mod."  # torch.compile's wrapper, stripped as weights.py does
 
 
-class MLPGradStep:
-    """``model``: an ``nn.Module`` whose ``state_dict()`` has PyRatMLP's keys (an ``_orig_mod.`` prefix is stripped).
-    ``ValueError`` for a ``Dropout`` with ``p != 0``, an ``ownership_head``, a missing key, or a parameter or BatchNorm
-    buffer that is not float32 or not contiguous. One persistent gradient tensor per parameter is allocated here."""
+class _GradStep:
+    """What both steps do. A subclass names its architecture (``_NAME``, for the messages), its parameter and
+    running-statistic keys, the ``(num_batches_tracked key, BatchNorm calls per step)`` pairs and the ``RowSet`` method
+    that launches it; ``_read_dims`` takes the widths from the checked parameters and ``_check_board`` holds them
+    against a row set's board."""
+
+    _NAME = _PARAM_KEYS = _RUNNING_KEYS = _TRACKED = _ROWSET_METHOD = None
 
     def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0) -> None:
         import torch
@@ -43,42 +46,38 @@ class MLPGradStep:
         self.policy_weight, self.value_weight = float(policy_weight), float(value_weight)
         for m in model.modules():
             if isinstance(m, torch.nn.Dropout) and m.p != 0:
-                raise ValueError(f"dropout {m.p} is not supported: the step is built for PyRatMLP's default dropout 0.0")
+                raise ValueError(f"dropout {m.p} is not supported: the step is built for {self._NAME}'s default dropout 0.0")
         named = {k.removeprefix(_PREFIX): v for k, v in model.named_parameters()}
         buffers = {k.removeprefix(_PREFIX): v for k, v in model.named_buffers()}
-        if any(k.startswith("ownership_head.") for k in list(named) + list(buffers)):
-            raise ValueError("the model has an ownership_head (LocalValueMLP): its loss has a third term that this step "
-                             "does not compute")
-        missing = [k for k in MLP_PARAM_KEYS if k not in named] + [
-            k for k in MLP_RUNNING_KEYS + ("trunk.1.num_batches_tracked", "trunk.5.num_batches_tracked") if k not in buffers]
+        self._refuse(named, buffers)
+        tracked = tuple(k for k, _ in self._TRACKED)
+        missing = [k for k in self._PARAM_KEYS if k not in named] + [k for k in self._RUNNING_KEYS + tracked if k not in buffers]
         if missing:
-            raise ValueError(f"the model is not a PyRatMLP: its state_dict lacks {', '.join(missing)}")
-        self.params = {k: named[k] for k in MLP_PARAM_KEYS}
-        self.running = {k: buffers[k] for k in MLP_RUNNING_KEYS}
-        self._tracked = (buffers["trunk.1.num_batches_tracked"], buffers["trunk.5.num_batches_tracked"])
+            raise ValueError(f"the model is not a {self._NAME}: its state_dict lacks {', '.join(missing)}")
+        self.params = {k: named[k] for k in self._PARAM_KEYS}
+        self.running = {k: buffers[k] for k in self._RUNNING_KEYS}
+        self._tracked = tuple((buffers[k], calls) for k, calls in self._TRACKED)
         for k, t in {**self.params, **self.running}.items():
             if t.dtype != torch.float32:
                 raise ValueError(f"{k} has dtype {t.dtype}: the step is float32 throughout")
             if not t.is_contiguous():
                 raise ValueError(f"{k} is not contiguous")
-        w0 = self.params["trunk.0.weight"]
-        if w0.dim() != 2:
-            raise ValueError(f"trunk.0.weight has shape {tuple(w0.shape)}")
-        self.hidden_dim, self.obs_dim = int(w0.shape[0]), int(w0.shape[1])
+        self._read_dims()
         self.grads = {k: torch.zeros_like(p) for k, p in self.params.items()}
 
+    def _refuse(self, named: dict, buffers: dict) -> None:
+        pass
+
+    def _weight(self, key: str):
+        w = self.params[key]
+        if w.dim() != 2:
+            raise ValueError(f"{key} has shape {tuple(w.shape)}")
+        return w
+
     def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
-        """Loss and gradients of rows ``first .. first + n`` of ``rowset``'s order, launched on torch's current stream;
-        nothing is synchronised. Every parameter's ``.grad`` is (again) this object's buffer, overwritten -- so
-        ``zero_grad(set_to_none=True)`` between steps is harmless and gradient accumulation is not what this does. With
-        ``model.training`` the running statistics are updated in place and both ``num_batches_tracked`` grow by one.
-        Returns the ``(6,)`` tensor loss_p1, loss_p2, loss_value_p1, loss_value_p2, loss_value, loss; with ``outputs``
-        ``(losses, logits_p1 (n, 5), logits_p2 (n, 5), value_p1 (n,), value_p2 (n,))``, the training-mode outputs."""
         import torch
 
-        if rowset.width * rowset.height * 7 + 6 != self.obs_dim:
-            raise ValueError(f"the model reads {self.obs_dim} inputs, a {rowset.width}x{rowset.height} row has "
-                             f"{rowset.width * rowset.height * 7 + 6}")
+        self._check_board(rowset)
         device = torch.device("cuda", rowset.device_index)
         n = int(n)
         out = dict(losses=torch.empty(6, device=device, dtype=torch.float32))
@@ -87,76 +86,8 @@ class MLPGradStep:
                        value_p1=torch.empty(n, device=device), value_p2=torch.empty(n, device=device))
         training = bool(self.model.training)
         params = {k: p.data for k, p in self.params.items()}
-        rowset.grad_mlp_into(first, n, self.hidden_dim, params, self.grads, self.running if training else None,
-                             self.policy_weight, self.value_weight, out)
-        for k, p in self.params.items():
-            p.grad = self.grads[k]
-        if training:
-            for t in self._tracked:
-                t.add_(1)
-        if outputs:
-            return out["losses"], out["logits_p1"], out["logits_p2"], out["value_p1"], out["value_p2"]
-        return out["losses"]
-
-
-class SymmetricGradStep:
-    """``MLPGradStep`` for SymmetricMLP: ``model`` is an ``nn.Module`` whose ``state_dict()`` has SymmetricMLP's keys (an
-    ``_orig_mod.`` prefix is stripped). ``ValueError`` for a ``Dropout`` with ``p != 0``, a missing key (a PyRatMLP lacks
-    the encoders and ``policy_head``), or a parameter or BatchNorm buffer that is not float32 or not contiguous. One
-    persistent gradient tensor per parameter is allocated here."""
-
-    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0) -> None:
-        import torch
-
-        self.model = model
-        self.policy_weight, self.value_weight = float(policy_weight), float(value_weight)
-        for m in model.modules():
-            if isinstance(m, torch.nn.Dropout) and m.p != 0:
-                raise ValueError(f"dropout {m.p} is not supported: the step is built for SymmetricMLP's default dropout 0.0")
-        named = {k.removeprefix(_PREFIX): v for k, v in model.named_parameters()}
-        buffers = {k.removeprefix(_PREFIX): v for k, v in model.named_buffers()}
-        tracked = tuple(f"{bn}.num_batches_tracked" for bn in SYM_BN_MODULES)
-        missing = [k for k in SYM_PARAM_KEYS if k not in named] + [k for k in SYM_RUNNING_KEYS + tracked if k not in buffers]
-        if missing:
-            raise ValueError(f"the model is not a SymmetricMLP: its state_dict lacks {', '.join(missing)}")
-        self.params = {k: named[k] for k in SYM_PARAM_KEYS}
-        self.running = {k: buffers[k] for k in SYM_RUNNING_KEYS}
-        # shared_encoder.1 sees a batch once, the other three modules once per player
-        self._tracked = tuple((buffers[k], 1 if k.startswith("shared_encoder.") else 2) for k in tracked)
-        for k, t in {**self.params, **self.running}.items():
-            if t.dtype != torch.float32:
-                raise ValueError(f"{k} has dtype {t.dtype}: the step is float32 throughout")
-            if not t.is_contiguous():
-                raise ValueError(f"{k} is not contiguous")
-        w4, ws, wp = (self.params[k] for k in ("trunk.4.weight", "shared_encoder.0.weight", "player_encoder.0.weight"))
-        for k, w in (("trunk.4.weight", w4), ("shared_encoder.0.weight", ws), ("player_encoder.0.weight", wp)):
-            if w.dim() != 2:
-                raise ValueError(f"{k} has shape {tuple(w.shape)}")
-        self.hidden_dim, self.shared_dim, self.player_dim = int(w4.shape[0]), int(ws.shape[1]), int(wp.shape[1])
-        self.grads = {k: torch.zeros_like(p) for k, p in self.params.items()}
-
-    def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
-        """``MLPGradStep.step`` under the same contract: launched on torch's current stream, nothing synchronised, every
-        parameter's ``.grad`` is (again) this object's buffer, overwritten. The batch's statistics are always used; with
-        ``model.training`` the running statistics are updated in place (P1's call, then P2's) and
-        ``num_batches_tracked`` grows by one for ``shared_encoder.1`` and by two for the other three modules. Returns the
-        ``(6,)`` losses, with ``outputs`` also the four training-mode outputs."""
-        import torch
-
-        hw = rowset.width * rowset.height
-        if (5 * hw + 1, hw + 2) != (self.shared_dim, self.player_dim):
-            raise ValueError(f"the model's encoders read {self.shared_dim} and {self.player_dim} inputs, a "
-                             f"{rowset.width}x{rowset.height} board gives {5 * hw + 1} and {hw + 2}")
-        device = torch.device("cuda", rowset.device_index)
-        n = int(n)
-        out = dict(losses=torch.empty(6, device=device, dtype=torch.float32))
-        if outputs:
-            out.update(logits_p1=torch.empty((n, 5), device=device), logits_p2=torch.empty((n, 5), device=device),
-                       value_p1=torch.empty(n, device=device), value_p2=torch.empty(n, device=device))
-        training = bool(self.model.training)
-        params = {k: p.data for k, p in self.params.items()}
-        rowset.grad_symmetric_into(first, n, self.hidden_dim, params, self.grads, self.running if training else None,
-                                   self.policy_weight, self.value_weight, out)
+        getattr(rowset, self._ROWSET_METHOD)(first, n, self.hidden_dim, params, self.grads, self.running if training else None,
+                                             self.policy_weight, self.value_weight, out)
         for k, p in self.params.items():
             p.grad = self.grads[k]
         if training:
@@ -165,3 +96,64 @@ class SymmetricGradStep:
         if outputs:
             return out["losses"], out["logits_p1"], out["logits_p2"], out["value_p1"], out["value_p2"]
         return out["losses"]
+
+
+class MLPGradStep(_GradStep):
+    """``model``: an ``nn.Module`` whose ``state_dict()`` has PyRatMLP's keys (an ``_orig_mod.`` prefix is stripped).
+    ``ValueError`` for a ``Dropout`` with ``p != 0``, an ``ownership_head``, a missing key, or a parameter or BatchNorm
+    buffer that is not float32 or not contiguous. One persistent gradient tensor per parameter is allocated here."""
+
+    _NAME, _PARAM_KEYS, _RUNNING_KEYS, _ROWSET_METHOD = "PyRatMLP", MLP_PARAM_KEYS, MLP_RUNNING_KEYS, "grad_mlp_into"
+    _TRACKED = (("trunk.1.num_batches_tracked", 1), ("trunk.5.num_batches_tracked", 1))
+
+    def _refuse(self, named: dict, buffers: dict) -> None:
+        if any(k.startswith("ownership_head.") for k in list(named) + list(buffers)):
+            raise ValueError("the model has an ownership_head (LocalValueMLP): its loss has a third term that this step "
+                             "does not compute")
+
+    def _read_dims(self) -> None:
+        w0 = self._weight("trunk.0.weight")
+        self.hidden_dim, self.obs_dim = int(w0.shape[0]), int(w0.shape[1])
+
+    def _check_board(self, rowset: RowSet) -> None:
+        if rowset.width * rowset.height * 7 + 6 != self.obs_dim:
+            raise ValueError(f"the model reads {self.obs_dim} inputs, a {rowset.width}x{rowset.height} row has "
+                             f"{rowset.width * rowset.height * 7 + 6}")
+
+    def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
+        """Loss and gradients of rows ``first .. first + n`` of ``rowset``'s order, launched on torch's current stream;
+        nothing is synchronised. Every parameter's ``.grad`` is (again) this object's buffer, overwritten -- so
+        ``zero_grad(set_to_none=True)`` between steps is harmless and gradient accumulation is not what this does. With
+        ``model.training`` the running statistics are updated in place and both ``num_batches_tracked`` grow by one.
+        Returns the ``(6,)`` tensor loss_p1, loss_p2, loss_value_p1, loss_value_p2, loss_value, loss; with ``outputs``
+        ``(losses, logits_p1 (n, 5), logits_p2 (n, 5), value_p1 (n,), value_p2 (n,))``, the training-mode outputs."""
+        return super().step(rowset, first, n, outputs)
+
+
+class SymmetricGradStep(_GradStep):
+    """``MLPGradStep`` for SymmetricMLP: ``model`` is an ``nn.Module`` whose ``state_dict()`` has SymmetricMLP's keys (an
+    ``_orig_mod.`` prefix is stripped). ``ValueError`` for a ``Dropout`` with ``p != 0``, a missing key (a PyRatMLP lacks
+    the encoders and ``policy_head``), or a parameter or BatchNorm buffer that is not float32 or not contiguous. One
+    persistent gradient tensor per parameter is allocated here."""
+
+    _NAME, _PARAM_KEYS, _RUNNING_KEYS, _ROWSET_METHOD = "SymmetricMLP", SYM_PARAM_KEYS, SYM_RUNNING_KEYS, "grad_symmetric_into"
+    # shared_encoder.1 sees a batch once, the other three modules once per player
+    _TRACKED = tuple((f"{bn}.num_batches_tracked", 1 if bn.startswith("shared_encoder.") else 2) for bn in SYM_BN_MODULES)
+
+    def _read_dims(self) -> None:
+        w4, ws, wp = (self._weight(k) for k in ("trunk.4.weight", "shared_encoder.0.weight", "player_encoder.0.weight"))
+        self.hidden_dim, self.shared_dim, self.player_dim = int(w4.shape[0]), int(ws.shape[1]), int(wp.shape[1])
+
+    def _check_board(self, rowset: RowSet) -> None:
+        hw = rowset.width * rowset.height
+        if (5 * hw + 1, hw + 2) != (self.shared_dim, self.player_dim):
+            raise ValueError(f"the model's encoders read {self.shared_dim} and {self.player_dim} inputs, a "
+                             f"{rowset.width}x{rowset.height} board gives {5 * hw + 1} and {hw + 2}")
+
+    def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
+        """``MLPGradStep.step`` under the same contract: launched on torch's current stream, nothing synchronised, every
+        parameter's ``.grad`` is (again) this object's buffer, overwritten. The batch's statistics are always used; with
+        ``model.training`` the running statistics are updated in place (P1's call, then P2's) and
+        ``num_batches_tracked`` grows by one for ``shared_encoder.1`` and by two for the other three modules. Returns the
+        ``(6,)`` losses, with ``outputs`` also the four training-mode outputs."""
+        return super().step(rowset, first, n, outputs)

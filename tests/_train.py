@@ -202,6 +202,9 @@ def sim() -> C.CDLL:
         L.ts_bn_backward.restype = None
         L.ts_bn_backward.argtypes = [C.c_uint64, C.c_uint32] + [C.c_void_p] * 7
         L.ts_terms_words.restype = C.c_int
+        L.ts_cols.restype = L.ts_split.restype = None
+        L.ts_cols.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.ts_split.argtypes = [C.c_int, C.c_void_p]
         assert L.ts_terms_words() * 4 == TERMS.itemsize
         _sim = L
     return _sim
@@ -231,3 +234,17 @@ def sim_bn_backward(dy, xhat, var, gamma, mean_dy, mean_dyx):
     dz = np.zeros_like(arrs[0])
     sim().ts_bn_backward(arrs[0].shape[0], arrs[0].shape[1], *[a.ctypes.data for a in arrs], dz.ctypes.data)
     return dz
+
+
+def sim_cols(n: int, H: int) -> tuple:
+    """dev_train.h train_cols: (P, rpp)"""
+    out = np.zeros(2, np.int32)
+    sim().ts_cols(n, H, out.ctypes.data)
+    return int(out[0]), int(out[1])
+
+
+def sim_split(rows: int) -> tuple:
+    """dev_train.h train_split: (S, kps)"""
+    out = np.zeros(2, np.int32)
+    sim().ts_split(rows, out.ctypes.data)
+    return int(out[0]), int(out[1])

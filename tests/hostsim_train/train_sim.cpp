@@ -1,7 +1,8 @@
 // TEST HARNESS -- runs alpharat_amd/csrc/dev_train.h on the CPU: the heads' terms of a row (train_head_terms, one lane per
 // row in k_train_heads) and the BatchNorm forward and backward of an element (train_bn_forward, train_bn_backward, one lane
 // per element in k_train_bn_apply, k_train_colsum and k_train_bn_bwd), with loops where the device has lanes. The column
-// statistics are arguments, as they are for the kernels. It is NOT a CPU fallback: nothing in alpharat_amd/ loads this file.
+// statistics are arguments, as they are for the kernels. Also the two partitions of a step (train_cols, train_split), which
+// the host drivers call as they stand. It is NOT a CPU fallback: nothing in alpharat_amd/ loads this file.
 #include <cstdint>
 #include <cstring>
 
@@ -38,6 +39,19 @@ void ts_bn_backward(uint64_t n, uint32_t H, const float* dy, const float* xhat, 
             const uint64_t i = r * H + c;
             dz[i] = train_bn_backward(dy[i], xhat[i], train_bn_rstd(var[c]), gamma[c], mean_dy[c], mean_dy_xhat[c]);
         }
+}
+
+// P, rpp of train_cols(n, H); S, kps of train_split(rows)
+void ts_cols(int n, int H, int* out) {
+    const TrainCols t = train_cols(n, H);
+    out[0] = t.P;
+    out[1] = t.rpp;
+}
+
+void ts_split(int rows, int* out) {
+    const TrainSplit s = train_split(rows);
+    out[0] = s.S;
+    out[1] = s.kps;
 }
 
 }  // extern "C"

@@ -2,7 +2,8 @@
 tests/hostsim_train against the float64 restatement (tests/_train_np.py): the heads' loss terms and dOut of every row, the
 BatchNorm forward and backward of every element given the float64 column statistics. Inputs are the float64 step's values
 rounded to float32; the expectation is the same formula in float64 on those rounded inputs. Bound: 1e-6 relative to
-1 + |value| (f32 expf / logf against float64, the bound the validation terms use)."""
+1 + |value| (f32 expf / logf against float64, the bound the validation terms use). And the two partitions of a step
+(train_cols, train_split), which fix the order of every sum over the batch, against a table of literals."""
 import numpy as np
 import pytest
 
@@ -90,3 +91,44 @@ def test_batchnorm_of_every_element(kind, arg):
         _within(dz, want, f"dz{layer}")
         # and the rounded chain stays at the float64 step's own dz
         assert np.abs(dz - r[f"dz{layer}"]).max() <= 1e-5 * (1.0 + np.abs(r[f"dz{layer}"]).max())
+
+
+# rows: (P, rpp, S, kps). The values the drivers computed inline before train_cols and train_split existed, printed from
+# those statements; 2, 257, 2049, 4096, 65536 and the split of 131072 also worked out by hand. 131072 is the symmetric
+# step's 2n at the row cap: a split only, no step has that many rows in a BatchNorm call.
+PARTITIONS = {
+    2: (1, 2, 1, 16),
+    15: (1, 15, 1, 16),
+    16: (1, 16, 1, 16),
+    17: (1, 17, 1, 32),
+    63: (1, 63, 1, 64),
+    64: (1, 64, 1, 64),
+    65: (2, 33, 1, 80),
+    255: (4, 64, 1, 256),
+    256: (4, 64, 1, 256),
+    257: (5, 52, 2, 144),
+    2047: (32, 64, 8, 256),
+    2048: (32, 64, 8, 256),
+    2049: (32, 65, 9, 240),
+    4096: (32, 128, 16, 256),
+    8191: (32, 256, 32, 256),
+    8193: (32, 257, 31, 272),
+    65535: (32, 2048, 32, 2048),
+    65536: (32, 2048, 32, 2048),
+    131072: (None, None, 32, 4096),
+}
+
+
+@pytest.mark.parametrize("rows", list(PARTITIONS))
+def test_partitions_of_the_batch(rows):
+    """every row in exactly one part and one split, within the caps the workspace is sized for, and the same partition as
+    ever: another one would sum in another order and change the gradients' bytes"""
+    want_P, want_rpp, want_S, want_kps = PARTITIONS[rows]
+    S, kps = TR.sim_split(rows)
+    assert S <= 32 and kps % 16 == 0 and (S - 1) * kps < rows <= S * kps
+    assert (S, kps) == (want_S, want_kps)
+    if want_P is not None:
+        for H in (32, 256):  # the width is carried along, it decides nothing
+            P, rpp = TR.sim_cols(rows, H)
+            assert P <= 32 and (P - 1) * rpp < rows <= P * rpp
+            assert (P, rpp) == (want_P, want_rpp)
