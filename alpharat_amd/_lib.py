@@ -231,6 +231,17 @@ class ArSymBnStats(C.Structure):
                                           "bn2_var")]
 
 
+LV_TENSORS = MLP_TENSORS + ("own0_w", "own0_b", "own2_w", "own2_b")
+
+
+class ArLvTensors(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in LV_TENSORS]
+
+
+class ArLvTrainOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("losses", "logits_p1", "logits_p2", "value_p1", "value_p2", "ownership_logits")]
+
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -282,6 +293,9 @@ EXPORTS = {
     "ar_rows_grad_symmetric": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArSymTensors),
                                          C.POINTER(ArSymTensors), C.POINTER(ArSymBnStats), C.c_float, C.c_float,
                                          C.POINTER(ArTrainOut), C.c_void_p]),
+    "ar_rows_grad_local_value": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArLvTensors),
+                                           C.POINTER(ArLvTensors), C.POINTER(ArMlpBnStats), C.c_float, C.c_float, C.c_float,
+                                           C.POINTER(ArLvTrainOut), C.c_void_p]),
 }
 
 _lib = None

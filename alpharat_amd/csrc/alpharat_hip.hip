@@ -39,6 +39,7 @@
 #include "dev_validate.h"
 #include "train_mlp.h"
 #include "train_sym.h"
+#include "train_lv.h"
 #include "host_games.h"
 #include "zig_norm_tables.inc"
 
@@ -2881,7 +2882,7 @@ struct RowStore {
     DevBuf<OwnAcc> own_total;
     size_t own_feat_n = 0, own_logits_n = 0;
     uint32_t own_chunk = 0;
-    // ar_rows_grad_mlp: the workspace of one training step (train_mlp.h), one allocation grown to the largest request
+    // ar_rows_grad_*: the workspace of one training step (train_mlp.h), one allocation grown to the largest request
     DevBuf<uint8_t> train_ws;
     size_t train_ws_bytes = 0;
     // uploads and builds run on the null stream: they wait for the attached session's last append, nothing else
@@ -3233,9 +3234,9 @@ static hipError_t regrow(DevBuf<T>& b, size_t count) {
     return b.alloc(count);
 }
 
-// What the training steps of a row set share (ar_rows_grad_mlp, ar_rows_grad_symmetric): the refusals, the workspace, the
-// stream rule and the launches that both chains are made of. One rule for the workspace and the stream, stated here only:
-// a set has one workspace, grown to the largest request; a step waits on ev_batch before it touches it, so a step on
+// What the training steps of a row set share (ar_rows_grad_mlp, ar_rows_grad_symmetric, ar_rows_grad_local_value): the
+// refusals, the workspace, the stream rule and the launches that the chains are made of. One rule for the workspace and
+// the stream, stated here only: a set has one workspace, grown to the largest request; a step waits on ev_batch before it touches it, so a step on
 // another stream starts behind the last one; growth first waits for the pending batches, which may still use the old
 // block; and ev_batch is recorded behind the step's last launch, so whatever waits for pending batches waits for a
 // pending step too. Everything is checked before the first launch; a step then only launches, and allocates only to grow.
@@ -3245,6 +3246,9 @@ static const char* const kMlpTensorNames[14] = {"trunk0_w", "trunk0_b", "bn1_w",
 static const char* const kSymTensorNames[20] = {"se0_w",    "se0_b",    "se1_w",  "se1_b",  "pe0_w",    "pe0_b",    "pe1_w",
                                                 "pe1_b",    "trunk0_w", "trunk0_b", "bn1_w", "bn1_b",    "trunk4_w", "trunk4_b",
                                                 "bn2_w",    "bn2_b",    "policy_w", "policy_b", "value_w", "value_b"};
+static const char* const kLvTensorNames[18] = {"trunk0_w", "trunk0_b", "bn1_w", "bn1_b", "trunk4_w", "trunk4_b", "bn2_w", "bn2_b", "p1_w",
+                                               "p1_b",     "p2_w",     "p2_b",  "value_w", "value_b", "own0_w",  "own0_b", "own2_w",
+                                               "own2_b"};
 struct TrainStep {
     RowStore& R;
     hipStream_t stream;
@@ -3392,9 +3396,10 @@ struct TrainStep {
     void linear(const float* in, int rows, int K, const float* w, const float* b, float* z) {
         gemm(in, K, 1, 1, w, 1, K, 1, z, rows, H, K, b, 1, K, nullptr);
     }
-    // dIn[rows][N] = d[rows][H] W[H][N]
-    void grad_in(const float* d, int rows, const float* w, int N, float* din) {
-        gemm(d, H, 1, 1, w, N, 1, 0, din, rows, N, H, nullptr, 1, H, nullptr);
+    // dIn[rows][N] = d[rows][K] W[K][N], K = H unless given (the ownership head's last layer has 4 hw outputs)
+    void grad_in(const float* d, int rows, const float* w, int N, float* din, int K = 0) {
+        if (K == 0) K = H;
+        gemm(d, K, 1, 1, w, N, 1, 0, din, rows, N, K, nullptr, 1, K, nullptr);
     }
     // dW[M][N] = d[rows][M]^T In[rows][N] and db = colsum(d): per row range of `sp`, then the ranges added in order into up
     // to three destinations, consecutive segments of dW's rows (the MLP's three heads; one segment otherwise)
@@ -3467,25 +3472,52 @@ struct TrainStep {
     }
 };
 
+// What ar_rows_grad_local_value adds to a call of rows_grad_mlp: the eighteen tensors (their first fourteen are the `p` and
+// `g` of the call), the third weight and the caller's outputs (the first five of them are the `out` of the call).
+struct LvStep {
+    const ArLvTensors *p, *g;
+    float ow;
+    const ArLvTrainOut* out;
+};
+
 // ar_rows_grad_mlp: the loss and the gradients of PyRatMLP over rows first .. first + n of the order, on the caller's
-// stream: train_mlp.h's chain, under TrainStep's rules.
+// stream: train_mlp.h's chain, under TrainStep's rules. With `lv`, ar_rows_grad_local_value: the same chain issued by the
+// same lines, and between them what train_lv.h lists for the ownership head.
 template <int NW>
 int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const ArMlpTensors& p, const ArMlpTensors& g,
-                  const ArMlpBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream) {
+                  const ArMlpBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream,
+                  const LvStep* lv = nullptr) {
     static_assert(sizeof(ArMlpTensors) == 14 * sizeof(float*), "fourteen pointers");
     static_assert(sizeof(ArMlpBnStats) == 4 * sizeof(float*), "four pointers");
+    static_assert(sizeof(ArLvTensors) == 18 * sizeof(float*) && offsetof(ArLvTensors, own0_w) == sizeof(ArMlpTensors),
+                  "ArMlpTensors' fourteen pointers, then four");
+    static_assert(sizeof(ArLvTrainOut) == 6 * sizeof(float*) && offsetof(ArLvTrainOut, ownership_logits) == sizeof(ArTrainOut),
+                  "ArTrainOut's five pointers, then one");
     TrainStep T{R, stream};
-    if (int rc = T.check(first, n64, H, kMlpTensorNames, (float* const*)&p, (float* const*)&g, 14, (float* const*)run, run ? 4 : 0, out))
+    if (int rc = lv ? T.check(first, n64, H, kLvTensorNames, (float* const*)lv->p, (float* const*)lv->g, 18, (float* const*)run,
+                              run ? 4 : 0, out)
+                    : T.check(first, n64, H, kMlpTensorNames, (float* const*)&p, (float* const*)&g, 14, (float* const*)run,
+                              run ? 4 : 0, out))
         return rc;
-    const int n = T.n, D = (int)rows_obs_dim(R.hw), Hi = T.H;
+    if (lv && lv->out && lv->out->ownership_logits)
+        if (int rc = rows_check_device_ptr(R, lv->out->ownership_logits, 4, "output")) return rc;
+    const int n = T.n, D = (int)rows_obs_dim(R.hw), Hi = T.H, hw4 = 4 * (int)R.hw;
+    const LvCells lc = lv_cells(n, (int)R.hw);
     const TrainSplit sp = train_split(n);
     const size_t nH = (size_t)n * H * 4;
     T.take_rows();
     const size_t o_z1 = T.take(nH), o_act1 = T.take(nH), o_z2 = T.take(nH), o_act2 = T.take(nH), o_dout = T.take((size_t)n * 48),
                  o_dz2 = T.take(nH), o_dz1 = T.take(nH), o_parts = T.take((size_t)6 * TRAIN_MAX_PARTS * H * 8),
                  o_mean = T.take((size_t)2 * H * 8), o_rstd = T.take((size_t)2 * H * 4),
-                 o_wpart = T.take((size_t)sp.S * H * std::max(D, Hi) * 4), o_bpart = T.take((size_t)sp.S * H * 4);
+                 o_wpart = T.take((size_t)sp.S * H * std::max(D, Hi) * 4),  // (D > 4 hw: dWo2's [S][4 hw][H] fits as well)
+                 o_bpart = T.take((size_t)sp.S * (lv ? std::max(Hi, hw4) : Hi) * 4);
     T.take_losses();
+    // the ownership head's: Zo, Ao, dAo [n][H], L [n][4 hw], the row parts' counts and ce sums, the seven losses
+    size_t o_zo = 0, o_ao = 0, o_dao = 0, o_l = 0, o_cnt = 0, o_ce = 0, o_loss7 = 0;
+    if (lv) {
+        o_zo = T.take(nH), o_ao = T.take(nH), o_dao = T.take(nH), o_l = T.take((size_t)n * hw4 * 4);
+        o_cnt = T.take((size_t)lc.B * 4), o_ce = T.take((size_t)lc.B * 8), o_loss7 = T.take(7 * 4);
+    }
     if (int rc = T.begin()) return rc;
     float *Z1 = T.f(o_z1), *A1 = T.f(o_act1), *Z2 = T.f(o_z2), *A2 = T.f(o_act2), *dOut = T.f(o_dout), *dZ2 = T.f(o_dz2),
           *dZ1 = T.f(o_dz1), *rstds = T.f(o_rstd);
@@ -3507,7 +3539,8 @@ int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const A
         a.w_p2 = p.p2_w;
         a.w_v = p.value_w;
         if (!head) return T.bn_backward_trunk(a, gamma, dgamma, dbeta);
-        hipLaunchKernelGGL(k_train_colsum<TC_DHEAD>, T.cgrid(), dim3(256), 0, stream, T.tc, a);
+        if (lv) hipLaunchKernelGGL(k_train_colsum<TC_DHEAD_ADD>, T.cgrid(), dim3(256), 0, stream, T.tc, a);  // d holds dZo Wo0
+        else hipLaunchKernelGGL(k_train_colsum<TC_DHEAD>, T.cgrid(), dim3(256), 0, stream, T.tc, a);
         T.bn_bwd(z, d, part(4), part(5), a.mu, a.rstd, gamma, dgamma, dbeta);
     };
     const float* X = T.f(T.o_rows[0]);
@@ -3533,10 +3566,53 @@ int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const A
         t.pw_n = pw / (float)n;
         t.vw_n = vw / (float)n;
         hipLaunchKernelGGL(k_train_heads, dim3(T.head_blocks), dim3(256), (size_t)12 * H * 4, stream, t);
-        T.loss_sum(pw, vw, out);
+        if (!lv) T.loss_sum(pw, vw, out);
+    }
+    float *Zo = nullptr, *Ao = nullptr, *dAo = nullptr, *L = nullptr;
+    if (lv) {  // the ownership head's forward, its cells' terms and dL in place of L, the seven losses
+        Zo = T.f(o_zo), Ao = T.f(o_ao), dAo = T.f(o_dao), L = T.f(o_l);
+        const size_t nH4 = (size_t)n * H / 4;
+        T.linear(A2, n, Hi, lv->p->own0_w, lv->p->own0_b, Zo);
+        if (T.ok()) {
+            hipLaunchKernelGGL(k_train_lv_relu, TrainStep::blocks(nH4), dim3(256), 0, stream, (const float4*)Zo, (float4*)Ao, nH4);
+            T.launched();
+        }
+        T.gemm(Ao, Hi, 1, 1, lv->p->own2_w, 1, Hi, 1, L, n, hw4, Hi, lv->p->own2_b, 1, Hi, nullptr);
+        if (T.ok()) {
+            uint32_t* cnt = (uint32_t*)(T.ws + o_cnt);
+            hipLaunchKernelGGL(k_train_own_count, dim3(lc.B), dim3(256), 0, stream, lc, (const int8_t*)T.ro.cheese_outcomes, cnt);
+            T.launched();
+            if (T.ok() && lv->out && lv->out->ownership_logits)
+                T.err = hipMemcpyAsync(lv->out->ownership_logits, L, (size_t)n * hw4 * 4, hipMemcpyDeviceToDevice, stream);
+        }
+        if (T.ok()) {
+            uint32_t* cnt = (uint32_t*)(T.ws + o_cnt);
+            LvOwn a;
+            a.l = L;
+            a.co = T.ro.cheese_outcomes;
+            a.count_part = cnt;
+            a.ce_part = T.d(o_ce);
+            a.ow = lv->ow;
+            hipLaunchKernelGGL(k_train_own_cells, dim3(lc.B), dim3(256), 0, stream, lc, a);
+            hipLaunchKernelGGL(k_train_lv_loss_sum, dim3(1), dim3(320), 0, stream, (const double*)T.d(T.o_lpart),
+                               (uint32_t)T.head_blocks, (uint32_t)n, (const double*)T.d(o_ce), (const uint32_t*)cnt, (uint32_t)lc.B,
+                               pw, vw, lv->ow, T.f(o_loss7), out ? out->losses : nullptr);
+            T.launched();
+        }
     }
     // backward
     T.grad_w(dOut, 12, A2, Hi, n, sp, {g.p1_w, g.p1_b, 5}, {g.p2_w, g.p2_b, 5}, {g.value_w, g.value_b, 2});
+    if (lv) {  // the ownership head's: its four gradients, and dZo Wo0 where the trunk's backward adds the three heads' part
+        const size_t nH4 = (size_t)n * H / 4;
+        T.grad_w(L, hw4, Ao, Hi, n, sp, {lv->g->own2_w, lv->g->own2_b, hw4});
+        T.grad_in(L, n, lv->p->own2_w, Hi, dAo, hw4);
+        if (T.ok()) {
+            hipLaunchKernelGGL(k_train_lv_relu_bwd, TrainStep::blocks(nH4), dim3(256), 0, stream, (const float4*)Zo, (float4*)dAo, nH4);
+            T.launched();
+        }
+        T.grad_w(dAo, Hi, A2, Hi, n, sp, {lv->g->own0_w, lv->g->own0_b, Hi});
+        T.grad_in(dAo, n, lv->p->own0_w, Hi, dZ2);
+    }
     bn_backward(1, true, Z2, A2, dZ2, p.bn2_w, g.bn2_w, g.bn2_b);
     T.grad_w(dZ2, Hi, A1, Hi, n, sp, {g.trunk4_w, g.trunk4_b, Hi});
     T.grad_in(dZ2, n, p.trunk4_w, Hi, dZ1);
@@ -5223,6 +5299,18 @@ int ar_rows_grad_mlp(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_di
                                                out, (hipStream_t)stream)
                             : rows_grad_mlp<4>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight, value_weight,
                                                out, (hipStream_t)stream);
+}
+
+int ar_rows_grad_local_value(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArLvTensors* params,
+                             const ArLvTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
+                             float ownership_weight, const ArLvTrainOut* out, void* stream) {
+    if (!s || !s->impl || !params || !grads) return fail(AR_E_INVALID, "null argument");
+    const LvStep lv{params, grads, ownership_weight, out};
+    const ArMlpTensors &p = *(const ArMlpTensors*)params, &g = *(const ArMlpTensors*)grads;
+    return s->impl->nw == 1 ? rows_grad_mlp<1>(*s->impl, first, n, hidden_dim, p, g, running, policy_weight, value_weight,
+                                               (const ArTrainOut*)out, (hipStream_t)stream, &lv)
+                            : rows_grad_mlp<4>(*s->impl, first, n, hidden_dim, p, g, running, policy_weight, value_weight,
+                                               (const ArTrainOut*)out, (hipStream_t)stream, &lv);
 }
 
 int ar_rows_grad_symmetric(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArSymTensors* params,

@@ -150,11 +150,12 @@ __device__ inline double train_col_total(const double* part, int P, int H, int c
     return s;
 }
 
-enum { TC_SUM = 0, TC_SQ = 1, TC_DHEAD = 2, TC_DTRUNK = 3 };
+// TC_DHEAD_ADD (train_lv.h): DHEAD with what another consumer of the activation already left in d added before the mask
+enum { TC_SUM = 0, TC_SQ = 1, TC_DHEAD = 2, TC_DTRUNK = 3, TC_DHEAD_ADD = 4 };
 struct TrainColArgs {
     const float* z;        // SUM, SQ, DHEAD, DTRUNK: the layer's pre-BatchNorm values
     const float* act;      // DHEAD, DTRUNK: relu(bn(z)), whose sign is the mask
-    float* d;              // DHEAD: dY written; DTRUNK: dA masked in place
+    float* d;              // DHEAD: dY written; DTRUNK: dA masked in place; DHEAD_ADD: the other part of dA in, dY out
     const float* dout;     // DHEAD: [n][12]
     const float *w_p1, *w_p2, *w_v;  // DHEAD: the head weights
     const double* sum_in;  // SQ: the partial sums of z
@@ -177,7 +178,7 @@ __global__ void __launch_bounds__(256) k_train_colsum(TrainCols t, TrainColArgs 
             mu = a.mu[col];
             rstd = a.rstd[col];
         }
-        if (MODE == TC_DHEAD) {
+        if (MODE == TC_DHEAD || MODE == TC_DHEAD_ADD) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) {
                 w[k] = a.w_p1[(size_t)k * t.H + col];
@@ -195,11 +196,12 @@ __global__ void __launch_bounds__(256) k_train_colsum(TrainCols t, TrainColArgs 
                 acc0 += (double)d * (double)d;
             } else {
                 float dy;
-                if (MODE == TC_DHEAD) {
+                if (MODE == TC_DHEAD || MODE == TC_DHEAD_ADD) {
                     const float* o = a.dout + (size_t)r * 12;
                     dy = 0.0f;
 #pragma unroll
                     for (int k = 0; k < 12; ++k) dy += o[k] * w[k];
+                    if (MODE == TC_DHEAD_ADD) dy += a.d[i];
                 } else
                     dy = a.d[i];
                 dy = a.act[i] > 0.0f ? dy : 0.0f;

@@ -168,12 +168,31 @@ def sym_param_shapes(width: int, height: int, hidden_dim: int) -> dict:
     return shapes
 
 
+# LocalValueMLP's parameters (alpharat/nn/models/local_value.py) in torch's named_parameters() order, which is the order of
+# ArLvTensors (_lib.LV_TENSORS): PyRatMLP's fourteen, then the ownership head's four. Its running statistics are the MLP's.
+LV_PARAM_KEYS = MLP_PARAM_KEYS + ("ownership_head.0.weight", "ownership_head.0.bias", "ownership_head.2.weight",
+                                  "ownership_head.2.bias")
+LV_TRAIN_OUT_KEYS = TRAIN_OUT_KEYS + ("ownership_logits",)
+
+
+def lv_param_shapes(width: int, height: int, hidden_dim: int) -> dict:
+    """The shape of every tensor of ``LV_PARAM_KEYS`` and ``MLP_RUNNING_KEYS``."""
+    shapes = mlp_param_shapes(width, height, hidden_dim)
+    shapes.update({"ownership_head.0.weight": (hidden_dim, hidden_dim), "ownership_head.0.bias": (hidden_dim,),
+                   "ownership_head.2.weight": (4 * width * height, hidden_dim), "ownership_head.2.bias": (4 * width * height,)})
+    return shapes
+
+
 # What a training step is made of, per architecture: the key tuples and shapes that check_grad_tensors holds the caller's
-# tensors to, and the two ctypes structs and the symbol that RowSet._grad_into hands them to.
+# tensors to, the two ctypes structs and the symbol that RowSet._grad_into hands them to, and its outputs: their struct,
+# their keys and the number of losses.
 _GRAD_STEPS = {
-    "mlp": (MLP_PARAM_KEYS, MLP_RUNNING_KEYS, mlp_param_shapes, _lib.ArMlpTensors, _lib.ArMlpBnStats, "ar_rows_grad_mlp"),
+    "mlp": (MLP_PARAM_KEYS, MLP_RUNNING_KEYS, mlp_param_shapes, _lib.ArMlpTensors, _lib.ArMlpBnStats, "ar_rows_grad_mlp",
+            _lib.ArTrainOut, TRAIN_OUT_KEYS, 6),
     "symmetric": (SYM_PARAM_KEYS, SYM_RUNNING_KEYS, sym_param_shapes, _lib.ArSymTensors, _lib.ArSymBnStats,
-                  "ar_rows_grad_symmetric"),
+                  "ar_rows_grad_symmetric", _lib.ArTrainOut, TRAIN_OUT_KEYS, 6),
+    "local_value": (LV_PARAM_KEYS, MLP_RUNNING_KEYS, lv_param_shapes, _lib.ArLvTensors, _lib.ArMlpBnStats,
+                    "ar_rows_grad_local_value", _lib.ArLvTrainOut, LV_TRAIN_OUT_KEYS, 7),
 }
 
 
@@ -181,19 +200,22 @@ def check_grad_tensors(params: dict, grads: dict, running, out, n: int, width: i
                        architecture: str = "mlp") -> None:
     """``RowSet.grad_mlp_into``'s conditions on its tensors (``ValueError``), in the manner of ``check_out_tensors``; no
     device and no library is needed. ``architecture="symmetric"``: ``RowSet.grad_symmetric_into``'s, over
-    ``SYM_PARAM_KEYS`` and ``SYM_RUNNING_KEYS``."""
+    ``SYM_PARAM_KEYS`` and ``SYM_RUNNING_KEYS``. ``architecture="local_value"``: ``RowSet.grad_local_value_into``'s, over
+    ``LV_PARAM_KEYS`` and ``MLP_RUNNING_KEYS``, with seven losses and ``ownership_logits`` ``(n, height, width, 4)``."""
     import torch
 
     if architecture not in _GRAD_STEPS:
         raise ValueError(f"no training step for architecture {architecture!r}")
     param_keys, running_keys, shapes_of = _GRAD_STEPS[architecture][:3]
+    out_keys, n_losses = _GRAD_STEPS[architecture][7:9]
     shapes = shapes_of(width, height, hidden_dim)
-    out_shapes = dict(losses=(6,), logits_p1=(n, 5), logits_p2=(n, 5), value_p1=(n,), value_p2=(n,))
+    out_shapes = dict(losses=(n_losses,), logits_p1=(n, 5), logits_p2=(n, 5), value_p1=(n,), value_p2=(n,),
+                      ownership_logits=(n, height, width, 4))
     groups = [("params", params, param_keys, shapes, True), ("grads", grads, param_keys, shapes, True)]
     if running is not None:
         groups.append(("running", running, running_keys, shapes, True))
     if out is not None:
-        groups.append(("out", out, TRAIN_OUT_KEYS, out_shapes, False))
+        groups.append(("out", out, out_keys, out_shapes, False))
     for what, d, keys, want, required in groups:
         for k in keys:
             t = d.get(k)
@@ -319,8 +341,20 @@ class RowSet:
         ``sym_param_shapes(width, height, hidden_dim)`` gives; everything else as there."""
         self._grad_into("symmetric", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream)
 
+    def grad_local_value_into(self, first: int, n: int, hidden_dim: int, params: dict, grads: dict, running,
+                              policy_weight: float, value_weight: float, ownership_weight: float, out, stream=None) -> None:
+        """``grad_mlp_into`` for LocalValueMLP (``ar_rows_grad_local_value``): ``params`` and ``grads`` are the eighteen
+        tensors under ``LV_PARAM_KEYS``, ``running`` the four ``MLP_RUNNING_KEYS`` or ``None``, of the shapes
+        ``lv_param_shapes(width, height, hidden_dim)`` gives. The loss has the third term, ``ownership_weight`` times the
+        cross-entropy of the ownership head over the window's active cells. ``out``: any of ``LV_TRAIN_OUT_KEYS`` --
+        ``losses`` is ``(7,)``, the six and ``loss_ownership``; ``ownership_logits`` ``(n, height, width, 4)``. The
+        workspace is the MLP step's plus ``3 n H + 4 n h w`` floats (the logits alone are 268 MB at 65536 rows of 16x16).
+        Everything else as there."""
+        self._grad_into("local_value", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream,
+                        (float(ownership_weight),))
+
     def _grad_into(self, architecture: str, first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out,
-                   stream) -> None:
+                   stream, more_weights: tuple = ()) -> None:
         import torch
 
         first, n, hidden_dim = int(first), int(n), int(hidden_dim)
@@ -328,18 +362,17 @@ class RowSet:
             raise ValueError("first and n must not be negative, hidden_dim positive")
         check_grad_tensors(params, grads, running, out, n, self.width, self.height, hidden_dim,
                            torch.device("cuda", self.device_index), architecture=architecture)
-        param_keys, running_keys, _, Tensors, BnStats, symbol = _GRAD_STEPS[architecture]
+        param_keys, running_keys, _, Tensors, BnStats, symbol, Out, out_keys, _ = _GRAD_STEPS[architecture]
         handle = self._handle()
         if stream is None:
             stream = torch.cuda.current_stream(self.device_index)
         p = Tensors(*[params[k].data_ptr() for k in param_keys])
         g = Tensors(*[grads[k].data_ptr() for k in param_keys])
         r = BnStats(*[running[k].data_ptr() for k in running_keys]) if running is not None else None
-        o = (_lib.ArTrainOut(*[out[k].data_ptr() if out.get(k) is not None else None for k in TRAIN_OUT_KEYS])
-             if out is not None else None)
+        o = Out(*[out[k].data_ptr() if out.get(k) is not None else None for k in out_keys]) if out is not None else None
         _lib.check(getattr(_lib.load(), symbol)(handle, first, n, hidden_dim, C.byref(p), C.byref(g),
                                                 C.byref(r) if r is not None else None, float(policy_weight),
-                                                float(value_weight), C.byref(o) if o is not None else None,
+                                                float(value_weight), *more_weights, C.byref(o) if o is not None else None,
                                                 C.c_void_p(stream.cuda_stream)))
 
     def validate(self, net, rows, chunk_rows: int = 0, return_rows: bool = False):

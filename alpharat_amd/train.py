@@ -1,4 +1,5 @@
-"""The training step of PyRatMLP or SymmetricMLP over a device-resident ``RowSet``: forward, losses and gradients in one call.
+"""The training step of PyRatMLP, SymmetricMLP or LocalValueMLP over a device-resident ``RowSet``: forward, losses and
+gradients in one call.
 
 The reference's loop (alpharat/nn/training/loop.py) gathers a batch, runs ``model(obs)`` in training mode,
 ``compute_mlp_losses`` and ``loss.backward()``. ``MLPGradStep.step`` does the three for rows ``first .. first + n`` of the
@@ -10,12 +11,13 @@ schedule and the checkpoints stay the trainer's::
     for n, losses in train_dataset.grad_iter(step, 4096, epoch=epoch, seed=seed):
         optimizer.step()
 
-Supported: PyRatMLP (``architecture: mlp``, ``MLPGradStep``) and SymmetricMLP (``architecture: symmetric``,
-``SymmetricGradStep`` over ``ar_rows_grad_symmetric``, alpharat_amd/csrc/train_sym.h; same loop, same contract) in float32
-with ``dropout`` 0.0 -- the architectures' default -- and a hidden width that is a multiple of 32, at most 256.
-LocalValueMLP is refused: its loss has a third term (the ownership head). AMP, dropout and the other architectures are not
-built. (The reference's configs/model/symmetric.yaml sets ``dropout: 0.1``: a model built from it is refused until that is
-0.0.)
+Supported: PyRatMLP (``architecture: mlp``, ``MLPGradStep``), SymmetricMLP (``architecture: symmetric``,
+``SymmetricGradStep`` over ``ar_rows_grad_symmetric``, alpharat_amd/csrc/train_sym.h) and LocalValueMLP (``architecture:
+local_value``, ``LocalValueGradStep`` over ``ar_rows_grad_local_value``, alpharat_amd/csrc/train_lv.h: the MLP's step plus
+the ownership head and ``ownership_weight`` times its masked cross-entropy, seven losses) -- same loop, same contract -- in
+float32 with ``dropout`` 0.0 -- the architectures' default -- and a hidden width that is a multiple of 32, at most 256. AMP,
+dropout and the other architectures are not built. (The reference's configs/model/symmetric.yaml sets ``dropout: 0.1``: a
+model built from it is refused until that is 0.0.)
 
 ``trunk.0.bias`` and ``trunk.4.bias`` -- and SymmetricMLP's ``shared_encoder.0.bias`` and ``player_encoder.0.bias`` -- sit
 in front of a BatchNorm, so their true gradient is zero and what any implementation writes there is rounding noise
@@ -26,18 +28,19 @@ torch ships its own copy of the HIP runtime and a process brings up only one: im
 """
 from __future__ import annotations
 
-from .shards import MLP_PARAM_KEYS, MLP_RUNNING_KEYS, SYM_BN_MODULES, SYM_PARAM_KEYS, SYM_RUNNING_KEYS, RowSet
+from .shards import LV_PARAM_KEYS, MLP_PARAM_KEYS, MLP_RUNNING_KEYS, SYM_BN_MODULES, SYM_PARAM_KEYS, SYM_RUNNING_KEYS, RowSet
 
 _PREFIX = "_orig_mod."  # torch.compile's wrapper, stripped as weights.py does
 
 
 class _GradStep:
-    """What both steps do. A subclass names its architecture (``_NAME``, for the messages), its parameter and
+    """What the steps do. A subclass names its architecture (``_NAME``, for the messages), its parameter and
     running-statistic keys, the ``(num_batches_tracked key, BatchNorm calls per step)`` pairs and the ``RowSet`` method
     that launches it; ``_read_dims`` takes the widths from the checked parameters and ``_check_board`` holds them
-    against a row set's board."""
+    against a row set's board. ``_N_LOSSES``, ``_weights`` and ``_more_outputs`` are the MLP's unless a loss has more terms."""
 
     _NAME = _PARAM_KEYS = _RUNNING_KEYS = _TRACKED = _ROWSET_METHOD = None
+    _N_LOSSES = 6
 
     def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0) -> None:
         import torch
@@ -74,27 +77,34 @@ class _GradStep:
             raise ValueError(f"{key} has shape {tuple(w.shape)}")
         return w
 
+    def _weights(self) -> tuple:
+        return self.policy_weight, self.value_weight
+
+    def _more_outputs(self, rowset: RowSet, n: int, device) -> dict:
+        return {}
+
     def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
         import torch
 
         self._check_board(rowset)
         device = torch.device("cuda", rowset.device_index)
         n = int(n)
-        out = dict(losses=torch.empty(6, device=device, dtype=torch.float32))
+        out = dict(losses=torch.empty(self._N_LOSSES, device=device, dtype=torch.float32))
         if outputs:
             out.update(logits_p1=torch.empty((n, 5), device=device), logits_p2=torch.empty((n, 5), device=device),
                        value_p1=torch.empty(n, device=device), value_p2=torch.empty(n, device=device))
+            out.update(self._more_outputs(rowset, n, device))
         training = bool(self.model.training)
         params = {k: p.data for k, p in self.params.items()}
         getattr(rowset, self._ROWSET_METHOD)(first, n, self.hidden_dim, params, self.grads, self.running if training else None,
-                                             self.policy_weight, self.value_weight, out)
+                                             *self._weights(), out)
         for k, p in self.params.items():
             p.grad = self.grads[k]
         if training:
             for t, calls in self._tracked:
                 t.add_(calls)
         if outputs:
-            return out["losses"], out["logits_p1"], out["logits_p2"], out["value_p1"], out["value_p2"]
+            return tuple(out.values())
         return out["losses"]
 
 
@@ -157,3 +167,45 @@ class SymmetricGradStep(_GradStep):
         ``num_batches_tracked`` grows by one for ``shared_encoder.1`` and by two for the other three modules. Returns the
         ``(6,)`` losses, with ``outputs`` also the four training-mode outputs."""
         return super().step(rowset, first, n, outputs)
+
+
+class LocalValueGradStep(MLPGradStep):
+    """``MLPGradStep`` for LocalValueMLP: ``model`` is an ``nn.Module`` whose ``state_dict()`` has LocalValueMLP's keys --
+    PyRatMLP's and the four of ``ownership_head.0`` / ``ownership_head.2`` (an ``_orig_mod.`` prefix is stripped; the
+    ``outcome_values`` buffer is not read: it only serves the model's ``ownership_value`` output). ``ValueError`` for a
+    ``Dropout`` with ``p != 0``, a missing key (a PyRatMLP lacks the head), or a parameter or BatchNorm buffer that is not
+    float32 or not contiguous. One persistent gradient tensor per parameter is allocated here."""
+
+    _NAME, _PARAM_KEYS, _ROWSET_METHOD, _N_LOSSES = "LocalValueMLP", LV_PARAM_KEYS, "grad_local_value_into", 7
+
+    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0, ownership_weight: float = 1.0) -> None:
+        self.ownership_weight = float(ownership_weight)
+        super().__init__(model, policy_weight, value_weight)
+
+    def _refuse(self, named: dict, buffers: dict) -> None:
+        pass
+
+    def _read_dims(self) -> None:
+        super()._read_dims()
+        self.cells = int(self._weight("ownership_head.2.weight").shape[0])
+
+    def _check_board(self, rowset: RowSet) -> None:
+        super()._check_board(rowset)
+        if 4 * rowset.width * rowset.height != self.cells:
+            raise ValueError(f"ownership_head.2.weight has {self.cells} rows, a {rowset.width}x{rowset.height} board has "
+                             f"4 * {rowset.width * rowset.height} cell logits")
+
+    def _weights(self) -> tuple:
+        return self.policy_weight, self.value_weight, self.ownership_weight
+
+    def _more_outputs(self, rowset: RowSet, n: int, device) -> dict:
+        import torch
+
+        return dict(ownership_logits=torch.empty((n, rowset.height, rowset.width, 4), device=device))
+
+    def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
+        """``MLPGradStep.step`` under the same contract, with the third term in the loss. Returns the ``(7,)`` tensor
+        loss_p1, loss_p2, loss_value_p1, loss_value_p2, loss_value, loss, loss_ownership -- ``loss`` includes
+        ``ownership_weight * loss_ownership``; with ``outputs`` ``(losses, logits_p1, logits_p2, value_p1, value_p2,
+        ownership_logits (n, h, w, 4))``, the training-mode outputs."""
+        return _GradStep.step(self, rowset, first, n, outputs)

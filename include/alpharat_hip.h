@@ -550,6 +550,46 @@ int ar_rows_grad_symmetric(ArRowSet* set, uint64_t first, uint64_t n, uint32_t h
                            const ArSymTensors* grads, const ArSymBnStats* running, float policy_weight, float value_weight,
                            const ArTrainOut* out, void* stream);
 
+/* ---- training gradients of LocalValueMLP over stored rows (nn/models/local_value.py in training mode, the loss of
+ * architectures/local_value/loss.py, loss.backward()) ---------------------------------------------------------------------
+ * ar_rows_grad_mlp for the third architecture of the family: the same rows, trunk, heads, BatchNorm arithmetic, streams,
+ * workspace (the three steps share the set's one workspace and wait for each other) and refusals, plus the ownership head
+ * on the trunk output A2 and its loss, over the window's cheese outcomes as ar_rows_build_device writes them (swapped rows:
+ * classes 0 and 3 exchanged). With hw = h*w:
+ *   Zo = A2 Wo0^T + bo0 [n][H]     Ao = relu(Zo)     L = Ao Wo2^T + bo2 [n][hw][4], class fastest
+ *   a cell is active iff its cheese outcome is >= 0; C = the active cells of the window
+ *   loss_ownership = (1/C) sum over active cells of logsumexp(l) - l[outcome]        (0 when C = 0)
+ *   loss = policy_weight (loss_p1 + loss_p2) + value_weight loss_value + ownership_weight loss_ownership
+ * The logits' gradient is (ownership_weight / C)(softmax(l) - onehot(outcome)) for an active cell and exactly 0 for any
+ * other; C = 0 writes zeros into the head's four gradients (the reference's early return), and no NaN anywhere. The cells
+ * are counted in integers, their terms added in double over a fixed partition in a fixed order: the same request gives the
+ * same bytes. */
+typedef struct ArLvTensors { /* device pointers, f32, C order: LocalValueMLP's parameters in named_parameters() order */
+    float *trunk0_w, *trunk0_b;       /* ArMlpTensors' fourteen, as there */
+    float *bn1_w, *bn1_b;
+    float *trunk4_w, *trunk4_b;
+    float *bn2_w, *bn2_b;
+    float *p1_w, *p1_b, *p2_w, *p2_b;
+    float *value_w, *value_b;
+    float *own0_w, *own0_b;           /* [H][H], [H]        ownership_head.0 */
+    float *own2_w, *own2_b;           /* [4hw][H], [4hw]    ownership_head.2 */
+} ArLvTensors;
+typedef struct ArLvTrainOut { /* device memory of the caller's, any may be NULL */
+    float* losses;                /* [7] ArTrainOut's six (loss with the third term), then loss_ownership */
+    float *logits_p1, *logits_p2; /* [n][5] the training-mode outputs */
+    float *value_p1, *value_p2;   /* [n] */
+    float* ownership_logits;      /* [n][h][w][4] the forward's L, copied out before dL takes its place */
+} ArLvTrainOut;
+/* As ar_rows_grad_mlp in every other respect: `grads` overwritten; running and out may be NULL; launched on `stream` with
+ * no synchronisation (the copy of the logits is a device-to-device copy on that stream). hidden_dim a multiple of 32, at
+ * most 256; 2 to 65536 rows; any board of the set. The workspace is the MLP step's plus 3 n H + 4 n hw floats and a few KB
+ * of partial sums: about 46 MB at n = 4096, 7x7, H = 256, and at the cap of 65536 rows of 16x16 about 1.4 GB, of which L
+ * is 268 MB. AR_E_INVALID before any launch, nothing written, for the same list (here eighteen tensors, four running
+ * statistics, six outputs). */
+int ar_rows_grad_local_value(ArRowSet* set, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArLvTensors* params,
+                             const ArLvTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
+                             float ownership_weight, const ArLvTrainOut* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
