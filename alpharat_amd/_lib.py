@@ -242,6 +242,10 @@ class ArLvTrainOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("losses", "logits_p1", "logits_p2", "value_p1", "value_p2", "ownership_logits")]
 
 
+class ArTrainDropout(C.Structure):
+    _fields_ = [("p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64)]
+
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -296,6 +300,17 @@ EXPORTS = {
     "ar_rows_grad_local_value": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArLvTensors),
                                            C.POINTER(ArLvTensors), C.POINTER(ArMlpBnStats), C.c_float, C.c_float, C.c_float,
                                            C.POINTER(ArLvTrainOut), C.c_void_p]),
+    "ar_rows_grad_mlp_dropout": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArMlpTensors),
+                                           C.POINTER(ArMlpTensors), C.POINTER(ArMlpBnStats), C.c_float, C.c_float,
+                                           C.POINTER(ArTrainOut), C.POINTER(ArTrainDropout), C.c_void_p]),
+    "ar_rows_grad_symmetric_dropout": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArSymTensors),
+                                                 C.POINTER(ArSymTensors), C.POINTER(ArSymBnStats), C.c_float, C.c_float,
+                                                 C.POINTER(ArTrainOut), C.POINTER(ArTrainDropout), C.c_void_p]),
+    "ar_rows_grad_local_value_dropout": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArLvTensors),
+                                                   C.POINTER(ArLvTensors), C.POINTER(ArMlpBnStats), C.c_float, C.c_float,
+                                                   C.c_float, C.POINTER(ArLvTrainOut), C.POINTER(ArTrainDropout), C.c_void_p]),
+    "ar_train_dropout_mask": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p,
+                                        C.c_void_p]),
 }
 
 _lib = None

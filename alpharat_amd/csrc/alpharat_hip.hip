@@ -3262,6 +3262,32 @@ struct TrainStep {
     RowOut ro{};
     hipError_t err = hipSuccess;
     int before = 0;  // the caller's framework keeps its own current device
+    // dropout (dev_dropout.h): off unless check_dropout saw a p above 0
+    bool dropping = false;
+    float drop_p = 0.0f;
+    uint64_t drop_seed = 0, drop_step = 0;
+
+    // the dropout's refusal, before any launch; NULL or p == 0: the step without dropout, launch for launch
+    int check_dropout(const ArTrainDropout* dr) {
+        if (!dr) return AR_OK;
+        if (!(dr->p >= 0.0f) || !(dr->p < 1.0f))  // (NaN fails both)
+            return fail(AR_E_INVALID, "dropout p must be in [0, 1) (got " + std::to_string(dr->p) + ")");
+        dropping = dr->p > 0.0f;
+        drop_p = dr->p;
+        drop_seed = dr->seed;
+        drop_step = dr->step;
+        return AR_OK;
+    }
+    // (key, thr, scale) of the dropout behind BatchNorm call `call`, formed once per call on the host; without dropout
+    // nothing is hashed: keep everything at scale 1, which no kernel of that path reads
+    TrainDrop drop_of(int call) const {
+        TrainDrop d{0, 0, 1.0f};
+        if (!dropping) return d;
+        d.key = dropout_key(drop_seed, drop_step, (uint64_t)call);
+        d.thr = dropout_thr(drop_p);
+        d.scale = dropout_scale(drop_p);
+        return d;
+    }
 
     // the refusals; `params`, `grads`: `count` pointers named by `names`; `running`: n_running pointers (0: none given)
     int check(uint64_t first, uint64_t n64, uint32_t H_, const char* const* names, float* const* params, float* const* grads,
@@ -3424,8 +3450,9 @@ struct TrainStep {
         launched();
     }
     // act = relu(bn(z)) over n rows at z with the batch's statistics (two passes over z); mu and rstd kept for the backward
+    // `dr`: the dropout behind it (null: none)
     void bn_forward(const float* z, const float* gamma, const float* beta, float* act, double* mu, float* rstd, float* run_mean,
-                    float* run_var, double* part_sum, double* part_sq) {
+                    float* run_var, double* part_sum, double* part_sq, const TrainDrop* dr = nullptr) {
         if (err != hipSuccess) return;
         TrainColArgs a;
         memset(&a, 0, sizeof a);
@@ -3435,14 +3462,19 @@ struct TrainStep {
         a.sum_in = part_sum;
         a.part0 = part_sq;
         hipLaunchKernelGGL(k_train_colsum<TC_SQ>, cgrid(), dim3(256), 0, stream, tc, a);
-        hipLaunchKernelGGL(k_train_bn_apply, cgrid(), dim3(256), 0, stream, tc, z, (const double*)part_sum, (const double*)part_sq,
-                           gamma, beta, act, mu, rstd, run_mean, run_var);
+        if (dr)
+            hipLaunchKernelGGL(k_train_bn_apply_drop, cgrid(), dim3(256), 0, stream, tc, z, (const double*)part_sum,
+                               (const double*)part_sq, gamma, beta, act, mu, rstd, run_mean, run_var, *dr);
+        else
+            hipLaunchKernelGGL(k_train_bn_apply, cgrid(), dim3(256), 0, stream, tc, z, (const double*)part_sum,
+                               (const double*)part_sq, gamma, beta, act, mu, rstd, run_mean, run_var);
         launched();
     }
     // the backward of one BatchNorm call: a column kernel leaves the masked dy in a.d and its two column sums in a.part0,
-    // a.part1 (bn_backward_trunk: from dA already in a.d; a head's own kernel is its driver's), then bn_bwd puts dz there
+    // a.part1 (bn_backward_trunk: from dA already in a.d; a head's own kernel is its driver's), then bn_bwd puts dz there.
+    // `dr`: the dropout behind the call's activation (null: none); its scale goes with the arguments.
     static TrainColArgs backward_args(const float* z, const float* act, float* d, const double* mu, const float* rstd,
-                                      double* part0, double* part1) {
+                                      double* part0, double* part1, const TrainDrop* dr = nullptr) {
         TrainColArgs a;
         memset(&a, 0, sizeof a);
         a.z = z;
@@ -3452,6 +3484,7 @@ struct TrainStep {
         a.rstd = rstd;
         a.part0 = part0;
         a.part1 = part1;
+        a.scale = dr ? dr->scale : 1.0f;
         return a;
     }
     void bn_bwd(const float* z, float* d, const double* part0, const double* part1, const double* mu, const float* rstd,
@@ -3461,7 +3494,8 @@ struct TrainStep {
     }
     void bn_backward_trunk(const TrainColArgs& a, const float* gamma, float* dgamma, float* dbeta) {
         if (err != hipSuccess) return;
-        hipLaunchKernelGGL(k_train_colsum<TC_DTRUNK>, cgrid(), dim3(256), 0, stream, tc, a);
+        if (dropping) hipLaunchKernelGGL((k_train_colsum<TC_DTRUNK, true>), cgrid(), dim3(256), 0, stream, tc, a);
+        else hipLaunchKernelGGL(k_train_colsum<TC_DTRUNK>, cgrid(), dim3(256), 0, stream, tc, a);
         bn_bwd(a.z, a.d, a.part0, a.part1, a.mu, a.rstd, gamma, dgamma, dbeta);
     }
     // the six losses from the heads' partial sums (called behind the driver's heads launch)
@@ -3486,7 +3520,7 @@ struct LvStep {
 template <int NW>
 int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const ArMlpTensors& p, const ArMlpTensors& g,
                   const ArMlpBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream,
-                  const LvStep* lv = nullptr) {
+                  const LvStep* lv = nullptr, const ArTrainDropout* dropout = nullptr) {
     static_assert(sizeof(ArMlpTensors) == 14 * sizeof(float*), "fourteen pointers");
     static_assert(sizeof(ArMlpBnStats) == 4 * sizeof(float*), "four pointers");
     static_assert(sizeof(ArLvTensors) == 18 * sizeof(float*) && offsetof(ArLvTensors, own0_w) == sizeof(ArMlpTensors),
@@ -3499,6 +3533,7 @@ int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const A
                     : T.check(first, n64, H, kMlpTensorNames, (float* const*)&p, (float* const*)&g, 14, (float* const*)run,
                               run ? 4 : 0, out))
         return rc;
+    if (int rc = T.check_dropout(dropout)) return rc;
     if (lv && lv->out && lv->out->ownership_logits)
         if (int rc = rows_check_device_ptr(R, lv->out->ownership_logits, 4, "output")) return rc;
     const int n = T.n, D = (int)rows_obs_dim(R.hw), Hi = T.H, hw4 = 4 * (int)R.hw;
@@ -3525,21 +3560,26 @@ int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const A
     T.wpart = T.f(o_wpart);
     T.bpart = T.f(o_bpart);
     auto part = [&](int i) { return parts + (size_t)i * TRAIN_MAX_PARTS * H; };
-    // z -> relu(bn(z)), layer 0 / 1
+    // z -> relu(bn(z)), layer 0 / 1, which is the BatchNorm call's index for the dropout behind it
     auto bn_forward = [&](int layer, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
+        const TrainDrop dr = T.drop_of(layer);
         T.bn_forward(z, gamma, beta, act, means + (size_t)layer * H, rstds + (size_t)layer * H, rm, rv, part(2 * layer),
-                     part(2 * layer + 1));
+                     part(2 * layer + 1), T.dropping ? &dr : nullptr);
     };
     auto bn_backward = [&](int layer, bool head, const float* z, const float* act, float* d, const float* gamma, float* dgamma,
                            float* dbeta) {
         if (!T.ok()) return;
-        TrainColArgs a = TrainStep::backward_args(z, act, d, means + (size_t)layer * H, rstds + (size_t)layer * H, part(4), part(5));
+        const TrainDrop dr = T.drop_of(layer);
+        TrainColArgs a = TrainStep::backward_args(z, act, d, means + (size_t)layer * H, rstds + (size_t)layer * H, part(4), part(5),
+                                                  T.dropping ? &dr : nullptr);
         a.dout = dOut;
         a.w_p1 = p.p1_w;
         a.w_p2 = p.p2_w;
         a.w_v = p.value_w;
         if (!head) return T.bn_backward_trunk(a, gamma, dgamma, dbeta);
-        if (lv) hipLaunchKernelGGL(k_train_colsum<TC_DHEAD_ADD>, T.cgrid(), dim3(256), 0, stream, T.tc, a);  // d holds dZo Wo0
+        if (lv && T.dropping) hipLaunchKernelGGL((k_train_colsum<TC_DHEAD_ADD, true>), T.cgrid(), dim3(256), 0, stream, T.tc, a);
+        else if (lv) hipLaunchKernelGGL(k_train_colsum<TC_DHEAD_ADD>, T.cgrid(), dim3(256), 0, stream, T.tc, a);  // d holds dZo Wo0
+        else if (T.dropping) hipLaunchKernelGGL((k_train_colsum<TC_DHEAD, true>), T.cgrid(), dim3(256), 0, stream, T.tc, a);
         else hipLaunchKernelGGL(k_train_colsum<TC_DHEAD>, T.cgrid(), dim3(256), 0, stream, T.tc, a);
         T.bn_bwd(z, d, part(4), part(5), a.mu, a.rstd, gamma, dgamma, dbeta);
     };
@@ -3626,12 +3666,14 @@ int rows_grad_mlp(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const A
 // P1's n, then P2's.
 template <int NW>
 int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, const ArSymTensors& p, const ArSymTensors& g,
-                        const ArSymBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream) {
+                        const ArSymBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream,
+                        const ArTrainDropout* dropout = nullptr) {
     static_assert(sizeof(ArSymTensors) == 20 * sizeof(float*), "twenty pointers");
     static_assert(sizeof(ArSymBnStats) == 8 * sizeof(float*), "eight pointers");
     float* const* rs = (float* const*)run;  // se mean, var; pe; trunk.1; trunk.5
     TrainStep T{R, stream};
     if (int rc = T.check(first, n64, H, kSymTensorNames, (float* const*)&p, (float* const*)&g, 20, rs, run ? 8 : 0, out)) return rc;
+    if (int rc = T.check_dropout(dropout)) return rc;
     const int n = T.n, n2 = 2 * n, hw = (int)R.hw, Hi = T.H, H2 = 2 * Hi;
     const int Ds = sym_shared_dim(hw), Dp = sym_player_dim(hw);
     // a product is reduced over the n rows of the shared encoder or the 2n of everything else
@@ -3658,7 +3700,9 @@ int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, c
     const size_t half = (size_t)n * H;  // P2's rows of a [2n][H] array
     // one BatchNorm call (0: shared; 1, 2: player_encoder.1 of P1, P2; 3, 4: trunk.1; 5, 6: trunk.5) over n rows at z
     auto bn_forward = [&](int call, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
-        T.bn_forward(z, gamma, beta, act, means + (size_t)call * H, rstds + (size_t)call * H, rm, rv, part(0), part(1));
+        const TrainDrop dr = T.drop_of(call);
+        T.bn_forward(z, gamma, beta, act, means + (size_t)call * H, rstds + (size_t)call * H, rm, rv, part(0), part(1),
+                     T.dropping ? &dr : nullptr);
     };
     // a module called for both players: P1's call, then P2's on top of it
     auto bn_forward2 = [&](int call, const float* z, const float* gamma, const float* beta, float* act, float* rm, float* rv) {
@@ -3672,7 +3716,9 @@ int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, c
         double *p0 = part(2 + 2 * slot), *p1 = part(3 + 2 * slot);
         const double* mu = means + (size_t)call * H;
         const float* rstd = rstds + (size_t)call * H;
-        if (!head) return T.bn_backward_trunk(TrainStep::backward_args(z, act, d, mu, rstd, p0, p1), gamma, dgamma, dbeta);
+        const TrainDrop dr = T.drop_of(call);
+        const TrainDrop* drp = T.dropping ? &dr : nullptr;
+        if (!head) return T.bn_backward_trunk(TrainStep::backward_args(z, act, d, mu, rstd, p0, p1, drp), gamma, dgamma, dbeta);
         SymDHead a;
         a.z = z;
         a.act = act;
@@ -3684,7 +3730,9 @@ int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, c
         a.rstd = rstd;
         a.part0 = p0;
         a.part1 = p1;
-        hipLaunchKernelGGL(k_sym_dhead, T.cgrid(), dim3(256), 0, stream, T.tc, a);
+        a.scale = drp ? drp->scale : 1.0f;
+        if (T.dropping) hipLaunchKernelGGL(k_sym_dhead<true>, T.cgrid(), dim3(256), 0, stream, T.tc, a);
+        else hipLaunchKernelGGL(k_sym_dhead<false>, T.cgrid(), dim3(256), 0, stream, T.tc, a);
         T.bn_bwd(z, d, p0, p1, mu, rstd, gamma, dgamma, dbeta);
     };
     // both calls of a shared module; the module's two gradients from both calls' column sums (k_train_bn_bwd's own go to bnscr)
@@ -5291,36 +5339,86 @@ int ar_rows_build_device(ArRowSet* s, uint64_t first, uint64_t n, const ArTrainR
                             : rows_build_device<4>(*s->impl, first, n, out ? *out : none, (hipStream_t)stream);
 }
 
+int ar_rows_grad_mlp_dropout(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArMlpTensors* params,
+                             const ArMlpTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
+                             const ArTrainOut* out, const ArTrainDropout* dropout, void* stream) {
+    if (!s || !s->impl || !params || !grads) return fail(AR_E_INVALID, "null argument");
+    return s->impl->nw == 1 ? rows_grad_mlp<1>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight, value_weight,
+                                               out, (hipStream_t)stream, nullptr, dropout)
+                            : rows_grad_mlp<4>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight, value_weight,
+                                               out, (hipStream_t)stream, nullptr, dropout);
+}
+
 int ar_rows_grad_mlp(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArMlpTensors* params,
                      const ArMlpTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
                      const ArTrainOut* out, void* stream) {
+    return ar_rows_grad_mlp_dropout(s, first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, nullptr,
+                                    stream);
+}
+
+int ar_rows_grad_local_value_dropout(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArLvTensors* params,
+                                     const ArLvTensors* grads, const ArMlpBnStats* running, float policy_weight,
+                                     float value_weight, float ownership_weight, const ArLvTrainOut* out,
+                                     const ArTrainDropout* dropout, void* stream) {
     if (!s || !s->impl || !params || !grads) return fail(AR_E_INVALID, "null argument");
-    return s->impl->nw == 1 ? rows_grad_mlp<1>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight, value_weight,
-                                               out, (hipStream_t)stream)
-                            : rows_grad_mlp<4>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight, value_weight,
-                                               out, (hipStream_t)stream);
+    const LvStep lv{params, grads, ownership_weight, out};
+    const ArMlpTensors &p = *(const ArMlpTensors*)params, &g = *(const ArMlpTensors*)grads;
+    return s->impl->nw == 1 ? rows_grad_mlp<1>(*s->impl, first, n, hidden_dim, p, g, running, policy_weight, value_weight,
+                                               (const ArTrainOut*)out, (hipStream_t)stream, &lv, dropout)
+                            : rows_grad_mlp<4>(*s->impl, first, n, hidden_dim, p, g, running, policy_weight, value_weight,
+                                               (const ArTrainOut*)out, (hipStream_t)stream, &lv, dropout);
 }
 
 int ar_rows_grad_local_value(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArLvTensors* params,
                              const ArLvTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
                              float ownership_weight, const ArLvTrainOut* out, void* stream) {
+    return ar_rows_grad_local_value_dropout(s, first, n, hidden_dim, params, grads, running, policy_weight, value_weight,
+                                            ownership_weight, out, nullptr, stream);
+}
+
+int ar_rows_grad_symmetric_dropout(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArSymTensors* params,
+                                   const ArSymTensors* grads, const ArSymBnStats* running, float policy_weight, float value_weight,
+                                   const ArTrainOut* out, const ArTrainDropout* dropout, void* stream) {
     if (!s || !s->impl || !params || !grads) return fail(AR_E_INVALID, "null argument");
-    const LvStep lv{params, grads, ownership_weight, out};
-    const ArMlpTensors &p = *(const ArMlpTensors*)params, &g = *(const ArMlpTensors*)grads;
-    return s->impl->nw == 1 ? rows_grad_mlp<1>(*s->impl, first, n, hidden_dim, p, g, running, policy_weight, value_weight,
-                                               (const ArTrainOut*)out, (hipStream_t)stream, &lv)
-                            : rows_grad_mlp<4>(*s->impl, first, n, hidden_dim, p, g, running, policy_weight, value_weight,
-                                               (const ArTrainOut*)out, (hipStream_t)stream, &lv);
+    return s->impl->nw == 1 ? rows_grad_symmetric<1>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight,
+                                                     value_weight, out, (hipStream_t)stream, dropout)
+                            : rows_grad_symmetric<4>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight,
+                                                     value_weight, out, (hipStream_t)stream, dropout);
 }
 
 int ar_rows_grad_symmetric(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArSymTensors* params,
                            const ArSymTensors* grads, const ArSymBnStats* running, float policy_weight, float value_weight,
                            const ArTrainOut* out, void* stream) {
-    if (!s || !s->impl || !params || !grads) return fail(AR_E_INVALID, "null argument");
-    return s->impl->nw == 1 ? rows_grad_symmetric<1>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight,
-                                                     value_weight, out, (hipStream_t)stream)
-                            : rows_grad_symmetric<4>(*s->impl, first, n, hidden_dim, *params, *grads, running, policy_weight,
-                                                     value_weight, out, (hipStream_t)stream);
+    return ar_rows_grad_symmetric_dropout(s, first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out,
+                                          nullptr, stream);
+}
+
+int ar_train_dropout_mask(uint64_t seed, uint64_t step, uint32_t call, uint64_t n, uint32_t hidden_dim, float p,
+                          uint8_t* keep_device, void* stream) {
+    if (!keep_device) return fail(AR_E_INVALID, "null argument");
+    if (!(p >= 0.0f) || !(p < 1.0f)) return fail(AR_E_INVALID, "dropout p must be in [0, 1) (got " + std::to_string(p) + ")");
+    if (n == 0 || n > (uint64_t)TRAIN_MAX_ROWS) return fail(AR_E_INVALID, "1 to 65536 rows a mask");
+    if (hidden_dim == 0 || hidden_dim % 32 != 0 || hidden_dim > 256)
+        return fail(AR_E_INVALID, "hidden_dim must be a multiple of 32, at most 256 (got " + std::to_string(hidden_dim) + ")");
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, keep_device) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return fail(AR_E_INVALID, "keep_device is not device memory");
+    }
+    int before = 0;
+    HIP_TRY(hipGetDevice(&before));
+    if (before != at.device) HIP_TRY(hipSetDevice(at.device));
+    TrainDrop dr;
+    dr.key = dropout_key(seed, step, (uint64_t)call);
+    dr.thr = dropout_thr(p);
+    dr.scale = dropout_scale(p);
+    const uint64_t count = n * hidden_dim;
+    hipLaunchKernelGGL(k_train_dropout_mask, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dr, count,
+                       keep_device);
+    const hipError_t e = hipGetLastError();
+    if (before != at.device) (void)hipSetDevice(before);
+    HIP_TRY(e);
+    return AR_OK;
 }
 
 int ar_rows_clear(ArRowSet* s) {

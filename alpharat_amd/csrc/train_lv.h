@@ -1,9 +1,9 @@
-// One training step of LocalValueMLP (alpharat/nn/models/local_value.py, BatchNorm in training mode, dropout 0) over a window
-// of the row set's order: PyRatMLP's step (train_mlp.h) with the ownership head, its masked cross-entropy
-// (alpharat/nn/losses/ownership.py) as the third term of the loss (alpharat/nn/architectures/local_value/loss.py) and what
-// loss.backward() leaves in the eighteen .grad tensors, f32 throughout. The trunk, the three heads, the products, the column
-// kernels and the ordered reductions are train_mlp.h's, untouched; the per-cell arithmetic is dev_train_lv.h; this file holds
-// what the head adds.
+// One training step of LocalValueMLP (alpharat/nn/models/local_value.py, BatchNorm in training mode, dropout when asked
+// for) over a window of the row set's order: PyRatMLP's step (train_mlp.h) with the ownership head, its masked
+// cross-entropy (alpharat/nn/losses/ownership.py) as the third term of the loss
+// (alpharat/nn/architectures/local_value/loss.py) and what loss.backward() leaves in the eighteen .grad tensors, f32
+// throughout. The trunk, the three heads, the products, the column kernels and the ordered reductions are train_mlp.h's;
+// the per-cell arithmetic is dev_train_lv.h; this file holds what the head adds.
 //
 // The chain of one step, every launch on the caller's stream: rows_grad_mlp in alpharat_hip.hip with its `lv` argument set
 // is this listing as calls. The lines without a number are train_mlp.h's own, issued by the same code:
@@ -24,6 +24,8 @@
 //   25   k_train_gemm                                 dZo Wo0, into the array the trunk's backward starts from
 //   26   k_train_colsum<DHEAD_ADD>                    dY2 = (dOut Wh + dZo Wo0) masked by trunk.5's ReLU, its column sums
 //        k_train_bn_bwd ... k_train_reduce            the rest of train_mlp.h's backward                                      9
+// With dropout (ar_rows_grad_local_value_dropout) A2 is the trunk output behind the second dropout, which the ownership head
+// reads as the other heads do, so the DROP form of k_train_colsum<DHEAD_ADD> scales the sum of both consumers' gradients.
 // 35 launches, 12 more than the MLP's step: k_train_lv_loss_sum stands where k_train_loss_sum stood and
 // k_train_colsum<DHEAD_ADD> where k_train_colsum<DHEAD> did.
 //

@@ -1,6 +1,7 @@
-// One training step of PyRatMLP (alpharat/nn/models/mlp.py, BatchNorm in training mode, dropout 0) over a window of the
-// row set's order: the forward, the losses of alpharat/nn/architectures/mlp/loss.py and what loss.backward() leaves in
-// the fourteen .grad tensors, f32 throughout. The per-element arithmetic is dev_train.h; this file holds the kernels.
+// One training step of PyRatMLP (alpharat/nn/models/mlp.py, BatchNorm in training mode, dropout when asked for) over a
+// window of the row set's order: the forward, the losses of alpharat/nn/architectures/mlp/loss.py and what
+// loss.backward() leaves in the fourteen .grad tensors, f32 throughout. The per-element arithmetic is dev_train.h; this
+// file holds the kernels.
 //
 // The chain of one step, every launch on the caller's stream. rows_grad_mlp in alpharat_hip.hip is this listing as calls;
 // the checks, the workspace, the stream rule and the launches themselves are TrainStep's, shared with train_sym.h:
@@ -19,6 +20,10 @@
 //   k_train_gemm                dA1 = dZ2 W4
 //   k_train_colsum<DTRUNK>, k_train_bn_bwd dZ1 in place; trunk.1's two gradients
 //   k_train_gemm (split), k_train_reduce   dZ1^T X: trunk.0's two gradients
+// With dropout (ar_rows_grad_mlp_dropout) the chain is the same 23 launches: k_train_bn_apply_drop stands where
+// k_train_bn_apply did and multiplies the kept elements of A by 1 / (1 - p) as it writes them, 0 for the dropped ones
+// (dev_dropout.h: a hash of (seed, step, BatchNorm call, row, column), no mask stored), and the DROP forms of
+// k_train_colsum<DHEAD> and <DTRUNK> multiply dA by the same scale before the mask they already read off A.
 // 23 launches. Fusing the column sums into the products' epilogues and the BatchNorm arithmetic into their load side
 // would shorten the chain; the first layer could also use the evaluators' sparse-operand shortcut.
 //
@@ -36,6 +41,7 @@
 // (train_cols and train_split, dev_train.h), each part in a fixed order, the parts combined in index order: the same
 // request gives the same bytes.
 #pragma once
+#include "dev_dropout.h"
 #include "dev_rows.h"
 #include "dev_train.h"
 
@@ -162,10 +168,15 @@ struct TrainColArgs {
     const double* mu;      // DHEAD, DTRUNK: the column's mean
     const float* rstd;     // DHEAD, DTRUNK: and 1 / sqrt(var + eps)
     double *part0, *part1;   // [P][H]
+    float scale;           // DROP: 1 / (1 - p) of the dropout behind the activation
 };
 
-template <int MODE>
+// DROP: the activation went through dropout (dev_dropout.h), so dy = dA * a.scale before the mask; act > 0 is then the
+// combined mask of the ReLU and the dropout, since a dropped element is exactly 0 and a kept positive one stays positive.
+// DHEAD_ADD scales the sum of both consumers' gradients.
+template <int MODE, bool DROP = false>
 __global__ void __launch_bounds__(256) k_train_colsum(TrainCols t, TrainColArgs a) {
+    static_assert(!DROP || MODE >= TC_DHEAD, "the forward's column sums see no dropout");
     __shared__ double s0[4][64], s1[4][64];
     const int c = threadIdx.x & 63, sub = threadIdx.x >> 6, col = blockIdx.x * 64 + c;
     const int r0 = blockIdx.y * t.rpp, r1 = t.n - r0 < t.rpp ? t.n : r0 + t.rpp;
@@ -204,6 +215,7 @@ __global__ void __launch_bounds__(256) k_train_colsum(TrainCols t, TrainColArgs 
                     if (MODE == TC_DHEAD_ADD) dy += a.d[i];
                 } else
                     dy = a.d[i];
+                if (DROP) dy *= a.scale;
                 dy = a.act[i] > 0.0f ? dy : 0.0f;
                 a.d[i] = dy;
                 const float xhat = train_bn_xhat(z, mu, rstd);
@@ -223,9 +235,11 @@ __global__ void __launch_bounds__(256) k_train_colsum(TrainCols t, TrainColArgs 
 
 // act = relu(bn(z)) with the batch's statistics from the partial sums; the first row block also keeps mu and rstd for the
 // backward and updates the running statistics (momentum 0.1, the unbiased variance), when they are given.
-__global__ void __launch_bounds__(256)
-k_train_bn_apply(TrainCols t, const float* z, const double* part_sum, const double* part_sq, const float* gamma,
-                 const float* beta, float* act, double* mu_out, float* rstd_out, float* run_mean, float* run_var) {
+// DROP: inverted dropout on top, act = keep(row * H + column) ? relu(bn(z)) * scale : 0 (dev_dropout.h); nothing is stored.
+template <bool DROP>
+__device__ __forceinline__ void train_bn_apply(const TrainCols& t, const float* z, const double* part_sum, const double* part_sq,
+                                               const float* gamma, const float* beta, float* act, double* mu_out,
+                                               float* rstd_out, float* run_mean, float* run_var, const TrainDrop& dr) {
     const int c = threadIdx.x & 63, sub = threadIdx.x >> 6, col = blockIdx.x * 64 + c;
     if (col >= t.H) return;
     const double mean = train_col_total(part_sum, t.P, t.H, col) / (double)t.n;
@@ -242,8 +256,29 @@ k_train_bn_apply(TrainCols t, const float* z, const double* part_sum, const doub
         const size_t i = (size_t)r * t.H + col;
         float xhat;
         const float y = train_bn_forward(z[i], mean, rstd, ga, be, xhat);
-        act[i] = y > 0.0f ? y : 0.0f;
+        if (DROP) act[i] = (y > 0.0f && dropout_keep(dr.key, dr.thr, (uint64_t)i)) ? y * dr.scale : 0.0f;
+        else act[i] = y > 0.0f ? y : 0.0f;
     }
+}
+
+__global__ void __launch_bounds__(256)
+k_train_bn_apply(TrainCols t, const float* z, const double* part_sum, const double* part_sq, const float* gamma,
+                 const float* beta, float* act, double* mu_out, float* rstd_out, float* run_mean, float* run_var) {
+    train_bn_apply<false>(t, z, part_sum, part_sq, gamma, beta, act, mu_out, rstd_out, run_mean, run_var, TrainDrop{});
+}
+
+__global__ void __launch_bounds__(256)
+k_train_bn_apply_drop(TrainCols t, const float* z, const double* part_sum, const double* part_sq, const float* gamma,
+                      const float* beta, float* act, double* mu_out, float* rstd_out, float* run_mean, float* run_var,
+                      TrainDrop dr) {
+    train_bn_apply<true>(t, z, part_sum, part_sq, gamma, beta, act, mu_out, rstd_out, run_mean, run_var, dr);
+}
+
+// the mask of one call as k_train_bn_apply_drop forms it, element by element (ar_train_dropout_mask): keep [n][H] bytes, 1 for
+// a kept element, 0 for a dropped one
+__global__ void __launch_bounds__(256) k_train_dropout_mask(TrainDrop dr, uint64_t count, uint8_t* keep) {
+    const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < count) keep[e] = dropout_keep(dr.key, dr.thr, e) ? 1 : 0;
 }
 
 // dz in place of the masked dy; the first row block writes dgamma = sum(dy * xhat) and dbeta = sum(dy)

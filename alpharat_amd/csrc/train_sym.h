@@ -1,7 +1,8 @@
-// One training step of SymmetricMLP (alpharat/nn/models/symmetric.py, BatchNorm in training mode, dropout 0) over a window of
-// the row set's order: the forward, the losses of alpharat/nn/architectures/symmetric/loss.py and what loss.backward()
-// leaves in the twenty .grad tensors, f32 throughout. The products, the column kernels and the ordered reductions are
-// train_mlp.h's, untouched; the per-row arithmetic is dev_train.h and dev_train_sym.h; this file holds what the network adds.
+// One training step of SymmetricMLP (alpharat/nn/models/symmetric.py, BatchNorm in training mode, dropout when asked for)
+// over a window of the row set's order: the forward, the losses of alpharat/nn/architectures/symmetric/loss.py and what
+// loss.backward() leaves in the twenty .grad tensors, f32 throughout. The products, the column kernels and the ordered
+// reductions are train_mlp.h's; the per-row arithmetic is dev_train.h and dev_train_sym.h; this file holds what the
+// network adds.
 //
 // P1's and P2's rows are stacked as [2n][.] arrays (P1's n rows, then P2's): every layer the two players share is then one
 // product over 2n rows, and every gradient of a shared weight -- the sum of its two calls' contributions, P1's before P2's --
@@ -33,6 +34,9 @@
 //   55  k_train_gemm (split), k_train_reduce      player_encoder.0's two gradients                                        2
 //   57  bn'                         shared_encoder.1's two gradients (one call: k_train_bn_bwd writes them)               2
 //   59  k_train_gemm (split), k_train_reduce      shared_encoder.0's two gradients                                        2
+// With dropout (ar_rows_grad_symmetric_dropout) the same 60 launches: each of the seven BatchNorm calls has its own mask
+// (call index 0 .. 6 in the order above, rows counted within the call's half), applied by k_train_bn_apply_drop and undone by
+// the DROP forms of k_sym_dhead and k_train_colsum<DTRUNK> (train_mlp.h, dev_dropout.h).
 // 60 launches. k_sym_cat and k_sym_uncat are copies that a leading dimension on the column kernels' arrays would save; so
 // would everything train_mlp.h lists for its own chain.
 //
@@ -182,8 +186,11 @@ struct SymDHead {
     const double* mu;
     const float* rstd;
     double *part0, *part1;  // [P][H]
+    float scale;            // DROP: 1 / (1 - p)
 };
 
+// DROP: behind trunk.7's dropout, dy = dh_i * a.scale before the mask (k_train_colsum's DROP, train_mlp.h).
+template <bool DROP = false>
 __global__ void __launch_bounds__(256) k_sym_dhead(TrainCols t, SymDHead a) {
     __shared__ double s0[4][64], s1[4][64];
     const int c = threadIdx.x & 63, sub = threadIdx.x >> 6, col = blockIdx.x * 64 + c;
@@ -202,6 +209,7 @@ __global__ void __launch_bounds__(256) k_sym_dhead(TrainCols t, SymDHead a) {
         for (int r = r0 + sub; r < r1; r += 4) {
             const size_t i = (size_t)r * t.H + col;
             float dy = sym_head_dy(a.d12 + (size_t)r * 12, w_lo, w_hi);
+            if (DROP) dy *= a.scale;
             dy = a.act[i] > 0.0f ? dy : 0.0f;
             a.d[i] = dy;
             const float xhat = train_bn_xhat(a.z[i], mu, rstd);

@@ -185,7 +185,7 @@ def lv_param_shapes(width: int, height: int, hidden_dim: int) -> dict:
 
 # What a training step is made of, per architecture: the key tuples and shapes that check_grad_tensors holds the caller's
 # tensors to, the two ctypes structs and the symbol that RowSet._grad_into hands them to, and its outputs: their struct,
-# their keys and the number of losses.
+# their keys and the number of losses. With a dropout the symbol is this one with "_dropout" behind it.
 _GRAD_STEPS = {
     "mlp": (MLP_PARAM_KEYS, MLP_RUNNING_KEYS, mlp_param_shapes, _lib.ArMlpTensors, _lib.ArMlpBnStats, "ar_rows_grad_mlp",
             _lib.ArTrainOut, TRAIN_OUT_KEYS, 6),
@@ -325,36 +325,44 @@ class RowSet:
         _lib.check(_lib.load().ar_rows_build_device(handle, first, n, C.byref(ptrs), C.c_void_p(stream.cuda_stream)))
 
     def grad_mlp_into(self, first: int, n: int, hidden_dim: int, params: dict, grads: dict, running, policy_weight: float,
-                      value_weight: float, out, stream=None) -> None:
+                      value_weight: float, out, stream=None, dropout=None) -> None:
         """The loss and the gradients of PyRatMLP in training mode over rows ``first .. first + n`` of the order
         (``ar_rows_grad_mlp``), on ``stream`` (``None``: torch's current stream of the set's device). Only launches.
         ``params`` and ``grads``: the fourteen tensors under ``MLP_PARAM_KEYS``; ``grads`` is overwritten. ``running``:
         the four ``MLP_RUNNING_KEYS``, updated in place, or ``None``. ``out``: any of ``TRAIN_OUT_KEYS`` (losses ``(6,)``,
         logits ``(n, 5)``, values ``(n,)``), or ``None``. Every tensor is on the set's device, float32, contiguous and of
-        the shape ``(width, height, hidden_dim)`` give, else ``ValueError`` before the library is touched."""
-        self._grad_into("mlp", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream)
+        the shape ``(width, height, hidden_dim)`` give, else ``ValueError`` before the library is touched. ``dropout``:
+        ``None``, or ``(p, seed, step)`` for inverted dropout at rate ``p`` behind both BatchNorm -> ReLU of the trunk
+        (``ar_rows_grad_mlp_dropout``): the mask is the library's own counter-based generator, a pure function of
+        ``(seed, step)``, the BatchNorm call and the element, so the same triple gives the same bytes; ``p`` outside
+        ``[0, 1)`` raises ``ValueError`` with nothing written, and ``p == 0`` is the call without it."""
+        self._grad_into("mlp", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream,
+                        dropout=dropout)
 
     def grad_symmetric_into(self, first: int, n: int, hidden_dim: int, params: dict, grads: dict, running, policy_weight: float,
-                            value_weight: float, out, stream=None) -> None:
+                            value_weight: float, out, stream=None, dropout=None) -> None:
         """``grad_mlp_into`` for SymmetricMLP (``ar_rows_grad_symmetric``): ``params`` and ``grads`` are the twenty tensors
         under ``SYM_PARAM_KEYS``, ``running`` the eight ``SYM_RUNNING_KEYS`` or ``None``, of the shapes
-        ``sym_param_shapes(width, height, hidden_dim)`` gives; everything else as there."""
-        self._grad_into("symmetric", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream)
+        ``sym_param_shapes(width, height, hidden_dim)`` gives; everything else as there (``dropout`` is applied behind all
+        seven BatchNorm calls, each with its own mask)."""
+        self._grad_into("symmetric", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream,
+                        dropout=dropout)
 
     def grad_local_value_into(self, first: int, n: int, hidden_dim: int, params: dict, grads: dict, running,
-                              policy_weight: float, value_weight: float, ownership_weight: float, out, stream=None) -> None:
+                              policy_weight: float, value_weight: float, ownership_weight: float, out, stream=None,
+                              dropout=None) -> None:
         """``grad_mlp_into`` for LocalValueMLP (``ar_rows_grad_local_value``): ``params`` and ``grads`` are the eighteen
         tensors under ``LV_PARAM_KEYS``, ``running`` the four ``MLP_RUNNING_KEYS`` or ``None``, of the shapes
         ``lv_param_shapes(width, height, hidden_dim)`` gives. The loss has the third term, ``ownership_weight`` times the
         cross-entropy of the ownership head over the window's active cells. ``out``: any of ``LV_TRAIN_OUT_KEYS`` --
         ``losses`` is ``(7,)``, the six and ``loss_ownership``; ``ownership_logits`` ``(n, height, width, 4)``. The
         workspace is the MLP step's plus ``3 n H + 4 n h w`` floats (the logits alone are 268 MB at 65536 rows of 16x16).
-        Everything else as there."""
+        Everything else as there (the ownership head reads the trunk output behind the second ``dropout``)."""
         self._grad_into("local_value", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream,
-                        (float(ownership_weight),))
+                        (float(ownership_weight),), dropout=dropout)
 
     def _grad_into(self, architecture: str, first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out,
-                   stream, more_weights: tuple = ()) -> None:
+                   stream, more_weights: tuple = (), dropout=None) -> None:
         import torch
 
         first, n, hidden_dim = int(first), int(n), int(hidden_dim)
@@ -370,10 +378,15 @@ class RowSet:
         g = Tensors(*[grads[k].data_ptr() for k in param_keys])
         r = BnStats(*[running[k].data_ptr() for k in running_keys]) if running is not None else None
         o = Out(*[out[k].data_ptr() if out.get(k) is not None else None for k in out_keys]) if out is not None else None
+        more = ()
+        if dropout is not None:
+            rate, seed, step = dropout
+            d = _lib.ArTrainDropout(float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF)
+            symbol, more = symbol + "_dropout", (C.byref(d),)
         _lib.check(getattr(_lib.load(), symbol)(handle, first, n, hidden_dim, C.byref(p), C.byref(g),
                                                 C.byref(r) if r is not None else None, float(policy_weight),
                                                 float(value_weight), *more_weights, C.byref(o) if o is not None else None,
-                                                C.c_void_p(stream.cuda_stream)))
+                                                *more, C.c_void_p(stream.cuda_stream)))
 
     def validate(self, net, rows, chunk_rows: int = 0, return_rows: bool = False):
         """``net`` over the stored positions ``rows``: the sums of the reference's validation pass

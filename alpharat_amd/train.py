@@ -15,9 +15,17 @@ Supported: PyRatMLP (``architecture: mlp``, ``MLPGradStep``), SymmetricMLP (``ar
 ``SymmetricGradStep`` over ``ar_rows_grad_symmetric``, alpharat_amd/csrc/train_sym.h) and LocalValueMLP (``architecture:
 local_value``, ``LocalValueGradStep`` over ``ar_rows_grad_local_value``, alpharat_amd/csrc/train_lv.h: the MLP's step plus
 the ownership head and ``ownership_weight`` times its masked cross-entropy, seven losses) -- same loop, same contract -- in
-float32 with ``dropout`` 0.0 -- the architectures' default -- and a hidden width that is a multiple of 32, at most 256. AMP,
-dropout and the other architectures are not built. (The reference's configs/model/symmetric.yaml sets ``dropout: 0.1``: a
-model built from it is refused until that is 0.0.)
+float32 and a hidden width that is a multiple of 32, at most 256. AMP and the other architectures are not built.
+
+Dropout is opt-in: without ``dropout_seed`` a model whose ``nn.Dropout`` has ``p != 0`` is refused, as it always was (the
+architectures' default is 0.0; the reference's configs/model/symmetric.yaml sets ``dropout: 0.1``). With
+``dropout_seed=<int>`` the rate is read from the model's ``Dropout`` modules -- all of one ``p`` in ``[0, 1)``, else
+``ValueError`` -- and every training-mode step applies inverted dropout behind each BatchNorm -> ReLU of the encoders and
+the trunk, as the modules would. The mask is the library's own counter-based generator (alpharat_amd/csrc/dev_dropout.h), a
+pure function of ``(dropout_seed, dropout_step)``, the BatchNorm call and the element: not torch's Philox stream, so a run
+is reproducible from the seed and the step count, never mask-for-mask equal to a torch run. ``dropout_step`` starts at 0 and
+grows by one with every training-mode step; it is an attribute, so a resumed run sets it. In eval mode no dropout is applied
+and the counter stays. ``dropout_mask`` returns the mask of one BatchNorm call as the device forms it.
 
 ``trunk.0.bias`` and ``trunk.4.bias`` -- and SymmetricMLP's ``shared_encoder.0.bias`` and ``player_encoder.0.bias`` -- sit
 in front of a BatchNorm, so their true gradient is zero and what any implementation writes there is rounding noise
@@ -42,14 +50,24 @@ class _GradStep:
     _NAME = _PARAM_KEYS = _RUNNING_KEYS = _TRACKED = _ROWSET_METHOD = None
     _N_LOSSES = 6
 
-    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0) -> None:
+    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0, dropout_seed: int | None = None) -> None:
         import torch
 
         self.model = model
         self.policy_weight, self.value_weight = float(policy_weight), float(value_weight)
-        for m in model.modules():
-            if isinstance(m, torch.nn.Dropout) and m.p != 0:
-                raise ValueError(f"dropout {m.p} is not supported: the step is built for {self._NAME}'s default dropout 0.0")
+        rates = sorted({float(m.p) for m in model.modules() if isinstance(m, torch.nn.Dropout)})
+        if dropout_seed is None:
+            for p in rates:
+                if p != 0:
+                    raise ValueError(f"dropout {p} is not supported: the step is built for {self._NAME}'s default dropout 0.0 "
+                                     "unless it is given a dropout_seed, which the device's own mask generator starts from")
+        elif len(rates) > 1:
+            raise ValueError(f"the model's Dropout modules have different p ({', '.join(map(str, rates))}): the step applies one")
+        elif rates and not 0.0 <= rates[0] < 1.0:
+            raise ValueError(f"dropout {rates[0]} is not supported: p must be in [0, 1)")
+        self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
+        self.dropout_p = rates[0] if dropout_seed is not None and rates else 0.0
+        self.dropout_step = 0  # sent with every training-mode step, then one more; a resumed run sets it
         named = {k.removeprefix(_PREFIX): v for k, v in model.named_parameters()}
         buffers = {k.removeprefix(_PREFIX): v for k, v in model.named_buffers()}
         self._refuse(named, buffers)
@@ -96,13 +114,18 @@ class _GradStep:
             out.update(self._more_outputs(rowset, n, device))
         training = bool(self.model.training)
         params = {k: p.data for k, p in self.params.items()}
+        # nn.Dropout is the identity in eval mode: no mask then, and the counter stays
+        dropping = training and self.dropout_seed is not None and self.dropout_p != 0
+        more = dict(dropout=(self.dropout_p, self.dropout_seed, self.dropout_step)) if dropping else {}
         getattr(rowset, self._ROWSET_METHOD)(first, n, self.hidden_dim, params, self.grads, self.running if training else None,
-                                             *self._weights(), out)
+                                             *self._weights(), out, **more)
         for k, p in self.params.items():
             p.grad = self.grads[k]
         if training:
             for t, calls in self._tracked:
                 t.add_(calls)
+            if self.dropout_seed is not None:
+                self.dropout_step += 1
         if outputs:
             return tuple(out.values())
         return out["losses"]
@@ -110,7 +133,8 @@ class _GradStep:
 
 class MLPGradStep(_GradStep):
     """``model``: an ``nn.Module`` whose ``state_dict()`` has PyRatMLP's keys (an ``_orig_mod.`` prefix is stripped).
-    ``ValueError`` for a ``Dropout`` with ``p != 0``, an ``ownership_head``, a missing key, or a parameter or BatchNorm
+    ``ValueError`` for a ``Dropout`` with ``p != 0`` and no ``dropout_seed`` (with one: for ``Dropout`` modules of different
+    ``p``, or ``p >= 1``), an ``ownership_head``, a missing key, or a parameter or BatchNorm
     buffer that is not float32 or not contiguous. One persistent gradient tensor per parameter is allocated here."""
 
     _NAME, _PARAM_KEYS, _RUNNING_KEYS, _ROWSET_METHOD = "PyRatMLP", MLP_PARAM_KEYS, MLP_RUNNING_KEYS, "grad_mlp_into"
@@ -178,9 +202,10 @@ class LocalValueGradStep(MLPGradStep):
 
     _NAME, _PARAM_KEYS, _ROWSET_METHOD, _N_LOSSES = "LocalValueMLP", LV_PARAM_KEYS, "grad_local_value_into", 7
 
-    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0, ownership_weight: float = 1.0) -> None:
+    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0, ownership_weight: float = 1.0,
+                 dropout_seed: int | None = None) -> None:
         self.ownership_weight = float(ownership_weight)
-        super().__init__(model, policy_weight, value_weight)
+        super().__init__(model, policy_weight, value_weight, dropout_seed)
 
     def _refuse(self, named: dict, buffers: dict) -> None:
         pass
@@ -209,3 +234,26 @@ class LocalValueGradStep(MLPGradStep):
         ``ownership_weight * loss_ownership``; with ``outputs`` ``(losses, logits_p1, logits_p2, value_p1, value_p2,
         ownership_logits (n, h, w, 4))``, the training-mode outputs."""
         return _GradStep.step(self, rowset, first, n, outputs)
+
+
+def dropout_mask(seed: int, step: int, call: int, n: int, hidden_dim: int, p: float, device_index: int = 0):
+    """The mask of BatchNorm call ``call`` of training step ``step`` under ``dropout_seed`` ``seed``, as the device's own
+    generator gives it (``ar_train_dropout_mask``): a bool tensor ``(n, hidden_dim)`` on the device, True where the element
+    is kept. ``call``: PyRatMLP and LocalValueMLP 0 ``trunk.3``, 1 ``trunk.7``; SymmetricMLP 0 ``shared_encoder``, 1 / 2
+    ``player_encoder`` on P1's / P2's rows, 3 / 4 ``trunk.3``, 5 / 6 ``trunk.7``. ``ValueError`` for ``p`` outside ``[0, 1)``,
+    ``n`` outside 1 .. 65536 or a ``hidden_dim`` that is no multiple of 32 up to 256."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    n, hidden_dim = int(n), int(hidden_dim)
+    if n < 0 or hidden_dim < 0 or int(call) < 0:
+        raise ValueError("call, n and hidden_dim must not be negative")
+    keep = torch.empty((n, hidden_dim), dtype=torch.uint8, device=torch.device("cuda", int(device_index)))
+    stream = torch.cuda.current_stream(int(device_index))
+    _lib.check(_lib.load().ar_train_dropout_mask(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(call), n,
+                                                 hidden_dim, float(p), C.c_void_p(keep.data_ptr()),
+                                                 C.c_void_p(stream.cuda_stream)))
+    return keep.bool()

@@ -478,7 +478,8 @@ int ar_rows_validate_lv(ArRowSet* set, ArNet* net, const uint64_t* rows, uint64_
  * architectures/mlp/loss.py, loss.backward()) -----------------------------------------------------------------------------
  * The loss and the gradients of one batch -- rows first .. first + n of the order, with their swap flags, exactly the
  * rows ar_rows_build_device writes -- computed on the device in f32 and written into the caller's tensors. The
- * optimiser, the schedule and the checkpoints stay the caller's. Dropout is not applied (the architecture's default 0).
+ * optimiser, the schedule and the checkpoints stay the caller's. Dropout is not applied here (the architecture's default
+ * 0; with it: ar_rows_grad_mlp_dropout, below).
  * BatchNorm (both layers), over the batch: mu = mean(z), var = mean((z - mu)^2) (two passes), xhat = (z - mu) *
  * rsqrt(var + 1e-5), y = gamma * xhat + beta, then ReLU. Running statistics, when given: rm = 0.9 rm + 0.1 mu,
  * rv = 0.9 rv + 0.1 var * n / (n - 1). Heads: l1, l2 the policy logits, v = softplus(o) of the value head (v = o above 20).
@@ -589,6 +590,41 @@ typedef struct ArLvTrainOut { /* device memory of the caller's, any may be NULL 
 int ar_rows_grad_local_value(ArRowSet* set, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArLvTensors* params,
                              const ArLvTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
                              float ownership_weight, const ArLvTrainOut* out, void* stream);
+
+/* ---- dropout in the three training steps (nn.Dropout in training mode behind every BatchNorm -> ReLU of the encoders and
+ * the trunk) ----------------------------------------------------------------------------------------------------------------
+ * Inverted dropout: a kept element of relu(bn(z)) is multiplied by scale = 1.0f / (float)(1.0 - (double)p), a dropped one is
+ * exactly 0, and the backward multiplies the gradient of the kept elements by the same scale. No mask is stored (a dropped
+ * element is 0 in the activation, which the backward already reads as its ReLU mask), so the workspace does not grow and no
+ * launch is added. The mask is this library's own counter-based generator (alpharat_amd/csrc/dev_dropout.h), a pure function
+ * of (seed, step, call, row, column) in wrapping 64-bit arithmetic, with G = 0x9e3779b97f4a7c15 and mix SplitMix64's finaliser:
+ *   key  = mix(mix(mix(seed + G) + step * G + G) + call * G + G)         bits = mix(key + (row * H + column + 1) * G)
+ *   thr  = floor(p * 2^32 + 0.5)                                          kept iff (bits >> 32) >= thr
+ * `call` is the index of the BatchNorm call the dropout follows and `row` counts within that call's own n rows: PyRatMLP and
+ * LocalValueMLP 0 = trunk.3, 1 = trunk.7 (the ownership head reads the trunk output behind the second); SymmetricMLP
+ * 0 = shared_encoder, 1, 2 = player_encoder on P1's, P2's rows, 3, 4 = trunk.3 for P1, P2, 5, 6 = trunk.7 for P1, P2. It is
+ * not torch's Philox stream: a step is reproducible from (seed, step) -- the same request gives the same bytes -- and is not
+ * mask-for-mask equal to a torch run. The caller counts the steps. */
+typedef struct ArTrainDropout { float p; uint64_t seed; uint64_t step; } ArTrainDropout;
+/* The three steps with `dropout` in front of `stream`. dropout == NULL or p == 0: exactly the function without the suffix,
+ * launch for launch (those are calls of these with NULL). AR_E_INVALID before any launch, nothing written, for that
+ * function's list and for p < 0, p >= 1 or NaN. */
+int ar_rows_grad_mlp_dropout(ArRowSet* set, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArMlpTensors* params,
+                             const ArMlpTensors* grads, const ArMlpBnStats* running, float policy_weight, float value_weight,
+                             const ArTrainOut* out, const ArTrainDropout* dropout, void* stream);
+int ar_rows_grad_symmetric_dropout(ArRowSet* set, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArSymTensors* params,
+                                   const ArSymTensors* grads, const ArSymBnStats* running, float policy_weight,
+                                   float value_weight, const ArTrainOut* out, const ArTrainDropout* dropout, void* stream);
+int ar_rows_grad_local_value_dropout(ArRowSet* set, uint64_t first, uint64_t n, uint32_t hidden_dim, const ArLvTensors* params,
+                                     const ArLvTensors* grads, const ArMlpBnStats* running, float policy_weight,
+                                     float value_weight, float ownership_weight, const ArLvTrainOut* out,
+                                     const ArTrainDropout* dropout, void* stream);
+/* The mask of one call as the device's own generator gives it: keep_device [n][hidden_dim] bytes of device memory, 1 for a
+ * kept element, 0 for a dropped one; launched on `stream` of the pointer's device, no synchronisation. AR_E_INVALID before any
+ * launch: a null or non-device pointer; n == 0 or n > 65536; hidden_dim not a multiple of 32 or above 256; p < 0, p >= 1 or
+ * NaN. */
+int ar_train_dropout_mask(uint64_t seed, uint64_t step, uint32_t call, uint64_t n, uint32_t hidden_dim, float p,
+                          uint8_t* keep_device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,9 @@ own. At batch sizes 256, 4096 and 65536 one epoch is timed two ways, on the same
                      plain torch ops in training mode (tests/_mlp_torch.py), the losses, backward(), AdamW.step()
 Five timed windows (one epoch each, epochs 1 .. 5) after a warm-up epoch, a host clock around a loop that ends in one
 torch.cuda.synchronize(). The mean loss of the last epoch of both sides is printed as a sanity check, not as a test: the
-two sides round differently, and AdamW amplifies that. Prints one JSON line and writes it to --out (profiles/train_bench.json).
+two sides round differently, and AdamW amplifies that. --dropout P trains both sides with dropout: the step with a
+dropout_seed, the torch side through the modules of a model built with nn.Dropout(P) (each side draws its own masks, so
+the losses agree only in the mean). Prints one JSON line and writes it to --out (profiles/train_bench.json).
 """
 from __future__ import annotations
 
@@ -41,6 +43,8 @@ def main() -> None:
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--blob", default=str(ROOT / "tests" / "golden" / "nets" / "mlp_7x7_h256.arnet"))
     ap.add_argument("--out", default=str(ROOT / "profiles" / "train_bench.json"))
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="both sides train with dropout P: the step with dropout_seed 0, the torch side a model built with nn.Dropout(P)")
     a = ap.parse_args()
 
     import _mlp_torch as MT
@@ -84,8 +88,8 @@ def main() -> None:
             continue
         rows = n - n % batch
         # this library
-        model = MT.MLP(w * h * 7 + 6, H, sd=tensors).to(device).train()
-        step = MLPGradStep(model, 1.0, 1.0)
+        model = MT.MLP(w * h * 7 + 6, H, a.dropout, sd=tensors).to(device).train()
+        step = MLPGradStep(model, 1.0, 1.0, dropout_seed=0 if a.dropout else None)
         opt = torch.optim.AdamW(model.parameters(), lr=a.lr)
 
         def ours(epoch):
@@ -100,12 +104,21 @@ def main() -> None:
         p = {k: torch.tensor(np.asarray(tensors[k], np.float32), device=device, requires_grad=True) for k in step.params}
         running = {k: torch.tensor(np.asarray(tensors[k], np.float32), device=device) for k in step.running}
         opt2 = torch.optim.AdamW(list(p.values()), lr=a.lr)
+        forward = lambda x: MT.forward(p, x, running)  # noqa: E731
+        if a.dropout:  # the modules themselves, nn.Dropout(P) among them: torch's own masks
+            tm = MT.MLP(w * h * 7 + 6, H, a.dropout, sd=tensors).to(device).train()
+            opt2 = torch.optim.AdamW(tm.parameters(), lr=a.lr)
+
+            def forward(x):
+                f = tm.trunk(x)
+                v = torch.nn.functional.softplus(tm.value_head(f))
+                return tm.policy_p1_head(f), tm.policy_p2_head(f), v[:, 0], v[:, 1]
 
         def today(epoch):
             losses = []
             for b in ds.epoch_iter(batch, epoch=epoch, seed=0):
                 opt2.zero_grad(set_to_none=True)
-                ls = MT.losses(MT.forward(p, b["observation"], running), b["policy_p1"], b["policy_p2"], b["value_p1"],
+                ls = MT.losses(forward(b["observation"]), b["policy_p1"], b["policy_p2"], b["value_p1"],
                                b["value_p2"], 1.0, 1.0)
                 ls["loss"].backward()
                 opt2.step()
@@ -123,7 +136,7 @@ def main() -> None:
         print(json.dumps(results[-1]), file=sys.stderr)
     rs.close()
     line = json.dumps(dict(board="7x7", net=Path(a.blob).name, hidden=int(H), games=games, positions=n, windows=WINDOWS,
-                           optimizer=f"AdamW(lr={a.lr})", results=results))
+                           optimizer=f"AdamW(lr={a.lr})", dropout=a.dropout, results=results))
     print(line)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)

@@ -13,8 +13,8 @@ this size is among the goldens) and with the same plan of batches:
                      in plain torch ops in training mode (tests/_lv_torch.py), the three-term loss, backward(), AdamW.step()
 Five timed windows (one epoch each, epochs 1 .. 5) after a warm-up epoch, a host clock around a loop that ends in one
 torch.cuda.synchronize(). The mean loss of the last epoch of both sides is printed as a sanity check, not as a test: the
-two sides round differently, and AdamW amplifies that. Prints one JSON line and writes it to --out
-(profiles/train_lv_bench.json).
+two sides round differently, and AdamW amplifies that. --dropout P as in tools/bench_train.py: both sides train with
+dropout, each with its own masks. Prints one JSON line and writes it to --out (profiles/train_lv_bench.json).
 """
 from __future__ import annotations
 
@@ -46,6 +46,8 @@ def main() -> None:
     ap.add_argument("--out", default=str(ROOT / "profiles" / "train_lv_bench.json"))
     ap.add_argument("--ownership-weight", type=float, default=1.0)
     ap.add_argument("--head-seed", type=int, default=0)
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="both sides train with dropout P: the step with dropout_seed 0, the torch side a model built with nn.Dropout(P)")
     a = ap.parse_args()
 
     import _lv_torch as LT
@@ -96,8 +98,8 @@ def main() -> None:
             continue
         rows = n - n % batch
         # this library
-        model = LT.LocalValue(w, h, H, sd=tensors).to(device).train()
-        step = LocalValueGradStep(model, 1.0, 1.0, ow)
+        model = LT.LocalValue(w, h, H, a.dropout, sd=tensors).to(device).train()
+        step = LocalValueGradStep(model, 1.0, 1.0, ow, dropout_seed=0 if a.dropout else None)
         opt = torch.optim.AdamW(model.parameters(), lr=a.lr)
 
         def ours(epoch):
@@ -112,12 +114,21 @@ def main() -> None:
         p = {k: torch.tensor(np.asarray(tensors[k], np.float32), device=device, requires_grad=True) for k in step.params}
         running = {k: torch.tensor(np.asarray(tensors[k], np.float32), device=device) for k in step.running}
         opt2 = torch.optim.AdamW(list(p.values()), lr=a.lr)
+        forward = lambda x: LT.forward(p, x, w, h, running)  # noqa: E731
+        if a.dropout:  # the modules themselves, nn.Dropout(P) among them: torch's own masks
+            tm = LT.LocalValue(w, h, H, a.dropout, sd=tensors).to(device).train()
+            opt2 = torch.optim.AdamW(tm.parameters(), lr=a.lr)
+
+            def forward(x):
+                f = tm.trunk(x)
+                v = torch.nn.functional.softplus(tm.value_head(f))
+                return (tm.policy_p1_head(f), tm.policy_p2_head(f), v[:, 0], v[:, 1], tm.ownership_head(f).view(-1, h, w, 4))
 
         def today(epoch):
             losses = []
             for b in ds.epoch_iter(batch, epoch=epoch, seed=0):
                 opt2.zero_grad(set_to_none=True)
-                ls = LT.losses(LT.forward(p, b["observation"], w, h, running), b["policy_p1"], b["policy_p2"], b["value_p1"],
+                ls = LT.losses(forward(b["observation"]), b["policy_p1"], b["policy_p2"], b["value_p1"],
                                b["value_p2"], b["cheese_outcomes"], 1.0, 1.0, ow)
                 ls["loss"].backward()
                 opt2.step()
@@ -135,7 +146,7 @@ def main() -> None:
         print(json.dumps(results[-1]), file=sys.stderr)
     rs.close()
     line = json.dumps(dict(board="7x7", net=Path(a.blob).name, hidden=int(H), games=games, positions=n, windows=WINDOWS,
-                           optimizer=f"AdamW(lr={a.lr})", augment=True, ownership_weight=ow, results=results))
+                           optimizer=f"AdamW(lr={a.lr})", augment=True, ownership_weight=ow, dropout=a.dropout, results=results))
     print(line)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)

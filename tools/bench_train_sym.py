@@ -13,8 +13,8 @@ own. At batch sizes 256, 4096 and 65536 one epoch is timed two ways, on the same
 The epochs are planned with augment=False, the reference's setting for this architecture (NoAugmentation).
 Five timed windows (one epoch each, epochs 1 .. 5) after a warm-up epoch, a host clock around a loop that ends in one
 torch.cuda.synchronize(). The mean loss of the last epoch of both sides is printed as a sanity check, not as a test: the
-two sides round differently, and AdamW amplifies that. Prints one JSON line and writes it to --out
-(profiles/train_sym_bench.json).
+two sides round differently, and AdamW amplifies that. --dropout P as in tools/bench_train.py: both sides train with
+dropout, each with its own masks. Prints one JSON line and writes it to --out (profiles/train_sym_bench.json).
 """
 from __future__ import annotations
 
@@ -44,6 +44,8 @@ def main() -> None:
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--blob", default=str(ROOT / "tests" / "golden" / "nets" / "symmetric_7x7_h256.arnet"))
     ap.add_argument("--out", default=str(ROOT / "profiles" / "train_sym_bench.json"))
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="both sides train with dropout P: the step with dropout_seed 0, the torch side a model built with nn.Dropout(P)")
     a = ap.parse_args()
 
     import _sym_torch as ST
@@ -87,8 +89,8 @@ def main() -> None:
             continue
         rows = n - n % batch
         # this library
-        model = ST.Symmetric(w, h, H, sd=tensors).to(device).train()
-        step = SymmetricGradStep(model, 1.0, 1.0)
+        model = ST.Symmetric(w, h, H, a.dropout, sd=tensors).to(device).train()
+        step = SymmetricGradStep(model, 1.0, 1.0, dropout_seed=0 if a.dropout else None)
         opt = torch.optim.AdamW(model.parameters(), lr=a.lr)
 
         def ours(epoch):
@@ -103,12 +105,27 @@ def main() -> None:
         p = {k: torch.tensor(np.asarray(tensors[k], np.float32), device=device, requires_grad=True) for k in step.params}
         running = {k: torch.tensor(np.asarray(tensors[k], np.float32), device=device) for k in step.running}
         opt2 = torch.optim.AdamW(list(p.values()), lr=a.lr)
+        forward = lambda x: ST.forward(p, x, w, h, running)  # noqa: E731
+        if a.dropout:  # the modules themselves, nn.Dropout(P) among them: torch's own masks
+            tm = ST.Symmetric(w, h, H, a.dropout, sd=tensors).to(device).train()
+            opt2 = torch.optim.AdamW(tm.parameters(), lr=a.lr)
+
+            def forward(x):  # alpharat/nn/models/symmetric.py forward, module by module
+                hw = w * h
+                sc = x[:, 7 * hw:]
+                shared = tm.shared_encoder(torch.cat([x[:, :4 * hw], x[:, 6 * hw:7 * hw], sc[:, 1:2]], dim=1))
+                pe = [tm.player_encoder(torch.cat([x[:, (4 + i) * hw:(5 + i) * hw], sc[:, 2 + i:3 + i], sc[:, 4 + i:5 + i]], dim=1))
+                      for i in (0, 1)]
+                hs = [tm.trunk(torch.cat([shared, pe[i]], dim=1)) for i in (0, 1)]
+                cat = [torch.cat([hs[i], hs[0] + hs[1]], dim=1) for i in (0, 1)]
+                v = [torch.nn.functional.softplus(tm.value_head(c)).squeeze(-1) for c in cat]
+                return tm.policy_head(cat[0]), tm.policy_head(cat[1]), v[0], v[1]
 
         def today(epoch):
             losses = []
             for b in ds.epoch_iter(batch, epoch=epoch, seed=0, augment=False):
                 opt2.zero_grad(set_to_none=True)
-                ls = ST.losses(ST.forward(p, b["observation"], w, h, running), b["policy_p1"], b["policy_p2"], b["value_p1"],
+                ls = ST.losses(forward(b["observation"]), b["policy_p1"], b["policy_p2"], b["value_p1"],
                                b["value_p2"], 1.0, 1.0)
                 ls["loss"].backward()
                 opt2.step()
@@ -126,7 +143,7 @@ def main() -> None:
         print(json.dumps(results[-1]), file=sys.stderr)
     rs.close()
     line = json.dumps(dict(board="7x7", net=Path(a.blob).name, hidden=int(H), games=games, positions=n, windows=WINDOWS,
-                           optimizer=f"AdamW(lr={a.lr})", augment=False, results=results))
+                           optimizer=f"AdamW(lr={a.lr})", augment=False, dropout=a.dropout, results=results))
     print(line)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
