@@ -5132,6 +5132,13 @@ int ar_debug_advance_clk(unsigned long long* out32) {
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ar::g_adv_clk), z, sizeof z));
     return AR_OK;
 }
+int ar_debug_backup16_clk(unsigned long long* out32) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out32, HIP_SYMBOL(ar::g_bk16_clk), sizeof(unsigned long long) * 32));
+    unsigned long long z[32] = {0};
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ar::g_bk16_clk), z, sizeof z));
+    return AR_OK;
+}
 int ar_debug_round_stats(unsigned long long* out32) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpyFromSymbol(out32, HIP_SYMBOL(ar::g_round_stats), sizeof(unsigned long long) * 32));

@@ -21,16 +21,29 @@
 //      path. Serving a node: find the entries that have it (sixteen LDS reads at its depth), load the header and the
 //      edges, apply finalize_score_update / update_multivisit of every such entry in entry order, exactly as
 //      backup_round does, store what changed. There is no fence inside the phase;
-//   3. collisions only subtract integers from in-flight counters: lanes take them 16 at a time and walk up with atomic
-//      subtractions, after the updates are done.
+//   3. collisions only subtract integers from in-flight counters (search.rs:860-889: a record's count comes off every
+//      ancestor of its node and off the two edges that lead down to it), and a record is only ever written for a node
+//      that is the leaf of an entry of the same batch (claimed at that moment, or claimed earlier in the batch and not
+//      yet visited: gw_visit, emit_coll's callers). So the record's way up is a path phase 1 has noted, and the three
+//      counters it meets at an ancestor are the header and the two edges phase 2 updates there for that entry. Between
+//      1 and 2 the lanes take the records sixteen at a time (the first two of a lane are loaded before the walk), find
+//      the lowest lane of the chunk whose leaf the record's node is (sixteen LDS compares) and add the count to that
+//      lane's total cm (bk16_fold); bk16_settle takes cm off after that entry's update of an ancestor, the leaf itself
+//      left alone. In-flight counts feed no float, so the subtraction commutes with everything else done to the node:
+//      the same bytes as the walk, no memory trip, no atomic, no barrier of its own. A record is folded in the first
+//      chunk that has its leaf and never again (a bit per record and lane); what no chunk takes -- a record without a
+//      node, on the leaf of an entry dropped with error 6, on a node that is no noted leaf, or beyond the 512th of a
+//      batch -- is walked up with atomic subtractions behind the last chunk (bk16_cancel_left), by the wavefronts that
+//      have one: in a regular batch none.
 // Levels are numbered from the leaf, so of a path longer than PATH_LDS_STEPS it is the root side that lives in scratch:
 // the lanes' scans at those depths are global loads (cached: sixteen lanes read the same few words). Searches with the
 // shipped constants stay near ten levels; tests/test_gpu_backup_merge.py has paths of forty.
 // A path longer than path_cap (never met: the cap is beyond the turn limit) flags the game with error 6 and drops that
 // entry alone; the other entries and later chunks are served (the pipeline this replaces stopped the lane for good).
-// Same arithmetic, same order per node as backup_round: trees are bit-identical. 1 and 2 are host-callable per lane
-// (bk16_walk, bk16_claim, bk16_apply: lanes meet only through the notes), and tests/hostsim_backup runs them on the CPU with the
-// lanes in ascending and in descending order against the entry-by-entry walk. End-of-batch bookkeeping (batch_end)
+// Same arithmetic, same order per node as backup_round: trees are bit-identical. 1, 2 and 3 are host-callable per lane
+// (bk16_walk, bk16_fold, bk16_claim, bk16_apply, bk16_cancel_left: lanes meet only through the notes), and
+// tests/hostsim_backup runs them on the CPU with the lanes in ascending and in descending order against the
+// entry-by-entry walk and the plain cancel walk. End-of-batch bookkeeping (batch_end)
 // is done by lane 0; the end of a move (extraction, sampling, record, step: finish_move) is left to k_finish.
 #pragma once
 #include "dev_search.h"
@@ -40,7 +53,8 @@ namespace ar {
 // one step of a path: node id (26 bits) | outcome pair of THIS node that leads to the level below (p1 3 bits, p2 3 bits)
 typedef uint32_t PathStep;
 // levels kept in LDS per lane; deeper ones go to the game's (idle) level-stack scratch. Twelve levels are 9.5 KB a
-// wavefront: sixteen wavefronts a CU, which the 128 registers of the kernel allow too (twenty would be ten)
+// wavefront (9.75 KB with the heads, cuts and collision totals; LDS is dealt in 1.25 KB steps, so 10 KB either way):
+// sixteen wavefronts a CU, which the 128 registers of the kernel allow too (twenty would be ten)
 enum { PATH_LDS_STEPS = 12 };
 enum { PATH_NODE_MASK = 0x3FFFFFF, PATH_LANES = 16 };
 AR_HD PathStep path_pack(uint32_t node, uint32_t o1, uint32_t o2) { return node | (o1 << 26) | (o2 << 29); }
@@ -77,6 +91,7 @@ struct PathNotes {
     uint32_t* cut;   // [16] first level (from the root) no lower lane has: bk16_claim
     PathNote* deep;
     uint32_t stride, deep_cap;
+    uint32_t* cm = nullptr;  // [16] collision total to cancel along the lane's path: bk16_fold (null: no totals)
 };
 AR_HD PathStep note_step(const PathNotes& P, uint32_t j, uint32_t l) {
     return l < PATH_LDS_STEPS ? P.step[l * P.stride + j] : P.deep[(size_t)j * P.deep_cap + (l - PATH_LDS_STEPS)].step;
@@ -225,6 +240,11 @@ AR_HD uint32_t bk16_settle(const PathNotes& P, uint32_t first_eval, uint32_t k, 
             finalize_h0(n.h0, q1, q2, 1);
             edge_update(e1, q1, 1);
             edge_update(e2, q2, 1);
+            // the collisions on this entry's leaf (search.rs:860-889): the three counters their walk would meet here
+            const uint32_t cmj = P.cm ? P.cm[j] : 0u;
+            n.h0.nif -= cmj;
+            e1.nif -= cmj;
+            e2.nif -= cmj;
             edge_place(n.e[0], a1, e1);
             edge_place(n.e[1], a2, e2);
             dirty |= (1u << a1) | (32u << a2);
@@ -300,6 +320,70 @@ AR_HD uint32_t bk16_apply(const PathNotes& P, uint32_t x, NodeStats* stats, cons
     return nv;
 }
 
+// ---- 3. collisions. A record (node, mv) asks for mv to be taken off the in-flight counters of every ancestor of `node`
+// and of the edges that lead down to it. The node of a record is the leaf of an entry of the same batch, so that path
+// is in the notes: the record's count goes to the lowest lane of the chunk whose leaf it is (cm, an LDS add), and
+// bk16_settle takes cm off while it has each ancestor in registers. Lane w has records w, 16 + w, ...; bit g of
+// `left` = record 16 g + w is still to be cancelled (the first 512 records of a batch: later ones are walked).
+AR_HD uint32_t bk16_coll_mask(uint32_t n_coll, uint32_t w) {
+    const uint32_t mine = n_coll > w ? (n_coll - w + PATH_LANES - 1) / PATH_LANES : 0u;
+    return mine >= 32u ? ~0u : (1u << mine) - 1u;
+}
+AR_HD bool bk16_fold_one(const PathNotes& P, CollEntry ce) {
+    uint32_t j = PATH_LANES;
+#pragma unroll 4
+    for (uint32_t i = PATH_LANES; i-- > 0;)  // (an entry dropped with error 6 has no length and notes no leaf)
+        if (head_len(P.head[i]) != 0 && (note_step(P, i, 0) & PATH_NODE_MASK) == ce.node) j = i;
+    if (j == PATH_LANES) return false;
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicAdd(&P.cm[j], ce.mv);
+#else
+    P.cm[j] += ce.mv;
+#endif
+    return true;
+}
+// Lane w folds what it can of its records into this chunk's totals and returns what is left. Every lane's notes must be
+// complete and cm zeroed before the first lane folds; `c0`, `c1` = the lane's first two records (read before the walk).
+AR_HD uint32_t bk16_fold(const PathNotes& P, uint32_t w, const CollEntry* coll, uint32_t left, CollEntry c0, CollEntry c1) {
+    if (P.cm == nullptr) return left;
+    if ((left & 1u) && bk16_fold_one(P, c0)) left &= ~1u;
+    if ((left & 2u) && bk16_fold_one(P, c1)) left &= ~2u;
+    for (uint32_t g = 2; g < 32u && (left >> g) != 0; ++g)
+        if (((left >> g) & 1u) && bk16_fold_one(P, coll[g * PATH_LANES + w])) left &= ~(1u << g);
+    return left;
+}
+// What no chunk folded (a record without a node, on the leaf of a dropped entry, on a node that is no entry's leaf, or
+// past the 512th) is walked up with subtractions, atomic on the device, after all the updates are stored. Returns the
+// number of records walked (`steps`, if given, takes the number of levels).
+AR_HD uint32_t bk16_cancel_left(uint32_t w, const CollEntry* coll, uint32_t n_coll, uint32_t left, NodeStats* stats,
+                                uint32_t* steps = nullptr) {
+    uint32_t walked = 0;
+    for (uint32_t g = 0; g * PATH_LANES + w < n_coll; ++g) {
+        if (g < 32u && !((left >> g) & 1u)) continue;
+        const CollEntry ce = coll[g * PATH_LANES + w];
+        if (ce.node == NIL) continue;
+        walked += 1;
+        for (uint32_t cur = ce.node;;) {
+            const NodeH1 h = stats[cur].h1;
+            const NodeH2 c = stats[cur].h2;
+            if (h.parent == NIL) break;
+            NodeStats& Q = stats[h.parent];
+#if defined(__HIP_DEVICE_COMPILE__)
+            atomicSub(&Q.h0.nif, ce.mv);
+            atomicSub(&Q.e[0][meta_po(c.meta, 0)].nif, ce.mv);
+            atomicSub(&Q.e[1][meta_po(c.meta, 1)].nif, ce.mv);
+#else
+            Q.h0.nif -= ce.mv;
+            Q.e[0][meta_po(c.meta, 0)].nif -= ce.mv;
+            Q.e[1][meta_po(c.meta, 1)].nif -= ce.mv;
+#endif
+            cur = h.parent;
+            if (steps) *steps += 1;
+        }
+    }
+    return walked;
+}
+
 }  // namespace ar
 
 #if defined(__HIPCC__)
@@ -308,8 +392,22 @@ namespace ar {
 __device__ inline uint32_t grp_pick(uint32_t v, uint32_t w) {  // value of group lane `w` (16 lanes per game)
     return (uint32_t)__shfl((int)v, (int)((threadIdx.x & 48u) | w), 64);
 }
-// LDS of a wavefront: step, q1, q2 [PATH_LDS_STEPS][64], one head word and one cut per lane
-enum { BACKUP16_LDS_BYTES = (3 * PATH_LDS_STEPS + 2) * 64 * 4 };
+// LDS of a wavefront: step, q1, q2 [PATH_LDS_STEPS][64], one head word, one cut and one collision total per lane
+enum { BACKUP16_LDS_BYTES = (3 * PATH_LDS_STEPS + 3) * 64 * 4 };
+
+#if defined(AR_STATS)
+// tools/bk16_stats.py. [0] wavefronts; 100 MHz clocks of a wavefront in [1] entries and sort, [2] walk, [3] claim + apply,
+// [4] collisions, [5] all of backup16(); [6] batches, [7] collision records, [8] chunks, [9] records whose node is the
+// leaf of an entry of a chunk, [10] records with node NIL, [11] (record, level) steps of the atomic walks (three
+// atomics each), [12] rounds of the walk loop (a wavefront's trips in sequence), [13] deepest path of a wavefront's
+// chunk, summed over [14] chunks of wavefronts, [15] wavefronts that walked at all
+__device__ unsigned long long g_bk16_clk[32];
+#define BK_STAT(...) __VA_ARGS__
+#else
+#define BK_STAT(...)
+#endif
+// the clock since the last mark goes to phase k
+#define BK_MARK(k) BK_STAT({ const unsigned long long bs_now = wall_clock64(); bs_clk[k] += bs_now - bs_t; bs_t = bs_now; })
 
 // A batch that evaluates the ROOT (a fresh tree's first batch: one entry) draws Dirichlet noise (search.rs:1036-1050,
 // the Gamma sampler is a hundred registers of code): such games are left to the lane-per-game kernel, which the host
@@ -336,15 +434,28 @@ __device__ inline void backup16(bool active, Slot<NW>& S, const Mem<NW>& m, cons
         P.q2 = (float*)(lds + 2 * PATH_LDS_STEPS * 64 + g0);
         P.head = lds + 3 * PATH_LDS_STEPS * 64 + g0;
         P.cut = lds + (3 * PATH_LDS_STEPS + 1) * 64 + g0;
+        P.cm = lds + (3 * PATH_LDS_STEPS + 2) * 64 + g0;
         P.deep = (PathNote*)m.levels;  // (not in use between gather and gather)
         P.stride = 64;
         P.deep_cap = path_cap > PATH_LDS_STEPS ? path_cap - PATH_LDS_STEPS : 0u;
     }
     uint32_t err = 0;
     uint32_t nv = 0;  // node records updated (the lane kernel's nv_backup)
+    BK_STAT(unsigned long long bs_clk[4] = {0, 0, 0, 0}, bs_cnt[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, bs_t = wall_clock64();
+            const unsigned long long bs_t0 = bs_t;
+            if (active && w == 0) { bs_cnt[0] = 1; bs_cnt[1] = n_coll; })
+    uint32_t left = bk16_coll_mask(n_coll, w);  // the lane's collision records no chunk has folded yet
     for (uint32_t base = 0; __any(base < n_proc); base += 16) {
+        BK_STAT(if (w == 0 && base < n_proc) bs_cnt[2] += 1;)
         const uint32_t e = base + w;
         const bool mine = e < n_proc;
+        // the lane's first two collision records: nothing in the walk waits for them, they arrive under it
+        CollEntry c0, c1;
+        c0.node = c1.node = NIL;
+        c0.mv = c1.mv = 0;
+        if (left & 1u) c0 = m.coll[w];
+        if (left & 2u) c1 = m.coll[PATH_LANES + w];
+        P.cm[w] = 0;
         ProcEntry pe;
         pe.node = NIL;
         pe.kind = proc_none();
@@ -363,42 +474,56 @@ __device__ inline void backup16(bool active, Slot<NW>& S, const Mem<NW>& m, cons
             pe.kind = grp_pick(pe.kind, src);
             // (entries without a batch entry sort last: lanes >= n_proc - base get those)
         }
+        BK_MARK(0)
         // ---- 1. the path of entry e, noted for all
         err |= bk16_walk(P, w, mine, pe.node, pe.kind, m.stats, ev, path_cap);
         __syncthreads();  // (one wavefront: a wait for the notes, those in scratch included)
+        BK_MARK(1)
+        BK_STAT({
+            uint32_t d = head_len(P.head[w]);
+            for (int off = 32; off > 0; off >>= 1) d = max(d, (uint32_t)__shfl_xor((int)d, off, 64));
+            if ((threadIdx.x & 63u) == 0) { bs_cnt[7] += d; bs_cnt[8] += 1; }
+            bs_t = wall_clock64();
+        })
+        // ---- 3. a collision record on a leaf of this chunk goes to that lane's total (LDS only; the barrier below
+        // orders the adds before phase 2 reads them, the one that ends the chunk orders the reads before the next zero)
+        {
+            const uint32_t was = left;
+            left = bk16_fold(P, w, m.coll, was, c0, c1);
+            BK_STAT(bs_cnt[3] += (unsigned long long)__popc(was ^ left);)
+        }
+        BK_MARK(3)
         // ---- 2. every node once: the lowest lane that has it lists it, the list is dealt round the group
         bk16_claim(P, w);
         __syncthreads();
         nv += bk16_apply(P, w, m.stats, ev);
         // a later chunk reads what this one stored, and phase 3's atomics hit words the stores wrote
         __syncthreads();
+        BK_MARK(2)
     }
-    // ---- 3. collisions (search.rs:860-889): integer subtractions, any order, atomics where paths meet
-    for (uint32_t base = 0; __any(base < n_coll); base += 16) {
-        const uint32_t e = base + w;
-        uint32_t cur = NIL, mv = 0;
-        if (e < n_coll) {
-            const CollEntry ce = m.coll[e];
-            cur = ce.node;
-            mv = ce.mv;
-        }
-        bool walking = cur != NIL;
-        while (__any(walking)) {
-            if (walking) {
-                const NodeH1 h = m.stats[cur].h1;
-                const NodeH2 c = m.stats[cur].h2;
-                if (h.parent == NIL) {
-                    walking = false;
-                } else {
-                    NodeStats& P = m.stats[h.parent];
-                    atomicSub(&P.h0.nif, mv);
-                    atomicSub(&P.e[0][meta_po(c.meta, 0)].nif, mv);
-                    atomicSub(&P.e[1][meta_po(c.meta, 1)].nif, mv);
-                    cur = h.parent;
-                }
-            }
-        }
+    // ---- 3, the rest: what no chunk folded is walked up, atomics where paths meet (none at all in a regular batch)
+    if (__any(left != 0 || n_coll > 32u * PATH_LANES)) {
+        BK_STAT(uint32_t steps = 0;)
+        bk16_cancel_left(w, m.coll, n_coll, left, m.stats BK_STAT(, &steps));
+        BK_STAT(bs_cnt[5] += steps; if ((threadIdx.x & 63u) == 0) bs_cnt[9] |= 1;
+                {
+                    uint32_t d = steps;  // (the slowest lane's levels: the wavefront's trips in sequence)
+                    for (int off = 32; off > 0; off >>= 1) d = max(d, (uint32_t)__shfl_xor((int)d, off, 64));
+                    if ((threadIdx.x & 63u) == 0) bs_cnt[6] += d;
+                })
     }
+    BK_MARK(3)
+    BK_STAT(for (uint32_t g = 0; g * PATH_LANES + w < n_coll; ++g) if (m.coll[g * PATH_LANES + w].node == NIL) bs_cnt[4] += 1;)
+    BK_STAT({
+        for (int k = 0; k < 10; ++k)
+            for (int off = 32; off > 0; off >>= 1) bs_cnt[k] += (unsigned long long)(uint32_t)__shfl_xor((int)(uint32_t)bs_cnt[k], off, 64);
+        if ((threadIdx.x & 63u) == 0) {
+            atomicAdd(&g_bk16_clk[0], 1ULL);
+            for (int k = 0; k < 4; ++k) atomicAdd(&g_bk16_clk[1 + k], bs_clk[k]);
+            atomicAdd(&g_bk16_clk[5], bs_t - bs_t0);
+            for (int k = 0; k < 10; ++k) atomicAdd(&g_bk16_clk[6 + k], bs_cnt[k]);
+        }
+    })
     // counters: sum over the group's lanes, written by lane 0
     for (int off = 8; off > 0; off >>= 1) {
         nv += (uint32_t)__shfl_xor((int)nv, off, 64);
