@@ -246,6 +246,27 @@ class ArTrainDropout(C.Structure):
     _fields_ = [("p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64)]
 
 
+class ArCnnDims(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("channels", "player_dim", "hidden_dim", "n_blocks")]
+
+
+# ArCnnTensors and ArCnnBnStats hold eight block slots each, as flat pointers: a model of B blocks fills the first B
+CNN_MAX_BLOCKS = 8
+CNN_BLOCK_TENSORS = ("bn1_w", "bn1_b", "conv1_w", "bn2_w", "bn2_b", "conv2_w")
+CNN_TENSORS = (("stem_w", "stem_bn_w", "stem_bn_b") + tuple(f"b{b}_{k}" for b in range(CNN_MAX_BLOCKS) for k in CNN_BLOCK_TENSORS)
+               + ("enc_w", "enc_b", "comb_w", "comb_b", "policy_w", "policy_b", "value_w", "value_b"))
+CNN_BLOCK_STATS = ("bn1_mean", "bn1_var", "bn2_mean", "bn2_var")
+CNN_STATS = ("stem_mean", "stem_var") + tuple(f"b{b}_{k}" for b in range(CNN_MAX_BLOCKS) for k in CNN_BLOCK_STATS)
+
+
+class ArCnnTensors(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in CNN_TENSORS]
+
+
+class ArCnnBnStats(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in CNN_STATS]
+
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -309,6 +330,9 @@ EXPORTS = {
     "ar_rows_grad_local_value_dropout": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(ArLvTensors),
                                                    C.POINTER(ArLvTensors), C.POINTER(ArMlpBnStats), C.c_float, C.c_float,
                                                    C.c_float, C.POINTER(ArLvTrainOut), C.POINTER(ArTrainDropout), C.c_void_p]),
+    "ar_rows_grad_cnn": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ArCnnDims), C.POINTER(ArCnnTensors),
+                                   C.POINTER(ArCnnTensors), C.POINTER(ArCnnBnStats), C.c_float, C.c_float,
+                                   C.POINTER(ArTrainOut), C.c_void_p]),
     "ar_train_dropout_mask": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p,
                                         C.c_void_p]),
 }

@@ -40,6 +40,7 @@
 #include "train_mlp.h"
 #include "train_sym.h"
 #include "train_lv.h"
+#include "train_cnn.h"
 #include "host_games.h"
 #include "zig_norm_tables.inc"
 
@@ -3809,6 +3810,246 @@ int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, c
     return T.end();
 }
 
+// ar_rows_grad_cnn: the loss and the gradients of PyRatCNN over rows first .. first + n of the order, on the caller's
+// stream: train_cnn.h's chain, under TrainStep's rules. A trunk activation is [R][C] with R = n hw; the heads' arrays hold
+// P1's n rows, then P2's, as in rows_grad_symmetric.
+template <int NW>
+int rows_grad_cnn(RowStore& R, uint64_t first, uint64_t n64, const ArCnnDims& dims, const ArCnnTensors& p, const ArCnnTensors& g,
+                  const ArCnnBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream) {
+    static_assert(sizeof(ArCnnTensors) == 59 * sizeof(float*) && sizeof(ArCnnBlock) == 6 * sizeof(float*), "3 + 8 * 6 + 8 pointers");
+    static_assert(sizeof(ArCnnBnStats) == 34 * sizeof(float*), "2 + 8 * 4 pointers");
+    const uint32_t Cu = dims.channels, PDu = dims.player_dim, HDu = dims.hidden_dim, Bu = dims.n_blocks;
+    if (Cu == 0 || Cu % 32 != 0 || Cu > 256)
+        return fail(AR_E_INVALID, "channels must be a multiple of 32, at most 256 (got " + std::to_string(Cu) + ")");
+    if (PDu == 0 || PDu > 256) return fail(AR_E_INVALID, "player_dim must be 1 to 256 (got " + std::to_string(PDu) + ")");
+    if (Bu > (uint32_t)CNN_MAX_BLOCKS_TRAIN) return fail(AR_E_INVALID, "at most 8 residual blocks (got " + std::to_string(Bu) + ")");
+    if (R.hw < 2 || R.hw > 256)  // (k_cnn_split's 5 n hw threads also fill the 6n side elements)
+        return fail(AR_E_INVALID, "boards of 2 to 256 cells (this one has " + std::to_string(R.hw) + ")");
+    if (n64 <= (uint64_t)TRAIN_MAX_ROWS && n64 * R.hw > (uint64_t)CNN_MAX_TRUNK_ROWS)  // (more rows than that: check's refusal)
+        return fail(AR_E_INVALID, "n * h * w is " + std::to_string(n64 * R.hw) + ": at most 2^22 trunk rows a step");
+    // the tensors that B blocks use, under their names
+    std::vector<std::string> names = {"stem_w", "stem_bn_w", "stem_bn_b"};
+    std::vector<float*> ps = {p.stem_w, p.stem_bn_w, p.stem_bn_b}, gs = {g.stem_w, g.stem_bn_w, g.stem_bn_b}, rs;
+    if (run) rs = {run->stem_mean, run->stem_var};
+    for (uint32_t b = 0; b < Bu; ++b) {
+        static const char* const kBlock[6] = {"bn1_w", "bn1_b", "conv1_w", "bn2_w", "bn2_b", "conv2_w"};
+        const ArCnnBlock &pb = p.blocks[b], &gb = g.blocks[b];
+        float* const pk[6] = {pb.bn1_w, pb.bn1_b, pb.conv1_w, pb.bn2_w, pb.bn2_b, pb.conv2_w};
+        float* const gk[6] = {gb.bn1_w, gb.bn1_b, gb.conv1_w, gb.bn2_w, gb.bn2_b, gb.conv2_w};
+        for (int k = 0; k < 6; ++k) {
+            names.push_back("blocks[" + std::to_string(b) + "]." + kBlock[k]);
+            ps.push_back(pk[k]);
+            gs.push_back(gk[k]);
+        }
+        if (run) {
+            const ArCnnBlockStats& rb = run->blocks[b];
+            rs.insert(rs.end(), {rb.bn1_mean, rb.bn1_var, rb.bn2_mean, rb.bn2_var});
+        }
+    }
+    {
+        static const char* const kTail[8] = {"enc_w", "enc_b", "comb_w", "comb_b", "policy_w", "policy_b", "value_w", "value_b"};
+        float* const pk[8] = {p.enc_w, p.enc_b, p.comb_w, p.comb_b, p.policy_w, p.policy_b, p.value_w, p.value_b};
+        float* const gk[8] = {g.enc_w, g.enc_b, g.comb_w, g.comb_b, g.policy_w, g.policy_b, g.value_w, g.value_b};
+        for (int k = 0; k < 8; ++k) {
+            names.push_back(kTail[k]);
+            ps.push_back(pk[k]);
+            gs.push_back(gk[k]);
+        }
+    }
+    std::vector<const char*> name_ptrs;
+    for (const std::string& s : names) name_ptrs.push_back(s.c_str());
+    TrainStep T{R, stream};
+    if (int rc = T.check(first, n64, HDu, name_ptrs.data(), ps.data(), gs.data(), (int)ps.size(), rs.data(), (int)rs.size(), out))
+        return rc;
+    const int n = T.n, n2 = 2 * n, hw = (int)R.hw, C = (int)Cu, PD = (int)PDu, HD = (int)HDu, B = (int)Bu, W = C + PD;
+    const int Rr = n * hw;
+    const TrainCols tcR = cnn_cols(n, hw, C);
+    TrainCols tc1 = tcR;  // what the column kernels see once the parts are collapsed: the same rows per part, one row of totals
+    tc1.P = 1;
+    const TrainSplit spR = cnn_split(n, hw), sp2 = train_split(n2);
+    const size_t act = (size_t)Rr * C * 4;
+    T.take_rows();
+    const size_t o_x5 = T.take((size_t)Rr * 5 * 4), o_side = T.take((size_t)n2 * 3 * 4), o_cells = T.take((size_t)n2 * 4),
+                 o_zs = T.take(act), o_x = T.take((size_t)(B + 1) * act), o_blk = T.take((size_t)3 * B * act), o_g = T.take(act),
+                 o_d = T.take(act), o_e = T.take(act), o_ze = T.take((size_t)n2 * PD * 4), o_cat = T.take((size_t)n2 * W * 4),
+                 o_zc = T.take((size_t)n2 * HD * 4), o_h = T.take((size_t)n2 * HD * 4), o_d12 = T.take((size_t)n2 * 48),
+                 o_dzc = T.take((size_t)n2 * HD * 4), o_dcat = T.take((size_t)n2 * W * 4), o_dze = T.take((size_t)n2 * PD * 4),
+                 o_parts = T.take((size_t)2 * CNN_MAX_PARTS * C * 8), o_tot = T.take((size_t)2 * C * 8),
+                 o_mean = T.take((size_t)(2 * B + 1) * C * 8), o_rstd = T.take((size_t)(2 * B + 1) * C * 4),
+                 o_wpart = T.take(std::max((size_t)spR.S * C * 9 * C, (size_t)sp2.S * std::max(HD * W, 12 * HD)) * 4),
+                 o_bpart = T.take((size_t)sp2.S * 256 * 4), o_scr = T.take((size_t)256 * 4);
+    T.take_losses();
+    if (int rc = T.begin()) return rc;
+    float *X5 = T.f(o_x5), *Side = T.f(o_side), *Zs = T.f(o_zs), *G = T.f(o_g), *Dd = T.f(o_d), *E = T.f(o_e), *Ze = T.f(o_ze),
+          *Cat = T.f(o_cat), *Zc = T.f(o_zc), *Hh = T.f(o_h), *D12 = T.f(o_d12), *dZc = T.f(o_dzc), *dCat = T.f(o_dcat),
+          *dZe = T.f(o_dze), *rstds = T.f(o_rstd), *scr = T.f(o_scr);
+    int* cells = (int*)(T.ws + o_cells);
+    double *parts = T.d(o_parts), *tots = T.d(o_tot), *means = T.d(o_mean);
+    T.wpart = T.f(o_wpart);
+    T.bpart = T.f(o_bpart);
+    auto xs = [&](int b) { return T.f(o_x) + (size_t)b * Rr * C; };                 // the residual stream x_b
+    auto blk = [&](int b, int i) { return T.f(o_blk) + (size_t)(3 * b + i) * Rr * C; };  // a block's a, z, a'
+    double *part0 = parts, *part1 = parts + (size_t)CNN_MAX_PARTS * C, *tot0 = tots, *tot1 = tots + C;
+    const dim3 cgrid((C + 63) / 64, tcR.P), colgrid((C + 255) / 256);
+    // one BatchNorm call over the R rows at z (0: stem_bn; 1 + 2 b, 2 + 2 b: block b's bn1, bn2)
+    auto bn_forward = [&](int call, const float* z, const float* gamma, const float* beta, float* a, float* rm, float* rv) {
+        if (!T.ok()) return;
+        TrainColArgs ca;
+        memset(&ca, 0, sizeof ca);
+        ca.z = z;
+        ca.part0 = part0;
+        hipLaunchKernelGGL(k_train_colsum<TC_SUM>, cgrid, dim3(256), 0, stream, tcR, ca);
+        hipLaunchKernelGGL(k_cnn_collapse, colgrid, dim3(256), 0, stream, tcR.P, C, (const double*)part0, tot0, (const double*)nullptr,
+                           (double*)nullptr);
+        ca.sum_in = tot0;
+        ca.part0 = part1;
+        hipLaunchKernelGGL(k_train_colsum<TC_SQ>, cgrid, dim3(256), 0, stream, tc1, ca);
+        hipLaunchKernelGGL(k_cnn_collapse, colgrid, dim3(256), 0, stream, tcR.P, C, (const double*)part1, tot1, (const double*)nullptr,
+                           (double*)nullptr);
+        hipLaunchKernelGGL(k_train_bn_apply, cgrid, dim3(256), 0, stream, tc1, z, (const double*)tot0, (const double*)tot1, gamma, beta,
+                           a, means + (size_t)call * C, rstds + (size_t)call * C, rm, rv);
+        T.launched();
+    };
+    // dz in place of dA at d, through the ReLU whose output is a
+    auto bn_backward = [&](int call, const float* z, const float* a, float* d, const float* gamma, float* dgamma, float* dbeta) {
+        if (!T.ok()) return;
+        const double* mu = means + (size_t)call * C;
+        const float* rstd = rstds + (size_t)call * C;
+        const TrainColArgs ca = TrainStep::backward_args(z, a, d, mu, rstd, part0, part1);
+        hipLaunchKernelGGL(k_train_colsum<TC_DTRUNK>, cgrid, dim3(256), 0, stream, tcR, ca);
+        hipLaunchKernelGGL(k_cnn_collapse, colgrid, dim3(256), 0, stream, tcR.P, C, (const double*)part0, tot0, (const double*)part1, tot1);
+        hipLaunchKernelGGL(k_train_bn_bwd, cgrid, dim3(256), 0, stream, tc1, z, d, (const double*)tot0, (const double*)tot1, mu, rstd,
+                           gamma, dgamma, dbeta);
+        T.launched();
+    };
+    auto conv_args = [&](const float* x, const float* w, const float* d, const float* add, float* c, int Cin) {
+        TrainConv t;
+        t.x = x, t.w = w, t.d = d, t.add = add, t.c = c;
+        t.R = Rr, t.hw = hw, t.bw = (int)R.width, t.bh = (int)R.height, t.Cin = Cin, t.Cout = C;
+        t.k_per_split = 9 * C;  // (FWD, DIN: one range, and K is at most this)
+        t.c_split = 0;
+        return t;
+    };
+    const unsigned mtiles = (unsigned)((Rr + TG_TILE - 1) / TG_TILE), ctiles = (unsigned)((C + TG_TILE - 1) / TG_TILE);
+    auto conv = [&](const float* in, int Cin, const float* w, const float* add, float* o) {
+        if (!T.ok()) return;
+        hipLaunchKernelGGL(k_train_conv3<CV_FWD>, dim3(mtiles, ctiles, 1), dim3(TG_THREADS), 0, stream, conv_args(in, w, nullptr, add, o, Cin));
+        T.launched();
+    };
+    auto conv_din = [&](const float* dout, const float* w, float* din) {
+        if (!T.ok()) return;
+        hipLaunchKernelGGL(k_train_conv3<CV_DIN>, dim3(mtiles, ctiles, 1), dim3(TG_THREADS), 0, stream,
+                           conv_args(dout, w, nullptr, nullptr, din, C));
+        T.launched();
+    };
+    auto conv_dw = [&](const float* dout, const float* in, int Cin, float* dw) {
+        if (!T.ok()) return;
+        TrainConv t = conv_args(in, nullptr, dout, nullptr, T.wpart, Cin);
+        t.k_per_split = spR.kps;
+        t.c_split = (size_t)C * 9 * Cin;
+        hipLaunchKernelGGL(k_train_conv3<CV_DW>, dim3((unsigned)((9 * Cin + TG_TILE - 1) / TG_TILE), ctiles, spR.S), dim3(TG_THREADS), 0,
+                           stream, t);
+        TrainReduce tr;
+        tr.wpart = T.wpart;
+        // A convolution here has no bias, and k_train_reduce always reduces M bias lanes beside the M x N weights. They are
+        // given something harmless to do: bpart = wpart, so lane j adds wpart[k * M + j], k < S -- inside the S * M * N floats of
+        // the partial products -- and writes the sum to scr[j], j < C <= 256, a scratch row nobody reads (train_mlp.h TrainReduce).
+        tr.bpart = T.wpart;
+        tr.S = spR.S, tr.M = C, tr.N = 9 * Cin;
+        tr.w[0] = dw, tr.w[1] = tr.w[2] = nullptr;
+        tr.b[0] = scr, tr.b[1] = tr.b[2] = nullptr;
+        tr.rows[0] = C, tr.rows[1] = tr.rows[2] = 0;
+        hipLaunchKernelGGL(k_train_reduce, TrainStep::blocks((size_t)C * 9 * Cin + C), dim3(256), 0, stream, tr);
+        T.launched();
+    };
+    T.rows<NW>(first);
+    if (T.ok()) {
+        hipLaunchKernelGGL(k_cnn_split, TrainStep::blocks((size_t)Rr * 5), dim3(256), 0, stream, (const float*)T.ro.observation, X5, Side,
+                           cells, n, hw);
+        T.launched();
+    }
+    // forward: the trunk
+    conv(X5, 5, p.stem_w, nullptr, Zs);
+    bn_forward(0, Zs, p.stem_bn_w, p.stem_bn_b, xs(0), run ? run->stem_mean : nullptr, run ? run->stem_var : nullptr);
+    for (int b = 0; b < B; ++b) {
+        const ArCnnBlock& q = p.blocks[b];
+        bn_forward(1 + 2 * b, xs(b), q.bn1_w, q.bn1_b, blk(b, 0), run ? run->blocks[b].bn1_mean : nullptr,
+                   run ? run->blocks[b].bn1_var : nullptr);
+        conv(blk(b, 0), C, q.conv1_w, nullptr, blk(b, 1));
+        bn_forward(2 + 2 * b, blk(b, 1), q.bn2_w, q.bn2_b, blk(b, 2), run ? run->blocks[b].bn2_mean : nullptr,
+                   run ? run->blocks[b].bn2_var : nullptr);
+        conv(blk(b, 2), C, q.conv2_w, xs(b), xs(b + 1));
+    }
+    // the player cells and the heads
+    T.gemm(Side, 3, 1, 1, p.enc_w, 1, 3, 1, Ze, n2, PD, 3, p.enc_b, 1, 3, nullptr);
+    if (T.ok()) {
+        hipLaunchKernelGGL(k_cnn_gather, TrainStep::blocks((size_t)n2 * W), dim3(256), 0, stream, (const float*)xs(B), (const int*)cells,
+                           (const float*)Ze, Cat, n, hw, C, PD);
+        T.launched();
+    }
+    T.gemm(Cat, W, 1, 1, p.comb_w, 1, W, 1, Zc, n2, HD, W, p.comb_b, 1, W, nullptr);
+    if (T.ok()) {
+        const size_t c4 = (size_t)n2 * HD / 4;
+        hipLaunchKernelGGL(k_train_lv_relu, TrainStep::blocks(c4), dim3(256), 0, stream, (const float4*)Zc, (float4*)Hh, c4);
+        SymHeads t;
+        t.h = Hh;
+        t.w_p = p.policy_w, t.b_p = p.policy_b, t.w_v = p.value_w, t.b_v = p.value_b;
+        t.t1 = T.ro.policy_p1, t.t2 = T.ro.policy_p2, t.y1 = T.ro.value_p1, t.y2 = T.ro.value_p2;
+        t.d12 = D12;
+        t.loss_part = T.d(T.o_lpart);
+        t.logits_p1 = out ? out->logits_p1 : nullptr;
+        t.logits_p2 = out ? out->logits_p2 : nullptr;
+        t.value_p1 = out ? out->value_p1 : nullptr;
+        t.value_p2 = out ? out->value_p2 : nullptr;
+        t.n = n;
+        t.H = HD;
+        t.pw_n = pw / (float)n;
+        t.vw_n = vw / (float)n;
+        hipLaunchKernelGGL(k_sym_heads, dim3(T.head_blocks), dim3(256), (size_t)12 * HD * 4, stream, t);
+        T.loss_sum(pw, vw, out);
+    }
+    // backward: the heads, the combiner, the encoder
+    T.gemm(D12, 1, 12, 0, Hh, HD, 1, 0, T.wpart, 12, HD, n2, nullptr, sp2.S, sp2.kps, T.bpart);
+    if (T.ok()) {
+        hipLaunchKernelGGL(k_sym_head_reduce, TrainStep::blocks((size_t)12 * HD + 6), dim3(256), 0, stream, (const float*)T.wpart,
+                           (const float*)T.bpart, sp2.S, HD, g.policy_w, g.policy_b, g.value_w, g.value_b);
+        hipLaunchKernelGGL(k_cnn_dhead, TrainStep::blocks((size_t)n2 * HD), dim3(256), 0, stream, (const float*)D12, (const float*)p.policy_w,
+                           (const float*)p.value_w, (const float*)Hh, dZc, n2, HD);
+        T.launched();
+    }
+    T.grad_w(dZc, HD, Cat, W, n2, sp2, {g.comb_w, g.comb_b, HD});
+    T.grad_in(dZc, n2, p.comb_w, W, dCat, HD);
+    if (T.ok()) {
+        hipLaunchKernelGGL(k_cnn_enc_bwd, TrainStep::blocks((size_t)n2 * PD), dim3(256), 0, stream, (const float*)dCat, (const float*)Ze, dZe,
+                           n2, C, PD);
+        T.launched();
+    }
+    T.grad_w(dZe, PD, Side, 3, n2, sp2, {g.enc_w, g.enc_b, PD});
+    if (T.ok()) {
+        hipLaunchKernelGGL(k_cnn_scatter, TrainStep::blocks((size_t)Rr * C), dim3(256), 0, stream, (const float*)dCat, (const int*)cells, G,
+                           n, hw, C, PD);
+        T.launched();
+    }
+    // the trunk, G the gradient of the residual stream
+    for (int b = B - 1; b >= 0; --b) {
+        const ArCnnBlock &q = p.blocks[b], &gq = g.blocks[b];
+        conv_dw(G, blk(b, 2), C, gq.conv2_w);
+        conv_din(G, q.conv2_w, Dd);
+        bn_backward(2 + 2 * b, blk(b, 1), blk(b, 2), Dd, q.bn2_w, gq.bn2_w, gq.bn2_b);
+        conv_dw(Dd, blk(b, 0), C, gq.conv1_w);
+        conv_din(Dd, q.conv1_w, E);
+        bn_backward(1 + 2 * b, xs(b), blk(b, 0), E, q.bn1_w, gq.bn1_w, gq.bn1_b);
+        if (T.ok()) {
+            const size_t c4 = (size_t)Rr * C / 4;
+            hipLaunchKernelGGL(k_cnn_add, TrainStep::blocks(c4), dim3(256), 0, stream, (float4*)G, (const float4*)E, c4);
+            T.launched();
+        }
+    }
+    bn_backward(0, Zs, xs(0), G, p.stem_bn_w, g.stem_bn_w, g.stem_bn_b);
+    conv_dw(G, X5, 5, g.stem_w);
+    return T.end();
+}
+
 // ar_rows_validate: the request in chunks of `chunk` rows -- requests from the stored records (k_val_requests), the
 // evaluator with its logits output (net_launch), the terms of every row summed per block (k_val_terms) and added to the
 // running total (k_val_sum) -- all on the null stream; blocks until the sums are on the host. No observation, no target
@@ -5398,6 +5639,16 @@ int ar_rows_grad_symmetric(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hid
                            const ArTrainOut* out, void* stream) {
     return ar_rows_grad_symmetric_dropout(s, first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out,
                                           nullptr, stream);
+}
+
+int ar_rows_grad_cnn(ArRowSet* s, uint64_t first, uint64_t n, const ArCnnDims* dims, const ArCnnTensors* params,
+                     const ArCnnTensors* grads, const ArCnnBnStats* running, float policy_weight, float value_weight,
+                     const ArTrainOut* out, void* stream) {
+    if (!s || !s->impl || !dims || !params || !grads) return fail(AR_E_INVALID, "null argument");
+    return s->impl->nw == 1 ? rows_grad_cnn<1>(*s->impl, first, n, *dims, *params, *grads, running, policy_weight, value_weight, out,
+                                               (hipStream_t)stream)
+                            : rows_grad_cnn<4>(*s->impl, first, n, *dims, *params, *grads, running, policy_weight, value_weight, out,
+                                               (hipStream_t)stream);
 }
 
 int ar_train_dropout_mask(uint64_t seed, uint64_t step, uint32_t call, uint64_t n, uint32_t hidden_dim, float p,

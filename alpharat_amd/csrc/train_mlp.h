@@ -124,6 +124,8 @@ __global__ void __launch_bounds__(TG_THREADS) k_train_gemm(TrainGemm g) {
 
 // The split partial products and partial column sums added in split order, in double, into up to three destinations: the
 // rows of C are cut into consecutive segments of rows[0], rows[1], rows[2] rows (the three heads; one segment otherwise).
+// The M bias lanes always run: a product without a bias (the convolutions of train_cnn.h) points bpart at any S * M readable
+// floats and b[0] at M floats of scratch.
 struct TrainReduce {
     const float *wpart, *bpart;  // [S][M][N], [S][M]
     int S, M, N;

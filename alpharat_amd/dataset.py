@@ -24,7 +24,7 @@ from typing import Iterator
 import numpy as np
 
 from .shards import KEYS, RowSet, row_shapes
-from .train import LocalValueGradStep, MLPGradStep, SymmetricGradStep  # noqa: F401  (exported beside RowDataset)
+from .train import CNNGradStep, LocalValueGradStep, MLPGradStep, SymmetricGradStep  # noqa: F401  (exported beside RowDataset)
 
 
 def epoch_plan(n: int, seed: int, epoch: int, shuffle: bool = True, augment: bool = True,
@@ -136,7 +136,7 @@ class RowDataset:
             rs.build_into(first, n, out)
             yield out
 
-    def grad_iter(self, step: "MLPGradStep | SymmetricGradStep | LocalValueGradStep", batch_size: int, *, epoch: int = 0,
+    def grad_iter(self, step: "MLPGradStep | SymmetricGradStep | LocalValueGradStep | CNNGradStep", batch_size: int, *, epoch: int = 0,
                   seed: int = 0, augment: bool = True, p_swap: float = 0.5, shuffle: bool = True,
                   drop_last: bool = True) -> Iterator[tuple]:
         """One epoch as training steps: the plan, the order and the order-token rule of ``epoch_iter``, but instead of
@@ -145,9 +145,10 @@ class RowDataset:
         ``LocalValueGradStep``, ``loss_ownership`` last). The trainer's loop body is ``optimizer.step()``. Nothing is synchronised. A trailing batch of one row is skipped even without
         ``drop_last``: a training BatchNorm over one row has no variance, and torch refuses it too.
 
-        ``step`` is an ``MLPGradStep``, a ``SymmetricGradStep`` or a ``LocalValueGradStep``. The reference trains LocalValueMLP
+        ``step`` is an ``MLPGradStep``, a ``SymmetricGradStep``, a ``LocalValueGradStep`` or a ``CNNGradStep``. The reference trains LocalValueMLP
         with the player swap at ``p_augment`` 0.5, as PyRatMLP: the defaults here. It trains SymmetricMLP with
-        ``NoAugmentation`` (alpharat/nn/architectures/symmetric/config.py): ``augment=False`` is its setting. Swapped rows stay legal."""
+        ``NoAugmentation`` (alpharat/nn/architectures/symmetric/config.py): ``augment=False`` is its setting. It trains PyRatCNN with
+        ``NoAugmentation`` too (alpharat/nn/architectures/cnn/config.py): ``augment=False`` again. Swapped rows stay legal."""
         windows = batch_windows(len(self), batch_size, drop_last)
         order, mask = epoch_plan(len(self), seed, epoch, shuffle, augment, p_swap)
         rs = self.rowset

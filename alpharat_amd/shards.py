@@ -183,6 +183,45 @@ def lv_param_shapes(width: int, height: int, hidden_dim: int) -> dict:
     return shapes
 
 
+# PyRatCNN's parameters (alpharat/nn/models/cnn/model.py with ResBlocks, MLPPolicyHead and PointValueHead) in torch's
+# named_parameters() order, which is the order of ArCnnTensors (_lib.CNN_TENSORS, whose eight block slots a model of fewer
+# blocks fills from the front); its running statistics in the order of ArCnnBnStats. Both depend on the number of blocks.
+def cnn_param_keys(n_blocks: int) -> tuple:
+    blocks = tuple(f"blocks.{b}.{k}" for b in range(int(n_blocks))
+                   for k in ("bn1.weight", "bn1.bias", "conv1.weight", "bn2.weight", "bn2.bias", "conv2.weight"))
+    return (("stem.weight", "stem_bn.weight", "stem_bn.bias") + blocks
+            + ("player_encoder.0.weight", "player_encoder.0.bias", "combiner.0.weight", "combiner.0.bias",
+               "policy_head.linear.weight", "policy_head.linear.bias", "value_head.linear.weight", "value_head.linear.bias"))
+
+
+def cnn_bn_modules(n_blocks: int) -> tuple:
+    return ("stem_bn",) + tuple(f"blocks.{b}.{bn}" for b in range(int(n_blocks)) for bn in ("bn1", "bn2"))
+
+
+def cnn_running_keys(n_blocks: int) -> tuple:
+    return tuple(f"{bn}.{s}" for bn in cnn_bn_modules(n_blocks) for s in ("running_mean", "running_var"))
+
+
+def cnn_param_shapes(width: int, height: int, dims) -> dict:
+    """The shape of every tensor of ``cnn_param_keys`` and ``cnn_running_keys``; ``dims`` is ``(channels, player_dim,
+    hidden_dim, n_blocks)``."""
+    Ch, PD, HD, B = (int(v) for v in dims)
+    shapes = {"stem.weight": (Ch, 5, 3, 3), "player_encoder.0.weight": (PD, 3), "player_encoder.0.bias": (PD,),
+              "combiner.0.weight": (HD, Ch + PD), "combiner.0.bias": (HD,), "policy_head.linear.weight": (5, 2 * HD),
+              "policy_head.linear.bias": (5,), "value_head.linear.weight": (1, 2 * HD), "value_head.linear.bias": (1,)}
+    for b in range(B):
+        shapes[f"blocks.{b}.conv1.weight"] = shapes[f"blocks.{b}.conv2.weight"] = (Ch, Ch, 3, 3)
+    for k in cnn_param_keys(B) + cnn_running_keys(B):
+        shapes.setdefault(k, (Ch,))
+    return shapes
+
+
+def _cnn_slots(keys: tuple, n_blocks: int, head: int, per_block: int) -> list:
+    """where the tensors of a model of ``n_blocks`` blocks go among the pointers of a struct with eight block slots"""
+    used = head + per_block * n_blocks
+    return list(range(used)) + [head + per_block * _lib.CNN_MAX_BLOCKS + i for i in range(len(keys) - used)]
+
+
 # What a training step is made of, per architecture: the key tuples and shapes that check_grad_tensors holds the caller's
 # tensors to, the two ctypes structs and the symbol that RowSet._grad_into hands them to, and its outputs: their struct,
 # their keys and the number of losses. With a dropout the symbol is this one with "_dropout" behind it.
@@ -193,7 +232,60 @@ _GRAD_STEPS = {
                   "ar_rows_grad_symmetric", _lib.ArTrainOut, TRAIN_OUT_KEYS, 6),
     "local_value": (LV_PARAM_KEYS, MLP_RUNNING_KEYS, lv_param_shapes, _lib.ArLvTensors, _lib.ArMlpBnStats,
                     "ar_rows_grad_local_value", _lib.ArLvTrainOut, LV_TRAIN_OUT_KEYS, 7),
+    # PyRatCNN: where the others have hidden_dim, (channels, player_dim, hidden_dim, n_blocks); its keys depend on n_blocks
+    "pyrat_cnn": (cnn_param_keys, cnn_running_keys, cnn_param_shapes, _lib.ArCnnTensors, _lib.ArCnnBnStats, "ar_rows_grad_cnn",
+                  _lib.ArTrainOut, TRAIN_OUT_KEYS, 6),
 }
+
+
+def _grad_keys(architecture: str, widths) -> tuple:
+    """(param_keys, running_keys) of a step; PyRatCNN's depend on the number of blocks, the last of its widths"""
+    param_keys, running_keys = _GRAD_STEPS[architecture][:2]
+    if callable(param_keys):
+        return param_keys(widths[3]), running_keys(widths[3])
+    return param_keys, running_keys
+
+
+# What RowSet._grad_into leaves to the architecture: check_widths(widths) -> (the widths checked, as the shape function takes
+# them; the entry point's argument for them), and fill_structs(architecture, widths, params, grads, running) -> the two tensor
+# structs and the running statistics' (None without them). The three MLP steps share the first pair.
+def _mlp_widths(hidden_dim) -> tuple:
+    hidden_dim = int(hidden_dim)
+    if hidden_dim <= 0:
+        raise ValueError("hidden_dim must be positive")
+    return hidden_dim, hidden_dim
+
+
+def _flat_structs(architecture: str, widths, params: dict, grads: dict, running) -> tuple:
+    Tensors, BnStats = _GRAD_STEPS[architecture][3:5]
+    param_keys, running_keys = _grad_keys(architecture, widths)
+    return (Tensors(*[params[k].data_ptr() for k in param_keys]), Tensors(*[grads[k].data_ptr() for k in param_keys]),
+            BnStats(*[running[k].data_ptr() for k in running_keys]) if running is not None else None)
+
+
+def _cnn_widths(dims) -> tuple:
+    dims = tuple(int(v) for v in dims)
+    if len(dims) != 4 or min(dims[:3]) <= 0 or not 0 <= dims[3] <= _lib.CNN_MAX_BLOCKS:
+        raise ValueError("dims must be (channels, player_dim, hidden_dim, n_blocks), the first three positive, at most "
+                         f"{_lib.CNN_MAX_BLOCKS} blocks (got {dims})")
+    return dims, C.byref(_lib.ArCnnDims(*dims))
+
+
+def _cnn_structs(architecture: str, dims, params: dict, grads: dict, running) -> tuple:
+    """the tensors of dims[3] blocks at the front of the structs' eight block slots"""
+    B = dims[3]
+    param_keys, running_keys = _grad_keys(architecture, dims)
+    p, g, r = _lib.ArCnnTensors(), _lib.ArCnnTensors(), _lib.ArCnnBnStats() if running is not None else None
+    for slot, k in zip(_cnn_slots(param_keys, B, 3, 6), param_keys):
+        setattr(p, _lib.CNN_TENSORS[slot], params[k].data_ptr())
+        setattr(g, _lib.CNN_TENSORS[slot], grads[k].data_ptr())
+    if r is not None:
+        for slot, k in zip(_cnn_slots(running_keys, B, 2, 4), running_keys):
+            setattr(r, _lib.CNN_STATS[slot], running[k].data_ptr())
+    return p, g, r
+
+
+_GRAD_HOOKS = {"pyrat_cnn": (_cnn_widths, _cnn_structs)}
 
 
 def check_grad_tensors(params: dict, grads: dict, running, out, n: int, width: int, height: int, hidden_dim: int, device,
@@ -206,8 +298,9 @@ def check_grad_tensors(params: dict, grads: dict, running, out, n: int, width: i
 
     if architecture not in _GRAD_STEPS:
         raise ValueError(f"no training step for architecture {architecture!r}")
-    param_keys, running_keys, shapes_of = _GRAD_STEPS[architecture][:3]
+    shapes_of = _GRAD_STEPS[architecture][2]
     out_keys, n_losses = _GRAD_STEPS[architecture][7:9]
+    param_keys, running_keys = _grad_keys(architecture, hidden_dim)  # ("pyrat_cnn": hidden_dim is its four widths)
     shapes = shapes_of(width, height, hidden_dim)
     out_shapes = dict(losses=(n_losses,), logits_p1=(n, 5), logits_p2=(n, 5), value_p1=(n,), value_p2=(n,),
                       ownership_logits=(n, height, width, 4))
@@ -361,29 +454,40 @@ class RowSet:
         self._grad_into("local_value", first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out, stream,
                         (float(ownership_weight),), dropout=dropout)
 
+    def grad_cnn_into(self, first: int, n: int, dims, params: dict, grads: dict, running, policy_weight: float,
+                      value_weight: float, out, stream=None) -> None:
+        """``grad_mlp_into`` for PyRatCNN (``ar_rows_grad_cnn``): ``dims`` is ``(channels, player_dim, hidden_dim,
+        n_blocks)``; ``params`` and ``grads`` are the ``11 + 6 * n_blocks`` tensors under ``cnn_param_keys(n_blocks)``,
+        ``running`` the ``2 + 4 * n_blocks`` of ``cnn_running_keys(n_blocks)`` or ``None``, of the shapes
+        ``cnn_param_shapes(width, height, dims)`` gives. ``channels`` and ``hidden_dim`` are multiples of 32 up to 256,
+        ``player_dim`` is 1 .. 256, at most 8 blocks, a board of 2 to 256 cells and ``n * width * height <= 2**22``.
+        There is no dropout. The workspace holds ``4 * n_blocks + 5`` arrays of ``n * width * height * channels`` floats."""
+        self._grad_into("pyrat_cnn", first, n, dims, params, grads, running, policy_weight, value_weight, out, stream)
+
     def _grad_into(self, architecture: str, first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out,
                    stream, more_weights: tuple = (), dropout=None) -> None:
         import torch
 
-        first, n, hidden_dim = int(first), int(n), int(hidden_dim)
-        if first < 0 or n < 0 or hidden_dim <= 0:
-            raise ValueError("first and n must not be negative, hidden_dim positive")
-        check_grad_tensors(params, grads, running, out, n, self.width, self.height, hidden_dim,
+        first, n = int(first), int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        # the two things that differ by architecture: what the widths are and how the tensors fill the structs
+        check_widths, fill_structs = _GRAD_HOOKS.get(architecture, (_mlp_widths, _flat_structs))
+        widths, widths_arg = check_widths(hidden_dim)
+        check_grad_tensors(params, grads, running, out, n, self.width, self.height, widths,
                            torch.device("cuda", self.device_index), architecture=architecture)
-        param_keys, running_keys, _, Tensors, BnStats, symbol, Out, out_keys, _ = _GRAD_STEPS[architecture]
+        symbol, Out, out_keys = _GRAD_STEPS[architecture][5:8]
         handle = self._handle()
         if stream is None:
             stream = torch.cuda.current_stream(self.device_index)
-        p = Tensors(*[params[k].data_ptr() for k in param_keys])
-        g = Tensors(*[grads[k].data_ptr() for k in param_keys])
-        r = BnStats(*[running[k].data_ptr() for k in running_keys]) if running is not None else None
+        p, g, r = fill_structs(architecture, widths, params, grads, running)
         o = Out(*[out[k].data_ptr() if out.get(k) is not None else None for k in out_keys]) if out is not None else None
         more = ()
         if dropout is not None:
             rate, seed, step = dropout
             d = _lib.ArTrainDropout(float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF)
             symbol, more = symbol + "_dropout", (C.byref(d),)
-        _lib.check(getattr(_lib.load(), symbol)(handle, first, n, hidden_dim, C.byref(p), C.byref(g),
+        _lib.check(getattr(_lib.load(), symbol)(handle, first, n, widths_arg, C.byref(p), C.byref(g),
                                                 C.byref(r) if r is not None else None, float(policy_weight),
                                                 float(value_weight), *more_weights, C.byref(o) if o is not None else None,
                                                 *more, C.c_void_p(stream.cuda_stream)))

@@ -1,4 +1,4 @@
-"""The training step of PyRatMLP, SymmetricMLP or LocalValueMLP over a device-resident ``RowSet``: forward, losses and
+"""The training step of PyRatMLP, SymmetricMLP, LocalValueMLP or PyRatCNN over a device-resident ``RowSet``: forward, losses and
 gradients in one call.
 
 The reference's loop (alpharat/nn/training/loop.py) gathers a batch, runs ``model(obs)`` in training mode,
@@ -15,7 +15,11 @@ Supported: PyRatMLP (``architecture: mlp``, ``MLPGradStep``), SymmetricMLP (``ar
 ``SymmetricGradStep`` over ``ar_rows_grad_symmetric``, alpharat_amd/csrc/train_sym.h) and LocalValueMLP (``architecture:
 local_value``, ``LocalValueGradStep`` over ``ar_rows_grad_local_value``, alpharat_amd/csrc/train_lv.h: the MLP's step plus
 the ownership head and ``ownership_weight`` times its masked cross-entropy, seven losses) -- same loop, same contract -- in
-float32 and a hidden width that is a multiple of 32, at most 256. AMP and the other architectures are not built.
+float32 and a hidden width that is a multiple of 32, at most 256. PyRatCNN (``architecture: cnn``, ``CNNGradStep`` over
+``ar_rows_grad_cnn``, alpharat_amd/csrc/train_cnn.h) as ``CNNModelConfig`` builds it by default: a stem, up to 8
+``ResBlock``s, ``MLPPolicyHead`` and ``PointValueHead``, ``channels`` and ``hidden_dim`` multiples of 32 up to 256,
+``player_dim`` up to 256, boards of 2 to 256 cells, ``n * width * height <= 2**22``; the reference trains it with
+``augment=False``. AMP, KataGoCNN, and for PyRatCNN the gpool block, the pooled value head and dropout are not built.
 
 Dropout is opt-in: without ``dropout_seed`` a model whose ``nn.Dropout`` has ``p != 0`` is refused, as it always was (the
 architectures' default is 0.0; the reference's configs/model/symmetric.yaml sets ``dropout: 0.1``). With
@@ -101,6 +105,10 @@ class _GradStep:
     def _more_outputs(self, rowset: RowSet, n: int, device) -> dict:
         return {}
 
+    def _dims(self):
+        """what the ``RowSet`` method takes for the network's widths: ``hidden_dim``, unless there are more"""
+        return self.hidden_dim
+
     def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
         import torch
 
@@ -117,7 +125,7 @@ class _GradStep:
         # nn.Dropout is the identity in eval mode: no mask then, and the counter stays
         dropping = training and self.dropout_seed is not None and self.dropout_p != 0
         more = dict(dropout=(self.dropout_p, self.dropout_seed, self.dropout_step)) if dropping else {}
-        getattr(rowset, self._ROWSET_METHOD)(first, n, self.hidden_dim, params, self.grads, self.running if training else None,
+        getattr(rowset, self._ROWSET_METHOD)(first, n, self._dims(), params, self.grads, self.running if training else None,
                                              *self._weights(), out, **more)
         for k, p in self.params.items():
             p.grad = self.grads[k]
@@ -234,6 +242,74 @@ class LocalValueGradStep(MLPGradStep):
         ``ownership_weight * loss_ownership``; with ``outputs`` ``(losses, logits_p1, logits_p2, value_p1, value_p2,
         ownership_logits (n, h, w, 4))``, the training-mode outputs."""
         return _GradStep.step(self, rowset, first, n, outputs)
+
+
+class CNNGradStep(_GradStep):
+    """``MLPGradStep`` for PyRatCNN as the reference's ``CNNModelConfig`` builds it by default: ``stem`` and ``stem_bn``,
+    ``ResBlock``s, ``player_encoder``, ``combiner``, ``MLPPolicyHead`` and ``PointValueHead`` (an ``_orig_mod.`` prefix is
+    stripped). ``channels``, ``player_dim``, ``hidden_dim`` and ``n_blocks`` are read from the parameters. ``ValueError``,
+    naming the reason, for a ``GPoolResBlock`` among the blocks (its ``pool_bn`` / ``pool_conv`` / ``pool_linear``), a
+    ``PooledValueHead`` (``value_head.mlp``), a KataGoCNN (``scalar_encoder``), any ``Dropout`` with ``p != 0`` -- with a
+    ``dropout_seed`` too: dropout is not built for this architecture yet --, a missing key, or a parameter or BatchNorm
+    buffer that is not float32 or not contiguous. One persistent gradient tensor per parameter is allocated here."""
+
+    _NAME, _ROWSET_METHOD = "PyRatCNN", "grad_cnn_into"
+
+    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0, dropout_seed: int | None = None) -> None:
+        import re
+
+        import torch
+
+        from .shards import cnn_bn_modules, cnn_param_keys, cnn_running_keys
+
+        for m in model.modules():
+            if isinstance(m, torch.nn.Dropout) and float(m.p) != 0:
+                raise ValueError(f"dropout {float(m.p)} is not supported: dropout is not built for PyRatCNN's step yet, "
+                                 "with a dropout_seed or without")
+        names = [k.removeprefix(_PREFIX) for k, _ in list(model.named_parameters()) + list(model.named_buffers())]
+        n_blocks = 1 + max((int(m.group(1)) for m in (re.match(r"blocks\.(\d+)\.", k) for k in names) if m), default=-1)
+        if n_blocks > 8:
+            raise ValueError(f"the model has {n_blocks} residual blocks: the step takes at most 8")
+        self.n_blocks = n_blocks
+        self._PARAM_KEYS, self._RUNNING_KEYS = cnn_param_keys(n_blocks), cnn_running_keys(n_blocks)
+        self._TRACKED = tuple((f"{bn}.num_batches_tracked", 1) for bn in cnn_bn_modules(n_blocks))
+        super().__init__(model, policy_weight, value_weight, None)
+
+    def _refuse(self, named: dict, buffers: dict) -> None:
+        keys = list(named) + list(buffers)
+        if any(k.startswith("scalar_encoder.") for k in keys):
+            raise ValueError("the model has a scalar_encoder (KataGoCNN): this step is PyRatCNN's")
+        for part in ("pool_bn", "pool_conv", "pool_linear"):
+            if any(k.startswith("blocks.") and f".{part}." in k for k in keys):
+                raise ValueError(f"a block has a {part} (GPoolResBlock): the step is built for ResBlocks only")
+        if any(k.startswith("value_head.mlp.") for k in keys):
+            raise ValueError("the model has a value_head.mlp (PooledValueHead): the step is built for PointValueHead")
+
+    def _read_dims(self) -> None:
+        stem, enc, comb = self.params["stem.weight"], self._weight("player_encoder.0.weight"), self._weight("combiner.0.weight")
+        if stem.dim() != 4 or tuple(stem.shape[1:]) != (5, 3, 3):
+            raise ValueError(f"stem.weight has shape {tuple(stem.shape)}, not (channels, 5, 3, 3)")
+        self.channels, self.player_dim, self.hidden_dim = int(stem.shape[0]), int(enc.shape[0]), int(comb.shape[0])
+
+    def _dims(self):
+        return self.channels, self.player_dim, self.hidden_dim, self.n_blocks
+
+    def _check_board(self, rowset: RowSet) -> None:
+        w, h = getattr(self.model, "width", None), getattr(self.model, "height", None)
+        inner = getattr(self.model, "_orig_mod", None)
+        if w is None and inner is not None:
+            w, h = getattr(inner, "width", None), getattr(inner, "height", None)
+        if w is not None and (int(w), int(h)) != (rowset.width, rowset.height):
+            raise ValueError(f"the model was built for a {w}x{h} board, the row set holds {rowset.width}x{rowset.height}")
+        if rowset.width * rowset.height > 256:
+            raise ValueError(f"a {rowset.width}x{rowset.height} board has more than 256 cells")
+
+    def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
+        """``MLPGradStep.step`` under the same contract: launched on torch's current stream, nothing synchronised, every
+        parameter's ``.grad`` is (again) this object's buffer, overwritten. The batch's statistics are always used; with
+        ``model.training`` the running statistics are updated in place and ``num_batches_tracked`` of every BatchNorm2d
+        grows by one. Returns the ``(6,)`` losses, with ``outputs`` also the four training-mode outputs."""
+        return super().step(rowset, first, n, outputs)
 
 
 def dropout_mask(seed: int, step: int, call: int, n: int, hidden_dim: int, p: float, device_index: int = 0):

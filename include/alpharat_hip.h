@@ -626,6 +626,51 @@ int ar_rows_grad_local_value_dropout(ArRowSet* set, uint64_t first, uint64_t n, 
 int ar_train_dropout_mask(uint64_t seed, uint64_t step, uint32_t call, uint64_t n, uint32_t hidden_dim, float p,
                           uint8_t* keep_device, void* stream);
 
+/* ---- training gradients of PyRatCNN over stored rows (nn/models/cnn/model.py in training mode as CNNModelConfig builds it by
+ * default, the loss of architectures/cnn/loss.py, loss.backward()) ---------------------------------------------------------
+ * ar_rows_grad_mlp for the fourth architecture: the same rows, the same loss (no third term), the same BatchNorm arithmetic
+ * (BatchNorm2d over (N, H, W): R = n*hw values per channel, rv takes var * R / (R - 1)), ArTrainOut, streams, workspace and
+ * refusals. With C = channels, PD = player_dim, HD = hidden_dim, B = n_blocks and hw = h*w:
+ *   in = 5 planes of the flat row (channel d < 4 of a cell is column 4 cell + d, channel 4 is column 6hw + cell)
+ *   x_0 = relu(stem_bn(stem(in))); per block x_b+1 = conv2(relu(bn2(conv1(relu(bn1(x_b)))))) + x_b; every convolution 3x3,
+ *   padding 1, no bias, torch's cross-correlation with the weights in torch's [Cout][Cin][3][3] layout
+ *   f_i = x_B at player i's cell (the 1 of columns [4hw, 5hw) for P1, [5hw, 6hw) for P2); side_i = [score, mud, progress],
+ *   scalars 4, 2, 1 for P1 and 5, 3, 1 for P2; h_i = relu(comb(cat(f_i, relu(enc(side_i))))), agg = h_1 + h_2,
+ *   logits_i = policy(cat(h_i, agg)), value_i = softplus(value(cat(h_i, agg))).
+ * Every BatchNorm module is called once per step. The gradient of a tensor shared by both players is the sum of its two
+ * calls' contributions, P1's before P2's. Not built, and refused by whoever fills these structs from a model
+ * (alpharat_amd/train.py): GPoolResBlock, PooledValueHead, dropout, KataGoCNN. */
+typedef struct ArCnnDims { uint32_t channels, player_dim, hidden_dim, n_blocks; } ArCnnDims;
+typedef struct ArCnnBlock {     /* a ResBlock's parameters in named_parameters() order */
+    float *bn1_w, *bn1_b;       /* [C]          */
+    float* conv1_w;             /* [C][C][3][3] */
+    float *bn2_w, *bn2_b;       /* [C]          */
+    float* conv2_w;             /* [C][C][3][3] */
+} ArCnnBlock;
+typedef struct ArCnnTensors { /* device pointers, f32, C order: PyRatCNN's parameters in named_parameters() order */
+    float* stem_w;              /* [C][5][3][3]        stem               */
+    float *stem_bn_w, *stem_bn_b; /* [C]               stem_bn            */
+    ArCnnBlock blocks[8];       /* the first n_blocks are read            */
+    float *enc_w, *enc_b;       /* [PD][3], [PD]       player_encoder.0   */
+    float *comb_w, *comb_b;     /* [HD][C + PD], [HD]  combiner.0         */
+    float *policy_w, *policy_b; /* [5][2HD], [5]       policy_head.linear */
+    float *value_w, *value_b;   /* [1][2HD], [1]       value_head.linear  */
+} ArCnnTensors;
+typedef struct ArCnnBlockStats { float *bn1_mean, *bn1_var, *bn2_mean, *bn2_var; } ArCnnBlockStats;
+typedef struct ArCnnBnStats { /* running statistics [C], updated in place */
+    float *stem_mean, *stem_var;
+    ArCnnBlockStats blocks[8];
+} ArCnnBnStats;
+/* As ar_rows_grad_mlp in every other respect: `grads` overwritten; running and out may be NULL; launched on `stream` with
+ * no synchronisation; the workspace holds 4 B + 5 activations of n*hw*C floats, about 0.9 GB at n = 4096, 7x7, C = 64,
+ * B = 3. AR_E_INVALID before any launch, nothing written, for ar_rows_grad_mlp's list (here 11 + 6 B tensors
+ * and 2 + 4 B running statistics, those of the first n_blocks blocks) and for: null dims; channels or hidden_dim not a
+ * multiple of 32 or above 256; player_dim outside 1 .. 256; n_blocks above 8; a board of fewer than 2 or more than 256 cells;
+ * n * hw above 2^22. */
+int ar_rows_grad_cnn(ArRowSet* set, uint64_t first, uint64_t n, const ArCnnDims* dims, const ArCnnTensors* params,
+                     const ArCnnTensors* grads, const ArCnnBnStats* running, float policy_weight, float value_weight,
+                     const ArTrainOut* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
