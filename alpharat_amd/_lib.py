@@ -267,6 +267,24 @@ class ArCnnBnStats(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in CNN_STATS]
 
 
+# ar_rows_grad_cnn_gpool: a block's gpool_channels (0: a ResBlock), its five further tensors and pool_bn's two statistics
+CNN_POOL_BLOCK_TENSORS = ("pool_bn_w", "pool_bn_b", "pool_conv_w", "pool_linear_w", "pool_linear_b")
+CNN_POOL_TENSORS = tuple(f"b{b}_{k}" for b in range(CNN_MAX_BLOCKS) for k in CNN_POOL_BLOCK_TENSORS)
+CNN_POOL_STATS = tuple(f"b{b}_{k}" for b in range(CNN_MAX_BLOCKS) for k in ("pool_bn_mean", "pool_bn_var"))
+
+
+class ArCnnPoolDims(C.Structure):
+    _fields_ = [("gpool_channels", C.c_uint32 * CNN_MAX_BLOCKS)]
+
+
+class ArCnnPoolTensors(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in CNN_POOL_TENSORS]
+
+
+class ArCnnPoolStats(C.Structure):  # the eight blocks' ArCnnPoolStats, as flat pointers
+    _fields_ = [(k, C.c_void_p) for k in CNN_POOL_STATS]
+
+
 # every symbol include/alpharat_hip.h declares (checked by the CPU test-suite)
 EXPORTS = {
     "ar_version": (C.c_char_p, []),
@@ -333,6 +351,10 @@ EXPORTS = {
     "ar_rows_grad_cnn": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ArCnnDims), C.POINTER(ArCnnTensors),
                                    C.POINTER(ArCnnTensors), C.POINTER(ArCnnBnStats), C.c_float, C.c_float,
                                    C.POINTER(ArTrainOut), C.c_void_p]),
+    "ar_rows_grad_cnn_gpool": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(ArCnnDims), C.POINTER(ArCnnPoolDims),
+                                         C.POINTER(ArCnnTensors), C.POINTER(ArCnnPoolTensors), C.POINTER(ArCnnTensors),
+                                         C.POINTER(ArCnnPoolTensors), C.POINTER(ArCnnBnStats), C.POINTER(ArCnnPoolStats),
+                                         C.c_float, C.c_float, C.POINTER(ArTrainOut), C.POINTER(ArTrainDropout), C.c_void_p]),
     "ar_train_dropout_mask": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p,
                                         C.c_void_p]),
 }

@@ -41,6 +41,7 @@
 #include "train_sym.h"
 #include "train_lv.h"
 #include "train_cnn.h"
+#include "train_gpool.h"
 #include "host_games.h"
 #include "zig_norm_tables.inc"
 
@@ -3810,12 +3811,18 @@ int rows_grad_symmetric(RowStore& R, uint64_t first, uint64_t n64, uint32_t H, c
     return T.end();
 }
 
-// ar_rows_grad_cnn: the loss and the gradients of PyRatCNN over rows first .. first + n of the order, on the caller's
+// ar_rows_grad_cnn_gpool: the loss and the gradients of PyRatCNN over rows first .. first + n of the order, on the caller's
 // stream: train_cnn.h's chain, under TrainStep's rules. A trunk activation is [R][C] with R = n hw; the heads' arrays hold
-// P1's n rows, then P2's, as in rows_grad_symmetric.
+// P1's n rows, then P2's, as in rows_grad_symmetric. A block b with pd->gpool_channels[b] != 0 is a GPoolResBlock, whose pool
+// path train_gpool.h lists; with `dropout` the four kernels around the player cells are their masked forms. Without either
+// (ar_rows_grad_cnn) the launches and their arguments are train_cnn.h's.
 template <int NW>
 int rows_grad_cnn(RowStore& R, uint64_t first, uint64_t n64, const ArCnnDims& dims, const ArCnnTensors& p, const ArCnnTensors& g,
-                  const ArCnnBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream) {
+                  const ArCnnBnStats* run, float pw, float vw, const ArTrainOut* out, hipStream_t stream,
+                  const ArCnnPoolDims* pd = nullptr, const ArCnnPoolTensors* pp = nullptr, const ArCnnPoolTensors* pg = nullptr,
+                  const ArCnnPoolStats* prun = nullptr, const ArTrainDropout* dropout = nullptr) {
+    static_assert(sizeof(ArCnnPoolTensors) == 40 * sizeof(float*) && sizeof(ArCnnPoolBlock) == 5 * sizeof(float*), "8 * 5 pointers");
+    static_assert(sizeof(ArCnnPoolStats) == 2 * sizeof(float*), "2 pointers a block");
     static_assert(sizeof(ArCnnTensors) == 59 * sizeof(float*) && sizeof(ArCnnBlock) == 6 * sizeof(float*), "3 + 8 * 6 + 8 pointers");
     static_assert(sizeof(ArCnnBnStats) == 34 * sizeof(float*), "2 + 8 * 4 pointers");
     const uint32_t Cu = dims.channels, PDu = dims.player_dim, HDu = dims.hidden_dim, Bu = dims.n_blocks;
@@ -3827,6 +3834,22 @@ int rows_grad_cnn(RowStore& R, uint64_t first, uint64_t n64, const ArCnnDims& di
         return fail(AR_E_INVALID, "boards of 2 to 256 cells (this one has " + std::to_string(R.hw) + ")");
     if (n64 <= (uint64_t)TRAIN_MAX_ROWS && n64 * R.hw > (uint64_t)CNN_MAX_TRUNK_ROWS)  // (more rows than that: check's refusal)
         return fail(AR_E_INVALID, "n * h * w is " + std::to_string(n64 * R.hw) + ": at most 2^22 trunk rows a step");
+    // the gpool blocks among the first n_blocks: Gs[b] = gpool_channels, 0 for a ResBlock
+    int Gs[CNN_MAX_BLOCKS_TRAIN] = {}, n_pool = 0, Gmax = 0;
+    for (uint32_t b = 0; pd && b < Bu; ++b) {
+        const uint32_t Gu = pd->gpool_channels[b];
+        if (Gu > (uint32_t)CNN_MAX_GPOOL)
+            return fail(AR_E_INVALID, "gpool_channels must be at most 256 (block " + std::to_string(b) + " has " + std::to_string(Gu) + ")");
+        if (Gu == 0) continue;
+        if (!pp || !pg) return fail(AR_E_INVALID, "null tensor: the pool tensors of block " + std::to_string(b));
+        if (run && !prun) return fail(AR_E_INVALID, "null running statistic: pool_bn of block " + std::to_string(b));
+        Gs[b] = (int)Gu;
+        Gmax = std::max(Gmax, (int)Gu);
+        ++n_pool;
+    }
+    // (the products over the trunk rows put their row tiles on blockIdx.y)
+    if (n_pool && n64 <= (uint64_t)TRAIN_MAX_ROWS && n64 * R.hw > (uint64_t)65535 * TG_TILE)
+        return fail(AR_E_INVALID, "n * h * w is " + std::to_string(n64 * R.hw) + ": at most 65535 * 64 trunk rows with a gpool block");
     // the tensors that B blocks use, under their names
     std::vector<std::string> names = {"stem_w", "stem_bn_w", "stem_bn_b"};
     std::vector<float*> ps = {p.stem_w, p.stem_bn_w, p.stem_bn_b}, gs = {g.stem_w, g.stem_bn_w, g.stem_bn_b}, rs;
@@ -3845,6 +3868,18 @@ int rows_grad_cnn(RowStore& R, uint64_t first, uint64_t n64, const ArCnnDims& di
             const ArCnnBlockStats& rb = run->blocks[b];
             rs.insert(rs.end(), {rb.bn1_mean, rb.bn1_var, rb.bn2_mean, rb.bn2_var});
         }
+        if (Gs[b]) {
+            static const char* const kPool[5] = {"pool_bn_w", "pool_bn_b", "pool_conv_w", "pool_linear_w", "pool_linear_b"};
+            const ArCnnPoolBlock &qb = pp->blocks[b], &hb = pg->blocks[b];
+            float* const pk[5] = {qb.pool_bn_w, qb.pool_bn_b, qb.pool_conv_w, qb.pool_linear_w, qb.pool_linear_b};
+            float* const gk[5] = {hb.pool_bn_w, hb.pool_bn_b, hb.pool_conv_w, hb.pool_linear_w, hb.pool_linear_b};
+            for (int k = 0; k < 5; ++k) {
+                names.push_back("blocks[" + std::to_string(b) + "]." + kPool[k]);
+                ps.push_back(pk[k]);
+                gs.push_back(gk[k]);
+            }
+            if (run) rs.insert(rs.end(), {prun[b].pool_bn_mean, prun[b].pool_bn_var});
+        }
     }
     {
         static const char* const kTail[8] = {"enc_w", "enc_b", "comb_w", "comb_b", "policy_w", "policy_b", "value_w", "value_b"};
@@ -3861,12 +3896,14 @@ int rows_grad_cnn(RowStore& R, uint64_t first, uint64_t n64, const ArCnnDims& di
     TrainStep T{R, stream};
     if (int rc = T.check(first, n64, HDu, name_ptrs.data(), ps.data(), gs.data(), (int)ps.size(), rs.data(), (int)rs.size(), out))
         return rc;
+    if (int rc = T.check_dropout(dropout)) return rc;
     const int n = T.n, n2 = 2 * n, hw = (int)R.hw, C = (int)Cu, PD = (int)PDu, HD = (int)HDu, B = (int)Bu, W = C + PD;
     const int Rr = n * hw;
     const TrainCols tcR = cnn_cols(n, hw, C);
     TrainCols tc1 = tcR;  // what the column kernels see once the parts are collapsed: the same rows per part, one row of totals
     tc1.P = 1;
-    const TrainSplit spR = cnn_split(n, hw), sp2 = train_split(n2);
+    const TrainSplit spR = cnn_split(n, hw), sp2 = train_split(n2), spN = train_split(n);
+    const int n_calls = 2 * B + 1 + (n_pool ? B : 0);  // pool_bn of block b is BatchNorm call 2 B + 1 + b
     const size_t act = (size_t)Rr * C * 4;
     T.take_rows();
     const size_t o_x5 = T.take((size_t)Rr * 5 * 4), o_side = T.take((size_t)n2 * 3 * 4), o_cells = T.take((size_t)n2 * 4),
@@ -3875,10 +3912,28 @@ int rows_grad_cnn(RowStore& R, uint64_t first, uint64_t n64, const ArCnnDims& di
                  o_zc = T.take((size_t)n2 * HD * 4), o_h = T.take((size_t)n2 * HD * 4), o_d12 = T.take((size_t)n2 * 48),
                  o_dzc = T.take((size_t)n2 * HD * 4), o_dcat = T.take((size_t)n2 * W * 4), o_dze = T.take((size_t)n2 * PD * 4),
                  o_parts = T.take((size_t)2 * CNN_MAX_PARTS * C * 8), o_tot = T.take((size_t)2 * C * 8),
-                 o_mean = T.take((size_t)(2 * B + 1) * C * 8), o_rstd = T.take((size_t)(2 * B + 1) * C * 4),
-                 o_wpart = T.take(std::max((size_t)spR.S * C * 9 * C, (size_t)sp2.S * std::max(HD * W, 12 * HD)) * 4),
-                 o_bpart = T.take((size_t)sp2.S * 256 * 4), o_scr = T.take((size_t)256 * 4);
+                 o_mean = T.take((size_t)n_calls * C * 8), o_rstd = T.take((size_t)n_calls * C * 4),
+                 o_wpart = T.take(std::max({(size_t)spR.S * C * 9 * C, (size_t)sp2.S * std::max(HD * W, 12 * HD),
+                                            n_pool ? (size_t)spN.S * C * 2 * Gmax : (size_t)0}) * 4),
+                 o_bpart = T.take((size_t)(n_pool ? std::max({sp2.S, spN.S, spR.S}) : sp2.S) * 256 * 4), o_scr = T.take((size_t)256 * 4);
     T.take_losses();
+    // what the gpool blocks add: per block ap, pz, pool_cat and the tie counts; once c2 / the third gradient array, po, dpo,
+    // dcat and dpz
+    size_t o_ap[CNN_MAX_BLOCKS_TRAIN] = {}, o_pz[CNN_MAX_BLOCKS_TRAIN] = {}, o_pcat[CNN_MAX_BLOCKS_TRAIN] = {},
+           o_pcnt[CNN_MAX_BLOCKS_TRAIN] = {}, o_pe = 0, o_po = 0, o_dpcat = 0, o_dpz = 0;
+    if (n_pool) {
+        for (int b = 0; b < B; ++b)
+            if (Gs[b]) {
+                o_ap[b] = T.take(act);
+                o_pz[b] = T.take((size_t)Rr * Gs[b] * 4);
+                o_pcat[b] = T.take((size_t)n * 2 * Gs[b] * 4);
+                o_pcnt[b] = T.take((size_t)n * Gs[b] * 4);
+            }
+        o_pe = T.take(act);
+        o_po = T.take((size_t)n * C * 4);
+        o_dpcat = T.take((size_t)n * 2 * Gmax * 4);
+        o_dpz = T.take((size_t)Rr * Gmax * 4);
+    }
     if (int rc = T.begin()) return rc;
     float *X5 = T.f(o_x5), *Side = T.f(o_side), *Zs = T.f(o_zs), *G = T.f(o_g), *Dd = T.f(o_d), *E = T.f(o_e), *Ze = T.f(o_ze),
           *Cat = T.f(o_cat), *Zc = T.f(o_zc), *Hh = T.f(o_h), *D12 = T.f(o_d12), *dZc = T.f(o_dzc), *dCat = T.f(o_dcat),
@@ -3978,19 +4033,51 @@ int rows_grad_cnn(RowStore& R, uint64_t first, uint64_t n64, const ArCnnDims& di
         conv(blk(b, 0), C, q.conv1_w, nullptr, blk(b, 1));
         bn_forward(2 + 2 * b, blk(b, 1), q.bn2_w, q.bn2_b, blk(b, 2), run ? run->blocks[b].bn2_mean : nullptr,
                    run ? run->blocks[b].bn2_var : nullptr);
-        conv(blk(b, 2), C, q.conv2_w, xs(b), xs(b + 1));
+        if (!Gs[b]) {
+            conv(blk(b, 2), C, q.conv2_w, xs(b), xs(b + 1));
+            continue;
+        }
+        // a gpool block: conv2 without the skip, the pool path, and the three terms joined in torch's order
+        const int Gp = Gs[b];
+        const ArCnnPoolBlock& qp = pp->blocks[b];
+        float *Pe = T.f(o_pe), *Ap = T.f(o_ap[b]), *Pz = T.f(o_pz[b]), *Pcat = T.f(o_pcat[b]), *Po = T.f(o_po);
+        conv(blk(b, 2), C, q.conv2_w, nullptr, Pe);
+        bn_forward(2 * B + 1 + b, xs(b), qp.pool_bn_w, qp.pool_bn_b, Ap, run ? prun[b].pool_bn_mean : nullptr,
+                   run ? prun[b].pool_bn_var : nullptr);
+        T.gemm(Ap, C, 1, 1, qp.pool_conv_w, 1, C, 1, Pz, Rr, Gp, C, nullptr, 1, C, nullptr);
+        if (T.ok()) {
+            hipLaunchKernelGGL(k_gpool_reduce, TrainStep::blocks((size_t)n * Gp), dim3(256), 0, stream, (const float*)Pz, Pcat,
+                               (int*)(T.ws + o_pcnt[b]), n, hw, Gp);
+            T.launched();
+        }
+        T.gemm(Pcat, 2 * Gp, 1, 1, qp.pool_linear_w, 1, 2 * Gp, 1, Po, n, C, 2 * Gp, qp.pool_linear_b, 1, 2 * Gp, nullptr);
+        if (T.ok()) {
+            const size_t c4 = (size_t)Rr * C / 4;
+            hipLaunchKernelGGL(k_gpool_join, TrainStep::blocks(c4), dim3(256), 0, stream, (const float4*)Pe, (const float*)Po,
+                               (const float4*)xs(b), (float4*)xs(b + 1), c4, hw, C);
+            T.launched();
+        }
     }
     // the player cells and the heads
+    const TrainDrop dr_e1 = T.drop_of(0), dr_e2 = T.drop_of(1), dr_c1 = T.drop_of(2), dr_c2 = T.drop_of(3);
     T.gemm(Side, 3, 1, 1, p.enc_w, 1, 3, 1, Ze, n2, PD, 3, p.enc_b, 1, 3, nullptr);
     if (T.ok()) {
-        hipLaunchKernelGGL(k_cnn_gather, TrainStep::blocks((size_t)n2 * W), dim3(256), 0, stream, (const float*)xs(B), (const int*)cells,
-                           (const float*)Ze, Cat, n, hw, C, PD);
+        if (T.dropping)
+            hipLaunchKernelGGL(k_cnn_gather_drop, TrainStep::blocks((size_t)n2 * W), dim3(256), 0, stream, (const float*)xs(B),
+                               (const int*)cells, (const float*)Ze, Cat, n, hw, C, PD, dr_e1, dr_e2);
+        else
+            hipLaunchKernelGGL(k_cnn_gather, TrainStep::blocks((size_t)n2 * W), dim3(256), 0, stream, (const float*)xs(B), (const int*)cells,
+                               (const float*)Ze, Cat, n, hw, C, PD);
         T.launched();
     }
     T.gemm(Cat, W, 1, 1, p.comb_w, 1, W, 1, Zc, n2, HD, W, p.comb_b, 1, W, nullptr);
     if (T.ok()) {
         const size_t c4 = (size_t)n2 * HD / 4;
-        hipLaunchKernelGGL(k_train_lv_relu, TrainStep::blocks(c4), dim3(256), 0, stream, (const float4*)Zc, (float4*)Hh, c4);
+        if (T.dropping)
+            hipLaunchKernelGGL(k_cnn_relu_drop, TrainStep::blocks((size_t)n2 * HD), dim3(256), 0, stream, (const float*)Zc, Hh, n, HD,
+                               dr_c1, dr_c2);
+        else
+            hipLaunchKernelGGL(k_train_lv_relu, TrainStep::blocks(c4), dim3(256), 0, stream, (const float4*)Zc, (float4*)Hh, c4);
         SymHeads t;
         t.h = Hh;
         t.w_p = p.policy_w, t.b_p = p.policy_b, t.w_v = p.value_w, t.b_v = p.value_b;
@@ -4013,15 +4100,23 @@ int rows_grad_cnn(RowStore& R, uint64_t first, uint64_t n64, const ArCnnDims& di
     if (T.ok()) {
         hipLaunchKernelGGL(k_sym_head_reduce, TrainStep::blocks((size_t)12 * HD + 6), dim3(256), 0, stream, (const float*)T.wpart,
                            (const float*)T.bpart, sp2.S, HD, g.policy_w, g.policy_b, g.value_w, g.value_b);
-        hipLaunchKernelGGL(k_cnn_dhead, TrainStep::blocks((size_t)n2 * HD), dim3(256), 0, stream, (const float*)D12, (const float*)p.policy_w,
-                           (const float*)p.value_w, (const float*)Hh, dZc, n2, HD);
+        if (T.dropping)
+            hipLaunchKernelGGL(k_cnn_dhead_drop, TrainStep::blocks((size_t)n2 * HD), dim3(256), 0, stream, (const float*)D12,
+                               (const float*)p.policy_w, (const float*)p.value_w, (const float*)Hh, dZc, n2, HD, dr_c1.scale);
+        else
+            hipLaunchKernelGGL(k_cnn_dhead, TrainStep::blocks((size_t)n2 * HD), dim3(256), 0, stream, (const float*)D12,
+                               (const float*)p.policy_w, (const float*)p.value_w, (const float*)Hh, dZc, n2, HD);
         T.launched();
     }
     T.grad_w(dZc, HD, Cat, W, n2, sp2, {g.comb_w, g.comb_b, HD});
     T.grad_in(dZc, n2, p.comb_w, W, dCat, HD);
     if (T.ok()) {
-        hipLaunchKernelGGL(k_cnn_enc_bwd, TrainStep::blocks((size_t)n2 * PD), dim3(256), 0, stream, (const float*)dCat, (const float*)Ze, dZe,
-                           n2, C, PD);
+        if (T.dropping)
+            hipLaunchKernelGGL(k_cnn_enc_bwd_drop, TrainStep::blocks((size_t)n2 * PD), dim3(256), 0, stream, (const float*)dCat,
+                               (const float*)Cat, dZe, n2, C, PD, dr_e1.scale);
+        else
+            hipLaunchKernelGGL(k_cnn_enc_bwd, TrainStep::blocks((size_t)n2 * PD), dim3(256), 0, stream, (const float*)dCat,
+                               (const float*)Ze, dZe, n2, C, PD);
         T.launched();
     }
     T.grad_w(dZe, PD, Side, 3, n2, sp2, {g.enc_w, g.enc_b, PD});
@@ -4039,9 +4134,37 @@ int rows_grad_cnn(RowStore& R, uint64_t first, uint64_t n64, const ArCnnDims& di
         conv_dw(Dd, blk(b, 0), C, gq.conv1_w);
         conv_din(Dd, q.conv1_w, E);
         bn_backward(1 + 2 * b, xs(b), blk(b, 0), E, q.bn1_w, gq.bn1_w, gq.bn1_b);
+        float* Pe = nullptr;
+        if (Gs[b]) {  // the pool path, from the same G = d x_b+1, into Pe
+            const int Gp = Gs[b];
+            const ArCnnPoolBlock &qp = pp->blocks[b], &gp = pg->blocks[b];
+            float *Ap = T.f(o_ap[b]), *Pz = T.f(o_pz[b]), *Pcat = T.f(o_pcat[b]), *dPo = T.f(o_po), *dPcat = T.f(o_dpcat),
+                  *dPz = T.f(o_dpz);
+            Pe = T.f(o_pe);
+            if (T.ok()) {
+                hipLaunchKernelGGL(k_gpool_rowsum, TrainStep::blocks((size_t)n * C), dim3(256), 0, stream, (const float*)G, dPo, n, hw, C);
+                T.launched();
+            }
+            T.grad_w(dPo, C, Pcat, 2 * Gp, n, spN, {gp.pool_linear_w, gp.pool_linear_b, C});
+            T.grad_in(dPo, n, qp.pool_linear_w, 2 * Gp, dPcat, C);
+            if (T.ok()) {
+                hipLaunchKernelGGL(k_gpool_dpz, TrainStep::blocks((size_t)Rr * Gp), dim3(256), 0, stream, (const float*)Pz,
+                                   (const float*)Pcat, (const int*)(T.ws + o_pcnt[b]), (const float*)dPcat, dPz, n, hw, Gp);
+                T.launched();
+            }
+            // over cnn_split's ranges of the trunk rows, as CV_DW (no bias: the column sums go to the scratch row)
+            T.grad_w(dPz, Gp, Ap, C, Rr, spR, {gp.pool_conv_w, scr, Gp});
+            T.grad_in(dPz, Rr, qp.pool_conv_w, C, Pe, Gp);
+            bn_backward(2 * B + 1 + b, xs(b), Ap, Pe, qp.pool_bn_w, gp.pool_bn_w, gp.pool_bn_b);
+        }
         if (T.ok()) {
             const size_t c4 = (size_t)Rr * C / 4;
             hipLaunchKernelGGL(k_cnn_add, TrainStep::blocks(c4), dim3(256), 0, stream, (float4*)G, (const float4*)E, c4);
+            T.launched();
+        }
+        if (Pe && T.ok()) {
+            const size_t c4 = (size_t)Rr * C / 4;
+            hipLaunchKernelGGL(k_cnn_add, TrainStep::blocks(c4), dim3(256), 0, stream, (float4*)G, (const float4*)Pe, c4);
             T.launched();
         }
     }
@@ -5641,14 +5764,23 @@ int ar_rows_grad_symmetric(ArRowSet* s, uint64_t first, uint64_t n, uint32_t hid
                                           nullptr, stream);
 }
 
+int ar_rows_grad_cnn_gpool(ArRowSet* s, uint64_t first, uint64_t n, const ArCnnDims* dims, const ArCnnPoolDims* pool_dims,
+                           const ArCnnTensors* params, const ArCnnPoolTensors* pool_params, const ArCnnTensors* grads,
+                           const ArCnnPoolTensors* pool_grads, const ArCnnBnStats* running, const ArCnnPoolStats* pool_running,
+                           float policy_weight, float value_weight, const ArTrainOut* out, const ArTrainDropout* dropout,
+                           void* stream) {
+    if (!s || !s->impl || !dims || !params || !grads) return fail(AR_E_INVALID, "null argument");
+    return s->impl->nw == 1 ? rows_grad_cnn<1>(*s->impl, first, n, *dims, *params, *grads, running, policy_weight, value_weight, out,
+                                               (hipStream_t)stream, pool_dims, pool_params, pool_grads, pool_running, dropout)
+                            : rows_grad_cnn<4>(*s->impl, first, n, *dims, *params, *grads, running, policy_weight, value_weight, out,
+                                               (hipStream_t)stream, pool_dims, pool_params, pool_grads, pool_running, dropout);
+}
+
 int ar_rows_grad_cnn(ArRowSet* s, uint64_t first, uint64_t n, const ArCnnDims* dims, const ArCnnTensors* params,
                      const ArCnnTensors* grads, const ArCnnBnStats* running, float policy_weight, float value_weight,
                      const ArTrainOut* out, void* stream) {
-    if (!s || !s->impl || !dims || !params || !grads) return fail(AR_E_INVALID, "null argument");
-    return s->impl->nw == 1 ? rows_grad_cnn<1>(*s->impl, first, n, *dims, *params, *grads, running, policy_weight, value_weight, out,
-                                               (hipStream_t)stream)
-                            : rows_grad_cnn<4>(*s->impl, first, n, *dims, *params, *grads, running, policy_weight, value_weight, out,
-                                               (hipStream_t)stream);
+    return ar_rows_grad_cnn_gpool(s, first, n, dims, nullptr, params, nullptr, grads, nullptr, running, nullptr, policy_weight,
+                                  value_weight, out, nullptr, stream);
 }
 
 int ar_train_dropout_mask(uint64_t seed, uint64_t step, uint32_t call, uint64_t n, uint32_t hidden_dim, float p,

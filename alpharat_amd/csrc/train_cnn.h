@@ -35,6 +35,8 @@
 //    per block b, downwards:      conv dW (conv2), conv^T, bn' (bn2), conv dW (conv1), conv^T, bn' (bn1),
 //                                 k_cnn_add (g = g + that)                                                        13
 //    bn' (stem_bn), conv dW (stem)                                                                                 5
+// (A GPoolResBlock's pool path and the dropout behind the two ReLUs of the heads are train_gpool.h, over ar_rows_grad_cnn_gpool:
+// the chain above is that function's with no gpool block and no dropout.)
 // 29 + 25 B launches: 104 at B = 3. Fusing the column sums into the convolution's epilogue and the BatchNorm into its
 // operand fetch would take most of the "bn" launches and a read and a write of [R][C] each out of the chain.
 //

@@ -24,7 +24,7 @@ from typing import Iterator
 import numpy as np
 
 from .shards import KEYS, RowSet, row_shapes
-from .train import CNNGradStep, LocalValueGradStep, MLPGradStep, SymmetricGradStep  # noqa: F401  (exported beside RowDataset)
+from .train import CNNGradStep, GPoolCNNGradStep, LocalValueGradStep, MLPGradStep, SymmetricGradStep  # noqa: F401  (exported beside RowDataset)
 
 
 def epoch_plan(n: int, seed: int, epoch: int, shuffle: bool = True, augment: bool = True,
@@ -145,7 +145,7 @@ class RowDataset:
         ``LocalValueGradStep``, ``loss_ownership`` last). The trainer's loop body is ``optimizer.step()``. Nothing is synchronised. A trailing batch of one row is skipped even without
         ``drop_last``: a training BatchNorm over one row has no variance, and torch refuses it too.
 
-        ``step`` is an ``MLPGradStep``, a ``SymmetricGradStep``, a ``LocalValueGradStep`` or a ``CNNGradStep``. The reference trains LocalValueMLP
+        ``step`` is an ``MLPGradStep``, a ``SymmetricGradStep``, a ``LocalValueGradStep``, a ``CNNGradStep`` or a ``GPoolCNNGradStep``. The reference trains LocalValueMLP
         with the player swap at ``p_augment`` 0.5, as PyRatMLP: the defaults here. It trains SymmetricMLP with
         ``NoAugmentation`` (alpharat/nn/architectures/symmetric/config.py): ``augment=False`` is its setting. It trains PyRatCNN with
         ``NoAugmentation`` too (alpharat/nn/architectures/cnn/config.py): ``augment=False`` again. Swapped rows stay legal."""

@@ -216,6 +216,51 @@ def cnn_param_shapes(width: int, height: int, dims) -> dict:
     return shapes
 
 
+# PyRatCNN with GPoolResBlocks among its blocks (ar_rows_grad_cnn_gpool). ``blocks`` is a tuple of gpool_channels, one per
+# block, 0 for a ResBlock: a gpool block has five parameters and one BatchNorm module more, behind the ResBlock's own, in
+# torch's named_parameters() order.
+_CNN_BLOCK_KEYS = ("bn1.weight", "bn1.bias", "conv1.weight", "bn2.weight", "bn2.bias", "conv2.weight")
+CNN_POOL_KEYS = ("pool_bn.weight", "pool_bn.bias", "pool_conv.weight", "pool_linear.weight", "pool_linear.bias")
+
+
+def _gpool_blocks(blocks) -> tuple:
+    blocks = tuple(int(g) for g in blocks)
+    if len(blocks) > _lib.CNN_MAX_BLOCKS or any(g < 0 for g in blocks):
+        raise ValueError(f"blocks must be at most {_lib.CNN_MAX_BLOCKS} gpool_channels, 0 for a ResBlock (got {blocks})")
+    return blocks
+
+
+def cnn_gpool_param_keys(blocks) -> tuple:
+    blocks = _gpool_blocks(blocks)
+    plain = cnn_param_keys(0)
+    return (plain[:3] + tuple(f"blocks.{b}.{k}" for b, g in enumerate(blocks) for k in _CNN_BLOCK_KEYS + (CNN_POOL_KEYS if g else ()))
+            + plain[3:])
+
+
+def cnn_gpool_bn_modules(blocks) -> tuple:
+    return ("stem_bn",) + tuple(f"blocks.{b}.{bn}" for b, g in enumerate(_gpool_blocks(blocks))
+                                for bn in ("bn1", "bn2") + (("pool_bn",) if g else ()))
+
+
+def cnn_gpool_running_keys(blocks) -> tuple:
+    return tuple(f"{bn}.{s}" for bn in cnn_gpool_bn_modules(blocks) for s in ("running_mean", "running_var"))
+
+
+def cnn_gpool_param_shapes(width: int, height: int, dims) -> dict:
+    """The shape of every tensor of ``cnn_gpool_param_keys`` and ``cnn_gpool_running_keys``; ``dims`` is ``(channels,
+    player_dim, hidden_dim, blocks)``."""
+    Ch, PD, HD = (int(v) for v in dims[:3])
+    blocks = _gpool_blocks(dims[3])
+    shapes = cnn_param_shapes(width, height, (Ch, PD, HD, len(blocks)))
+    for b, g in enumerate(blocks):
+        if g:
+            shapes[f"blocks.{b}.pool_conv.weight"] = (g, Ch, 1, 1)
+            shapes[f"blocks.{b}.pool_linear.weight"] = (Ch, 2 * g)
+    for k in cnn_gpool_param_keys(blocks) + cnn_gpool_running_keys(blocks):
+        shapes.setdefault(k, (Ch,))
+    return shapes
+
+
 def _cnn_slots(keys: tuple, n_blocks: int, head: int, per_block: int) -> list:
     """where the tensors of a model of ``n_blocks`` blocks go among the pointers of a struct with eight block slots"""
     used = head + per_block * n_blocks
@@ -235,11 +280,16 @@ _GRAD_STEPS = {
     # PyRatCNN: where the others have hidden_dim, (channels, player_dim, hidden_dim, n_blocks); its keys depend on n_blocks
     "pyrat_cnn": (cnn_param_keys, cnn_running_keys, cnn_param_shapes, _lib.ArCnnTensors, _lib.ArCnnBnStats, "ar_rows_grad_cnn",
                   _lib.ArTrainOut, TRAIN_OUT_KEYS, 6),
+    # ... with gpool blocks: (channels, player_dim, hidden_dim, blocks), the keys depend on the tuple ``blocks``; its pool
+    # tensors travel in structs of their own (RowSet.grad_cnn_gpool_into)
+    "pyrat_cnn_gpool": (cnn_gpool_param_keys, cnn_gpool_running_keys, cnn_gpool_param_shapes, _lib.ArCnnTensors, _lib.ArCnnBnStats,
+                        "ar_rows_grad_cnn_gpool", _lib.ArTrainOut, TRAIN_OUT_KEYS, 6),
 }
 
 
 def _grad_keys(architecture: str, widths) -> tuple:
-    """(param_keys, running_keys) of a step; PyRatCNN's depend on the number of blocks, the last of its widths"""
+    """(param_keys, running_keys) of a step; PyRatCNN's depend on the number of blocks (with gpool blocks: on the tuple of
+    their widths), the last of its widths"""
     param_keys, running_keys = _GRAD_STEPS[architecture][:2]
     if callable(param_keys):
         return param_keys(widths[3]), running_keys(widths[3])
@@ -283,6 +333,34 @@ def _cnn_structs(architecture: str, dims, params: dict, grads: dict, running) ->
         for slot, k in zip(_cnn_slots(running_keys, B, 2, 4), running_keys):
             setattr(r, _lib.CNN_STATS[slot], running[k].data_ptr())
     return p, g, r
+
+
+def _cnn_gpool_structs(dims, blocks, params: dict, grads: dict, running) -> tuple:
+    """(params, grads, pool params, pool grads, running, pool running) of ar_rows_grad_cnn_gpool: the ResBlock tensors where
+    ``_cnn_structs`` puts them, a gpool block's five further tensors and two statistics in block b's slots of the pool structs"""
+    B = dims[3]
+    plain = {k: i for i, k in enumerate(cnn_param_keys(B))}
+    plain_run = {k: i for i, k in enumerate(cnn_running_keys(B))}
+    slots, run_slots = _cnn_slots(tuple(plain), B, 3, 6), _cnn_slots(tuple(plain_run), B, 2, 4)
+    p, g, pp, pg = _lib.ArCnnTensors(), _lib.ArCnnTensors(), _lib.ArCnnPoolTensors(), _lib.ArCnnPoolTensors()
+    for k in cnn_gpool_param_keys(blocks):
+        if k in plain:
+            field, a, b = _lib.CNN_TENSORS[slots[plain[k]]], p, g
+        else:  # blocks.<b>.pool_*
+            _, blk, mod, leaf = k.split(".")
+            field, a, b = f"b{blk}_{mod}_{'w' if leaf == 'weight' else 'b'}", pp, pg
+        setattr(a, field, params[k].data_ptr())
+        setattr(b, field, grads[k].data_ptr())
+    r = pr = None
+    if running is not None:
+        r, pr = _lib.ArCnnBnStats(), _lib.ArCnnPoolStats()
+        for k in cnn_gpool_running_keys(blocks):
+            if k in plain_run:
+                setattr(r, _lib.CNN_STATS[run_slots[plain_run[k]]], running[k].data_ptr())
+            else:
+                _, blk, _, leaf = k.split(".")
+                setattr(pr, f"b{blk}_pool_bn_{'mean' if leaf == 'running_mean' else 'var'}", running[k].data_ptr())
+    return p, g, pp, pg, r, pr
 
 
 _GRAD_HOOKS = {"pyrat_cnn": (_cnn_widths, _cnn_structs)}
@@ -463,6 +541,46 @@ class RowSet:
         ``player_dim`` is 1 .. 256, at most 8 blocks, a board of 2 to 256 cells and ``n * width * height <= 2**22``.
         There is no dropout. The workspace holds ``4 * n_blocks + 5`` arrays of ``n * width * height * channels`` floats."""
         self._grad_into("pyrat_cnn", first, n, dims, params, grads, running, policy_weight, value_weight, out, stream)
+
+    def grad_cnn_gpool_into(self, first: int, n: int, dims, blocks, params: dict, grads: dict, running, policy_weight: float,
+                            value_weight: float, out, stream=None, dropout=None) -> None:
+        """``grad_cnn_into`` for a PyRatCNN whose trunk mixes ``ResBlock`` and ``GPoolResBlock`` (``ar_rows_grad_cnn_gpool``).
+        ``dims`` is ``(channels, player_dim, hidden_dim, n_blocks)`` and ``blocks`` the ``n_blocks`` ``gpool_channels``, 0 for
+        a ``ResBlock`` and 1 .. 256 for a ``GPoolResBlock``; ``params`` and ``grads`` are the tensors under
+        ``cnn_gpool_param_keys(blocks)`` (11 a gpool block, 6 a res block), ``running`` those of
+        ``cnn_gpool_running_keys(blocks)`` or ``None``, of the shapes ``cnn_gpool_param_shapes`` gives. ``dropout``: ``None``
+        or ``(p, seed, step)``, applied behind the ReLU of ``player_encoder`` (calls 0, 1: P1's, P2's rows) and of ``combiner``
+        (calls 2, 3) from the library's own mask generator, as ``grad_mlp_into`` describes. Per gpool block the workspace
+        grows by ``n * width * height * (channels + gpool_channels)`` floats. Everything else, the checks included, as
+        ``grad_cnn_into``."""
+        import torch
+
+        first, n = int(first), int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must not be negative")
+        dims, dims_arg = _cnn_widths(dims)
+        blocks = _gpool_blocks(blocks)
+        if len(blocks) != dims[3]:
+            raise ValueError(f"blocks has {len(blocks)} entries, dims names {dims[3]} blocks")
+        if max(blocks, default=0) > 256:
+            raise ValueError(f"gpool_channels must be at most 256 (got {blocks})")
+        check_grad_tensors(params, grads, running, out, n, self.width, self.height, dims[:3] + (blocks,),
+                           torch.device("cuda", self.device_index), architecture="pyrat_cnn_gpool")
+        handle = self._handle()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device_index)
+        p, g, pp, pg, r, pr = _cnn_gpool_structs(dims, blocks, params, grads, running)
+        o = _lib.ArTrainOut(*[out[k].data_ptr() if out.get(k) is not None else None for k in TRAIN_OUT_KEYS]) if out is not None else None
+        d = None
+        if dropout is not None:
+            rate, seed, step = dropout
+            d = _lib.ArTrainDropout(float(rate), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF)
+        pool_dims = _lib.ArCnnPoolDims((C.c_uint32 * _lib.CNN_MAX_BLOCKS)(*blocks))
+        _lib.check(_lib.load().ar_rows_grad_cnn_gpool(
+            handle, first, n, dims_arg, C.byref(pool_dims), C.byref(p), C.byref(pp), C.byref(g), C.byref(pg),
+            C.byref(r) if r is not None else None, C.byref(pr) if pr is not None else None, float(policy_weight),
+            float(value_weight), C.byref(o) if o is not None else None, C.byref(d) if d is not None else None,
+            C.c_void_p(stream.cuda_stream)))
 
     def _grad_into(self, architecture: str, first, n, hidden_dim, params, grads, running, policy_weight, value_weight, out,
                    stream, more_weights: tuple = (), dropout=None) -> None:

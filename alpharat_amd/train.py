@@ -19,7 +19,10 @@ float32 and a hidden width that is a multiple of 32, at most 256. PyRatCNN (``ar
 ``ar_rows_grad_cnn``, alpharat_amd/csrc/train_cnn.h) as ``CNNModelConfig`` builds it by default: a stem, up to 8
 ``ResBlock``s, ``MLPPolicyHead`` and ``PointValueHead``, ``channels`` and ``hidden_dim`` multiples of 32 up to 256,
 ``player_dim`` up to 256, boards of 2 to 256 cells, ``n * width * height <= 2**22``; the reference trains it with
-``augment=False``. AMP, KataGoCNN, and for PyRatCNN the gpool block, the pooled value head and dropout are not built.
+``augment=False``. ``GPoolCNNGradStep`` (``ar_rows_grad_cnn_gpool``, alpharat_amd/csrc/train_gpool.h) is that step for a trunk of
+any mix of ``ResBlock`` and ``GPoolResBlock`` (``gpool_channels`` up to 256) with dropout behind the ReLU of
+``player_encoder`` and of ``combiner``: the network configs/train_cnn_7x7.yaml describes. ``CNNGradStep`` keeps refusing
+both. AMP, KataGoCNN and PyRatCNN's pooled value head are not built.
 
 Dropout is opt-in: without ``dropout_seed`` a model whose ``nn.Dropout`` has ``p != 0`` is refused, as it always was (the
 architectures' default is 0.0; the reference's configs/model/symmetric.yaml sets ``dropout: 0.1``). With
@@ -109,6 +112,10 @@ class _GradStep:
         """what the ``RowSet`` method takes for the network's widths: ``hidden_dim``, unless there are more"""
         return self.hidden_dim
 
+    def _dims_args(self) -> tuple:
+        """the ``RowSet`` method's arguments between ``n`` and ``params``"""
+        return (self._dims(),)
+
     def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
         import torch
 
@@ -125,7 +132,7 @@ class _GradStep:
         # nn.Dropout is the identity in eval mode: no mask then, and the counter stays
         dropping = training and self.dropout_seed is not None and self.dropout_p != 0
         more = dict(dropout=(self.dropout_p, self.dropout_seed, self.dropout_step)) if dropping else {}
-        getattr(rowset, self._ROWSET_METHOD)(first, n, self._dims(), params, self.grads, self.running if training else None,
+        getattr(rowset, self._ROWSET_METHOD)(first, n, *self._dims_args(), params, self.grads, self.running if training else None,
                                              *self._weights(), out, **more)
         for k, p in self.params.items():
             p.grad = self.grads[k]
@@ -244,6 +251,25 @@ class LocalValueGradStep(MLPGradStep):
         return _GradStep.step(self, rowset, first, n, outputs)
 
 
+def _cnn_block_count(model) -> int:
+    """the number of ``blocks.<b>`` of a PyRatCNN, at most 8 (``ValueError`` above): CNNGradStep's and GPoolCNNGradStep's"""
+    import re
+
+    names = [k.removeprefix(_PREFIX) for k, _ in list(model.named_parameters()) + list(model.named_buffers())]
+    n_blocks = 1 + max((int(m.group(1)) for m in (re.match(r"blocks\.(\d+)\.", k) for k in names) if m), default=-1)
+    if n_blocks > 8:
+        raise ValueError(f"the model has {n_blocks} residual blocks: the step takes at most 8")
+    return n_blocks
+
+
+def _refuse_other_cnns(keys: list) -> None:
+    """what neither CNN step computes, under one message each: KataGoCNN and the pooled value head"""
+    if any(k.startswith("scalar_encoder.") for k in keys):
+        raise ValueError("the model has a scalar_encoder (KataGoCNN): this step is PyRatCNN's")
+    if any(k.startswith("value_head.mlp.") for k in keys):
+        raise ValueError("the model has a value_head.mlp (PooledValueHead): the step is built for PointValueHead")
+
+
 class CNNGradStep(_GradStep):
     """``MLPGradStep`` for PyRatCNN as the reference's ``CNNModelConfig`` builds it by default: ``stem`` and ``stem_bn``,
     ``ResBlock``s, ``player_encoder``, ``combiner``, ``MLPPolicyHead`` and ``PointValueHead`` (an ``_orig_mod.`` prefix is
@@ -256,8 +282,6 @@ class CNNGradStep(_GradStep):
     _NAME, _ROWSET_METHOD = "PyRatCNN", "grad_cnn_into"
 
     def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0, dropout_seed: int | None = None) -> None:
-        import re
-
         import torch
 
         from .shards import cnn_bn_modules, cnn_param_keys, cnn_running_keys
@@ -266,24 +290,19 @@ class CNNGradStep(_GradStep):
             if isinstance(m, torch.nn.Dropout) and float(m.p) != 0:
                 raise ValueError(f"dropout {float(m.p)} is not supported: dropout is not built for PyRatCNN's step yet, "
                                  "with a dropout_seed or without")
-        names = [k.removeprefix(_PREFIX) for k, _ in list(model.named_parameters()) + list(model.named_buffers())]
-        n_blocks = 1 + max((int(m.group(1)) for m in (re.match(r"blocks\.(\d+)\.", k) for k in names) if m), default=-1)
-        if n_blocks > 8:
-            raise ValueError(f"the model has {n_blocks} residual blocks: the step takes at most 8")
-        self.n_blocks = n_blocks
+        self.n_blocks = n_blocks = _cnn_block_count(model)
         self._PARAM_KEYS, self._RUNNING_KEYS = cnn_param_keys(n_blocks), cnn_running_keys(n_blocks)
         self._TRACKED = tuple((f"{bn}.num_batches_tracked", 1) for bn in cnn_bn_modules(n_blocks))
         super().__init__(model, policy_weight, value_weight, None)
 
     def _refuse(self, named: dict, buffers: dict) -> None:
         keys = list(named) + list(buffers)
-        if any(k.startswith("scalar_encoder.") for k in keys):
-            raise ValueError("the model has a scalar_encoder (KataGoCNN): this step is PyRatCNN's")
+        if any(k.startswith("scalar_encoder.") for k in keys):  # (named first, as it always was)
+            _refuse_other_cnns(keys)
         for part in ("pool_bn", "pool_conv", "pool_linear"):
             if any(k.startswith("blocks.") and f".{part}." in k for k in keys):
                 raise ValueError(f"a block has a {part} (GPoolResBlock): the step is built for ResBlocks only")
-        if any(k.startswith("value_head.mlp.") for k in keys):
-            raise ValueError("the model has a value_head.mlp (PooledValueHead): the step is built for PointValueHead")
+        _refuse_other_cnns(keys)
 
     def _read_dims(self) -> None:
         stem, enc, comb = self.params["stem.weight"], self._weight("player_encoder.0.weight"), self._weight("combiner.0.weight")
@@ -312,12 +331,69 @@ class CNNGradStep(_GradStep):
         return super().step(rowset, first, n, outputs)
 
 
+class GPoolCNNGradStep(CNNGradStep):
+    """``CNNGradStep`` for the PyRatCNN the reference's configs train (configs/train_cnn_7x7.yaml: ``res, res, gpool(32)``,
+    ``dropout: 0.1``): a trunk of any mix of ``ResBlock`` and ``GPoolResBlock``, and dropout from the library's seeded mask
+    (``ar_rows_grad_cnn_gpool``, alpharat_amd/csrc/train_gpool.h). ``blocks`` is read from the model: a block is a gpool
+    block iff it has ``pool_conv.weight``, whose first dimension is its ``gpool_channels`` (at most 256). Dropout as the MLP
+    steps handle it: without ``dropout_seed`` a ``Dropout`` with ``p != 0`` is refused; with one, all ``Dropout`` modules
+    have one ``p`` in ``[0, 1)`` and every training-mode step applies the mask behind the ReLU of ``player_encoder`` and of
+    ``combiner`` (``dropout_mask`` calls 0 .. 3) and ``dropout_step`` grows by one. ``ValueError`` for a ``PooledValueHead``
+    or a KataGoCNN, with ``CNNGradStep``'s messages, and for what it refuses otherwise. A model of ``ResBlock``s alone gives
+    the bytes ``CNNGradStep`` gives."""
+
+    _ROWSET_METHOD = "grad_cnn_gpool_into"
+
+    def __init__(self, model, policy_weight: float = 1.0, value_weight: float = 1.0, dropout_seed: int | None = None) -> None:
+        from .shards import cnn_gpool_bn_modules, cnn_gpool_param_keys, cnn_gpool_running_keys
+
+        named = {k.removeprefix(_PREFIX): v for k, v in model.named_parameters()}
+        self.n_blocks = n_blocks = _cnn_block_count(model)
+        blocks = []
+        for b in range(n_blocks):
+            w = named.get(f"blocks.{b}.pool_conv.weight")
+            if w is None:  # a ResBlock: it may have nothing of a pool path, whose parameters would get no gradient
+                for k in named:
+                    if k.startswith((f"blocks.{b}.pool_bn.", f"blocks.{b}.pool_linear.")):
+                        raise ValueError(f"blocks.{b} has {k.split('.', 2)[2]} and no pool_conv.weight: neither a ResBlock nor a "
+                                         "GPoolResBlock")
+            blocks.append(0 if w is None else int(w.shape[0]))
+            if blocks[-1] > 256:
+                raise ValueError(f"blocks.{b} has gpool_channels {blocks[-1]}: the step takes at most 256")
+        self.blocks = tuple(blocks)
+        self._PARAM_KEYS, self._RUNNING_KEYS = cnn_gpool_param_keys(self.blocks), cnn_gpool_running_keys(self.blocks)
+        self._TRACKED = tuple((f"{bn}.num_batches_tracked", 1) for bn in cnn_gpool_bn_modules(self.blocks))
+        _GradStep.__init__(self, model, policy_weight, value_weight, dropout_seed)
+
+    def _refuse(self, named: dict, buffers: dict) -> None:
+        _refuse_other_cnns(list(named) + list(buffers))
+
+    def _read_dims(self) -> None:
+        super()._read_dims()
+        for b, g in enumerate(self.blocks):
+            if g:
+                conv, lin = self.params[f"blocks.{b}.pool_conv.weight"], self._weight(f"blocks.{b}.pool_linear.weight")
+                if tuple(conv.shape) != (g, self.channels, 1, 1) or tuple(lin.shape) != (self.channels, 2 * g):
+                    raise ValueError(f"blocks.{b}: pool_conv.weight has shape {tuple(conv.shape)} and pool_linear.weight "
+                                     f"{tuple(lin.shape)}, not ({g}, {self.channels}, 1, 1) and ({self.channels}, {2 * g})")
+
+    def _dims_args(self) -> tuple:
+        return self._dims(), self.blocks
+
+    def step(self, rowset: RowSet, first: int, n: int, outputs: bool = False):
+        """``CNNGradStep.step`` under the same contract; ``num_batches_tracked`` of every BatchNorm2d, each ``pool_bn``
+        included, grows by one in training mode, and with a ``dropout_seed`` so does ``dropout_step``."""
+        return _GradStep.step(self, rowset, first, n, outputs)
+
+
 def dropout_mask(seed: int, step: int, call: int, n: int, hidden_dim: int, p: float, device_index: int = 0):
     """The mask of BatchNorm call ``call`` of training step ``step`` under ``dropout_seed`` ``seed``, as the device's own
     generator gives it (``ar_train_dropout_mask``): a bool tensor ``(n, hidden_dim)`` on the device, True where the element
     is kept. ``call``: PyRatMLP and LocalValueMLP 0 ``trunk.3``, 1 ``trunk.7``; SymmetricMLP 0 ``shared_encoder``, 1 / 2
-    ``player_encoder`` on P1's / P2's rows, 3 / 4 ``trunk.3``, 5 / 6 ``trunk.7``. ``ValueError`` for ``p`` outside ``[0, 1)``,
-    ``n`` outside 1 .. 65536 or a ``hidden_dim`` that is no multiple of 32 up to 256."""
+    ``player_encoder`` on P1's / P2's rows, 3 / 4 ``trunk.3``, 5 / 6 ``trunk.7``; PyRatCNN (``GPoolCNNGradStep``) 0 / 1
+    ``player_encoder`` on P1's / P2's rows with ``hidden_dim`` = ``player_dim``, 2 / 3 ``combiner`` on P1's / P2's rows.
+    ``ValueError`` for ``p`` outside ``[0, 1)``, ``n`` outside 1 .. 65536 or a ``hidden_dim`` that is no multiple of 32 up
+    to 256."""
     import ctypes as C
 
     import torch

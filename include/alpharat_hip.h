@@ -639,7 +639,7 @@ int ar_train_dropout_mask(uint64_t seed, uint64_t step, uint32_t call, uint64_t 
  *   logits_i = policy(cat(h_i, agg)), value_i = softplus(value(cat(h_i, agg))).
  * Every BatchNorm module is called once per step. The gradient of a tensor shared by both players is the sum of its two
  * calls' contributions, P1's before P2's. Not built, and refused by whoever fills these structs from a model
- * (alpharat_amd/train.py): GPoolResBlock, PooledValueHead, dropout, KataGoCNN. */
+ * (alpharat_amd/train.py): PooledValueHead, KataGoCNN; GPoolResBlock and dropout are ar_rows_grad_cnn_gpool's, below. */
 typedef struct ArCnnDims { uint32_t channels, player_dim, hidden_dim, n_blocks; } ArCnnDims;
 typedef struct ArCnnBlock {     /* a ResBlock's parameters in named_parameters() order */
     float *bn1_w, *bn1_b;       /* [C]          */
@@ -670,6 +670,39 @@ typedef struct ArCnnBnStats { /* running statistics [C], updated in place */
 int ar_rows_grad_cnn(ArRowSet* set, uint64_t first, uint64_t n, const ArCnnDims* dims, const ArCnnTensors* params,
                      const ArCnnTensors* grads, const ArCnnBnStats* running, float policy_weight, float value_weight,
                      const ArTrainOut* out, void* stream);
+
+/* ---- PyRatCNN with GPoolResBlocks in its trunk and dropout (alpharat/nn/models/cnn/blocks.py; what
+ * configs/train_cnn_7x7.yaml trains: res, res, gpool(32), dropout 0.1) --------------------------------------------------------
+ * ar_rows_grad_cnn with any mix of ResBlock and GPoolResBlock among its blocks. A gpool block with G = gpool_channels has,
+ * beside the ResBlock's regular path,
+ *   ap = relu(pool_bn(x_b)); pz [n hw][G] = pool_conv(ap) (1x1, no bias); pool_cat [n][2G] = [mean | max over the hw cells];
+ *   x_b+1 = (conv2(..) + pool_linear(pool_cat) broadcast over the cells) + x_b.
+ * The mean is summed in cell order in double and rounded once; the maximum's gradient is shared evenly among the cells
+ * that equal it, as torch's amax does. pool_bn is a BatchNorm module of its own with its own running statistics.
+ * ArCnnPoolBlock holds a block's five further parameters in named_parameters() order, behind the block's six.
+ * Dropout (p > 0): inverted dropout behind the ReLU of player_encoder and of combiner, from the generator described above.
+ * Each module is called once per player on that player's n rows: call 0, 1 = player_encoder on P1's, P2's rows, call 2, 3 =
+ * combiner on P1's, P2's rows; element e = row * H + column, row within the call's n rows, H = player_dim resp. hidden_dim.
+ * The trunk has no dropout.
+ * pool_dims == NULL or all zeros, and dropout == NULL or p == 0: ar_rows_grad_cnn launch for launch (that function is a call
+ * of this one with NULLs). Per gpool block 21 launches more, and the workspace grows by ap [n hw][C], pz [n hw][G], pool_cat
+ * [n][2G] and the tie counts [n][G]; with any gpool block once by one more array of n*hw*C floats, dpz [n hw][max G], po / dpo
+ * [n][C] and dcat [n][2 max G]. AR_E_INVALID before any launch, nothing written, for ar_rows_grad_cnn's list and
+ * for: a gpool_channels above 256; a null pool tensor (or, with `running`, a null pool statistic) of a block whose
+ * gpool_channels != 0; n * hw above 65535 * 64 with a gpool block; p < 0, p >= 1 or NaN. */
+typedef struct ArCnnPoolDims { uint32_t gpool_channels[8]; } ArCnnPoolDims; /* 0: a ResBlock; 1 .. 256: a GPoolResBlock */
+typedef struct ArCnnPoolBlock {
+    float *pool_bn_w, *pool_bn_b;         /* [C]           */
+    float* pool_conv_w;                   /* [G][C][1][1]  */
+    float *pool_linear_w, *pool_linear_b; /* [C][2G], [C]  */
+} ArCnnPoolBlock;
+typedef struct ArCnnPoolTensors { ArCnnPoolBlock blocks[8]; } ArCnnPoolTensors;
+typedef struct ArCnnPoolStats { float *pool_bn_mean, *pool_bn_var; } ArCnnPoolStats; /* pool_running: an array of 8 */
+int ar_rows_grad_cnn_gpool(ArRowSet* set, uint64_t first, uint64_t n, const ArCnnDims* dims, const ArCnnPoolDims* pool_dims,
+                           const ArCnnTensors* params, const ArCnnPoolTensors* pool_params, const ArCnnTensors* grads,
+                           const ArCnnPoolTensors* pool_grads, const ArCnnBnStats* running, const ArCnnPoolStats* pool_running,
+                           float policy_weight, float value_weight, const ArTrainOut* out, const ArTrainDropout* dropout,
+                           void* stream);
 
 #ifdef __cplusplus
 }

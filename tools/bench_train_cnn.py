@@ -15,6 +15,11 @@ The epochs are planned with augment=False, the reference's setting for this arch
 windows (one epoch each) after a warm-up epoch, a host clock around a loop that ends in one torch.cuda.synchronize().
 --steps N instead runs N steps of this library's side only and prints nothing: the process a kernel trace is taken of.
 Prints one JSON line and appends it to --out (profiles/train_cnn_bench.jsonl).
+
+--gpool-last G makes the last block a GPoolResBlock of G gpool_channels and --dropout P trains both sides with dropout P
+(configs/train_cnn_7x7.yaml is --gpool-last 32 --dropout 0.1): this library's side is then GPoolCNNGradStep over
+ar_rows_grad_cnn_gpool with its seeded masks, today's side tests/_gpool_train_torch.py with torch's own dropout, the line
+carries ``gpool_last`` and ``dropout`` and --out defaults to profiles/train_gpool_bench.jsonl. Without either flag the run, the classes and the line are what they were.
 """
 from __future__ import annotations
 
@@ -44,8 +49,13 @@ def main() -> None:
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--steps", type=int, default=0, help="run this many steps of the library's side and stop (for a kernel trace)")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "train_cnn_bench.jsonl"))
+    ap.add_argument("--gpool-last", type=int, default=0, help="gpool_channels of the last block (0: a ResBlock)")
+    ap.add_argument("--dropout", type=float, default=0.0)
+    ap.add_argument("--out", default=None, help="the record the line is appended to: profiles/train_cnn_bench.jsonl, with "
+                    "--gpool-last or --dropout profiles/train_gpool_bench.jsonl")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = str(ROOT / "profiles" / ("train_gpool_bench.jsonl" if a.gpool_last or a.dropout else "train_cnn_bench.jsonl"))
 
     import _cnn_train_torch as CT
     import _train_cnn_np as NC
@@ -56,6 +66,14 @@ def main() -> None:
     w = h = 7
     Ch, PD, HD, B = a.channels, 32, 64, a.blocks
     tensors = NC.random_cnn(w, h, Ch, PD, HD, B, 0, decided=False)
+    gpool = bool(a.gpool_last or a.dropout)
+    if gpool:
+        import _gpool_train_torch as GT
+        import _train_gpool_np as NG
+        from alpharat_amd.dataset import GPoolCNNGradStep
+
+        trunk = (0,) * (B - 1) + (a.gpool_last,) if B else ()
+        tensors = NG.random_gpool_cnn(w, h, Ch, PD, HD, trunk, 0, decided=False)
     rs = shards.RowSet(7, 7, (a.positions // 12 + 1) * a.max_turns + a.positions)
     n, next_index = 0, 0
     while n < a.positions:  # (as tools/bench_rows.py: runs are added until the set is large enough)
@@ -72,8 +90,12 @@ def main() -> None:
     batch = a.batch
     rows = n - n % batch
 
-    model = CT.CNN(w, h, Ch, PD, HD, B, sd=tensors).to(device).train()
-    step = CNNGradStep(model, 1.0, 1.0)
+    if gpool:
+        model = GT.GPoolCNN(w, h, Ch, PD, HD, trunk, dropout=a.dropout, sd=tensors).to(device).train()
+        step = GPoolCNNGradStep(model, 1.0, 1.0, dropout_seed=0 if a.dropout else None)
+    else:
+        model = CT.CNN(w, h, Ch, PD, HD, B, sd=tensors).to(device).train()
+        step = CNNGradStep(model, 1.0, 1.0)
     opt = torch.optim.AdamW(model.parameters(), lr=a.lr)
 
     def ours(epoch, limit=0):
@@ -113,8 +135,9 @@ def main() -> None:
         losses = []
         for b in ds.epoch_iter(batch, epoch=epoch, seed=0, augment=False):
             opt2.zero_grad(set_to_none=True)
-            ls = CT.losses(CT.forward(p, b["observation"], w, h, running), b["policy_p1"], b["policy_p2"], b["value_p1"],
-                           b["value_p2"], 1.0, 1.0)
+            logits = (GT.forward(p, b["observation"], w, h, running, dropout=a.dropout) if gpool
+                      else CT.forward(p, b["observation"], w, h, running))
+            ls = CT.losses(logits, b["policy_p1"], b["policy_p2"], b["value_p1"], b["value_p2"], 1.0, 1.0)
             ls["loss"].backward()
             opt2.step()
             losses.append(ls["loss"].detach())
@@ -122,7 +145,8 @@ def main() -> None:
 
     today_times, today_loss = timed(today)
     rs.close()
-    line = json.dumps(dict(board="7x7", channels=Ch, blocks=B, player_dim=PD, hidden_dim=HD, games=games, positions=n, batch=batch,
+    more = dict(gpool_last=a.gpool_last, dropout=a.dropout) if gpool else {}
+    line = json.dumps(dict(board="7x7", channels=Ch, blocks=B, **more, player_dim=PD, hidden_dim=HD, games=games, positions=n, batch=batch,
                            rows=rows, windows=a.windows, optimizer=f"AdamW(lr={a.lr})", augment=False,
                            grad_secs=round(statistics.median(ours_times), 5),
                            grad_secs_min_max=[round(min(ours_times), 5), round(max(ours_times), 5)],
